@@ -6,10 +6,19 @@ the data loader).  N>1: one process per GPU, 256 images per rank (weak scaling),
 gradients averaged with RCCL all-reduces issued block by block during the
 backward (DDP in the reference, VIT:287).  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--graph] [--no-c3] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--graph] [--dump-outputs DIR] [--full]
 
-At N=1 the line also carries ``c3``: the CLIP-HBA step (BASELINE configs[2]) timed in fp32, the
-reference's precision, and in the bf16 opt-in -- an extra key, not the headline value.
+A plain run sets up, warms up, times the K steps and prints the headline line, nothing else.
+``--dump-outputs DIR`` also writes what the last timed step computed (its loss, its logits and a
+fixed seeded sample of the updated parameters) as ``DIR/<name>.npy``; the seeds are fixed, so two
+builds run with the same arguments see the same weights and batch and can be compared array by array.
+
+``--full`` adds every other measurement, each of which costs GPU or host time of its own: the GPU's
+clock / power telemetry and the HIP events around the weight-gradient and optimizer launches in the
+timed steps, the standalone weight-gradient leg and the ``roofline`` key, the CPU baseline
+(``--no-cpu`` drops it) and, at N=1, the ``c3`` key (``--no-c3`` drops it): the CLIP-HBA step
+(BASELINE configs[2]) timed in fp32, the reference's precision, and in the bf16 opt-in -- an extra
+key, not the headline value.
 
 ``--gpus N`` without a torchrun environment launches its own N ranks (one
 process per GPU, ``torch.distributed.run`` on 127.0.0.1, as the reference's
@@ -48,11 +57,17 @@ def parse(argv=None):
     ap.add_argument("--graph", action="store_true",
                     help="replay one captured HIP graph per step (ROCm replays graph branches serially, so the "
                          "two-stream overlap is lost; eager is faster with overlap on)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: GPU telemetry, per-launch HIP events, "
+                         "the standalone weight-gradient leg / roofline, the C3 legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, logits and a seeded sample of the updated parameters "
+                         "as DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-overlap", action="store_true", help="weight gradients inline instead of on a side stream")
-    ap.add_argument("--no-probe", action="store_true", help="no HIP events around the weight-gradient launches")
-    ap.add_argument("--no-c3", action="store_true", help="skip the CLIP-HBA (config C3) leg")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: no HIP events around the weight-gradient launches")
+    ap.add_argument("--no-c3", action="store_true", help="with --full: skip the CLIP-HBA (config C3) leg")
     ap.add_argument("--dry", action="store_true", help="CPU/gloo launcher + gradient-averaging check, no GPU")
     return ap.parse_args(argv)
 
@@ -371,6 +386,92 @@ class GpuTelemetry:
 
 # ----------------------------------------------------------------------------
 
+PARAM_SAMPLE = 1 << 22  # elements of the flattened parameters written by --dump-outputs (16 MiB as float32)
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    """What a caller of the timed step holds after its last call, as float32 .npy files: the step's
+    loss (``loss``), its logits (``logits``, [B, classes]) and the parameters the optimizer left
+    (``params_sample``: PARAM_SAMPLE elements of the parameters flattened in ``named_parameters()``
+    order, at indices drawn once from a CPU generator with a fixed seed; all 86.6 M would be 346 MB)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    flat = torch.cat([p.detach().float().reshape(-1) for _, p in model.named_parameters()])
+    idx = torch.randint(0, flat.numel(), (PARAM_SAMPLE,), generator=torch.Generator().manual_seed(4321))
+    arrays = {"loss": loss.detach().float().reshape(1), "logits": logits.detach().float(),
+              "params_sample": flat[idx.to(flat.device)]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
+def roofline_leg(dev, main_stream, B, wg):
+    """--full: the ``roofline`` key.  Times the weight-gradient kernel standalone and joins it with the
+    in-step figures of the probe (``wg``, or None) and the committed counter files."""
+    import torch
+    from vit_amd import ops
+    # --- standalone leg of the same kernel as the step runs it: the MLP weight-gradient pair
+    #     (dW2 = dy^T act, M = B*197, 768 x 3072, and dW1 = dpre^T h2, 3072 x 768) as one grouped
+    #     launch at the step's split, then its split-K slab sums (the block's reduction launch),
+    #     alone on the GPU, HIP events on its stream; both launches count in the time
+    M = B * 197
+    bf = torch.bfloat16
+    dy2, act = torch.randn(M, 768, device=dev).to(bf), torch.randn(M, 3072, device=dev).to(bf)
+    dpre, h2 = torch.randn(M, 3072, device=dev).to(bf), torch.randn(M, 768, device=dev).to(bf)
+    dw2, dw1 = torch.empty(768, 3072, device=dev), torch.empty(3072, 768, device=dev)
+
+    def pair_step():
+        cb = ops.ColBatch()
+        ops.linear_wgrad_pair((dy2, act, dw2), (dpre, h2, dw1), cb)
+        cb.launch()
+
+    with torch.cuda.stream(main_stream):
+        for _ in range(10):
+            pair_step()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = 20
+        e0.record()
+        for _ in range(reps):
+            pair_step()
+        e1.record()
+        torch.cuda.synchronize(dev)
+    k_ms = e0.elapsed_time(e1) / reps
+    k_flop = 2.0 * 2.0 * M * 3072 * 768
+    k_tflops = k_flop / (k_ms * 1e-3) / 1e12
+    traffic, traffic_src, traffic_sha = _pmc_traffic("pmc_traffic_wgrad_pair.json")
+    mfma_busy, busy_src, busy_sha = _pmc_mfma_busy()
+    src_sha = wgrad_src_sha()
+    if wg is not None:
+        roof = {"bound": "mfma", "kernel": "big::pp_kernel2 / pp_kernel (split-K weight-gradient GEMM, 256x256x32 "
+                                           "ping-pong; fc2+fc1 and proj+qkv as grouped pairs; VIT_GEMM_WGRAD=11 selects "
+                                           "the w4 kernel): every bf16 dW = dY^T X of the step",
+                "achieved": wg["tflops"], "peak": round(PEAK_BF16_TFLOPS, 1), "unit": "TFLOP/s",
+                "frac": round(wg["tflops"] / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
+                "measured": "in-step: HIP events around each launch on the side stream it runs on, over the timed "
+                            "steps (its CUs are shared with the caller stream's kernels); the split-K slab sums run "
+                            "in each block's single reduction launch, which the standalone leg includes",
+                "launches_per_step": wg["launches_per_step"], "ms_per_step": wg["ms_per_step"],
+                "avg_launch_ms": wg["avg_launch_ms"], "flop_per_step": wg["flop_per_step"],
+                "standalone": {"shape": "MLP pair dW2 (768x3072) + dW1 (3072x768), M=%d, grouped launch + slab-sum "
+                                        "launch" % M, "ms": round(k_ms, 4),
+                               "achieved": round(k_tflops, 1), "frac": round(k_tflops / PEAK_BF16_TFLOPS, 4),
+                               "flop_per_launch": k_flop},
+                "traffic_unit": "HBM bytes per standalone pair (grouped launch + its slab sums; FETCH_SIZE x2 + "
+                                "WRITE_SIZE, rocprofv3 --pmc passes, %s)" % traffic_src,
+                "mfma_busy": mfma_busy,
+                "mfma_busy_unit": "SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE/8) of the weight-gradient "
+                                  "launches in the step's counter passes (dispatches serialized; %s)" % busy_src,
+                # the counter files record the hash of the kernel sources they were taken on
+                "counters_src_sha": {"kernel_sources": src_sha, "traffic": traffic_sha, "mfma_busy": busy_sha},
+                "counters_match_kernel": traffic_sha == src_sha and busy_sha == src_sha}
+    else:
+        roof = {"bound": "mfma", "kernel": "MLP weight-gradient pair (ping-pong kernel), standalone",
+                "achieved": round(k_tflops, 1), "peak": round(PEAK_BF16_TFLOPS, 1), "unit": "TFLOP/s",
+                "frac": round(k_tflops / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "kernel_ms": round(k_ms, 4),
+                "flop_per_launch": k_flop}
+    return roof
+
+
 def main(a):
     import torch
     import torch.distributed as dist
@@ -402,8 +503,14 @@ def main(a):
     red_events = []
     sgd_events = []  # HIP events around the optimizer's one launch in the timed steps (a kernel no round changes)
 
-    def step(record=False, sgd=False):
-        loss = vit_amd.cross_entropy(model(x), y)
+    last = {}  # --dump-outputs: the logits of the last timed step
+
+    def step(record=False, sgd=False, keep=False):
+        logits = model(x)
+        if keep:
+            last["logits"] = logits
+        loss = vit_amd.cross_entropy(logits, y)
+        del logits
         loss.backward()
         if world > 1:
             if record:
@@ -440,36 +547,40 @@ def main(a):
         if use_graph:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                gloss = step()
+                gloss = step(keep=a.dump_outputs is not None)
             graph.replay()  # one untimed replay
             torch.cuda.synchronize(dev)
 
         # --- timed region: exactly K steps, barrier + synchronize on both sides.  HIP events on
-        #     the caller's stream between steps give per-step times (median); HIP events around
-        #     every weight-gradient launch (on the side stream it runs on) give that kernel's
-        #     live in-step duration for the roofline line.
-        probe = [] if (not a.no_probe and graph is None) else None
+        #     the caller's stream between steps give per-step times (median); with --full, HIP
+        #     events around every weight-gradient launch (on the side stream it runs on) give that
+        #     kernel's live in-step duration for the roofline line.
+        probe = [] if (a.full and not a.no_probe and graph is None) else None
         ops.WGRAD_PROBE[0] = probe
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
-        telem = GpuTelemetry(local)
+        telem = GpuTelemetry(local) if a.full else None
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize(dev)
-        telem.start()
+        if telem is not None:
+            telem.start()
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(a.steps):
             if graph is not None:
                 graph.replay()
             else:
-                step(record=world > 1, sgd=True)
+                tloss = step(record=a.full and world > 1, sgd=a.full,
+                             keep=a.dump_outputs is not None and i == a.steps - 1)
             marks[i + 1].record()
         torch.cuda.synchronize(dev)
         if world > 1:
             dist.barrier()
         el = time.perf_counter() - t0
-        box = telem.stop()
+        box = telem.stop() if telem is not None else None
         ops.WGRAD_PROBE[0] = None
+        if a.dump_outputs is not None and rank == 0 and a.steps > 0:
+            dump_outputs(a.dump_outputs, gloss if graph is not None else tloss, last["logits"], model)
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]
     el_rank = el
     per_rank = [el_rank]
@@ -492,34 +603,7 @@ def main(a):
               "avg_launch_ms": round(tot_ms / per_step, 4), "flop_per_step": tot_fl,
               "tflops": round(tot_fl / (tot_ms * 1e-3) / 1e12, 1)}
 
-    # --- standalone leg of the same kernel as the step runs it: the MLP weight-gradient pair
-    #     (dW2 = dy^T act, M = B*197, 768 x 3072, and dW1 = dpre^T h2, 3072 x 768) as one grouped
-    #     launch at the step's split, then its split-K slab sums (the block's reduction launch),
-    #     alone on the GPU, HIP events on its stream; both launches count in the time
-    M = B * 197
-    bf = torch.bfloat16
-    dy2, act = torch.randn(M, 768, device=dev).to(bf), torch.randn(M, 3072, device=dev).to(bf)
-    dpre, h2 = torch.randn(M, 3072, device=dev).to(bf), torch.randn(M, 768, device=dev).to(bf)
-    dw2, dw1 = torch.empty(768, 3072, device=dev), torch.empty(3072, 768, device=dev)
-
-    def pair_step():
-        cb = ops.ColBatch()
-        ops.linear_wgrad_pair((dy2, act, dw2), (dpre, h2, dw1), cb)
-        cb.launch()
-
-    with torch.cuda.stream(main_stream):
-        for _ in range(10):
-            pair_step()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        reps = 20
-        e0.record()
-        for _ in range(reps):
-            pair_step()
-        e1.record()
-        torch.cuda.synchronize(dev)
-    k_ms = e0.elapsed_time(e1) / reps
-    k_flop = 2.0 * 2.0 * M * 3072 * 768
-    k_tflops = k_flop / (k_ms * 1e-3) / 1e12
+    roof = roofline_leg(dev, main_stream, B, wg) if a.full else None
     red_ms = None
     if red_events:
         torch.cuda.synchronize(dev)
@@ -539,37 +623,6 @@ def main(a):
     value = imgs / el
     ms = el / a.steps * 1e3
     step_tflops = value / world * STEP_FLOP_PER_IMG / 1e12
-    traffic, traffic_src, traffic_sha = _pmc_traffic("pmc_traffic_wgrad_pair.json")
-    mfma_busy, busy_src, busy_sha = _pmc_mfma_busy()
-    src_sha = wgrad_src_sha()
-    if wg is not None:
-        roof = {"bound": "mfma", "kernel": "big::pp_kernel2 / pp_kernel (split-K weight-gradient GEMM, 256x256x32 "
-                                           "ping-pong; fc2+fc1 and proj+qkv as grouped pairs; VIT_GEMM_WGRAD=11 selects "
-                                           "the w4 kernel): every bf16 dW = dY^T X of the step",
-                "achieved": wg["tflops"], "peak": round(PEAK_BF16_TFLOPS, 1), "unit": "TFLOP/s",
-                "frac": round(wg["tflops"] / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
-                "measured": "in-step: HIP events around each launch on the side stream it runs on, over the timed "
-                            "steps (its CUs are shared with the caller stream's kernels); the split-K slab sums run "
-                            "in each block's single reduction launch, which the standalone leg includes",
-                "launches_per_step": wg["launches_per_step"], "ms_per_step": wg["ms_per_step"],
-                "avg_launch_ms": wg["avg_launch_ms"], "flop_per_step": wg["flop_per_step"],
-                "standalone": {"shape": "MLP pair dW2 (768x3072) + dW1 (3072x768), M=%d, grouped launch + slab-sum "
-                                        "launch" % M, "ms": round(k_ms, 4),
-                               "achieved": round(k_tflops, 1), "frac": round(k_tflops / PEAK_BF16_TFLOPS, 4),
-                               "flop_per_launch": k_flop},
-                "traffic_unit": "HBM bytes per standalone pair (grouped launch + its slab sums; FETCH_SIZE x2 + "
-                                "WRITE_SIZE, rocprofv3 --pmc passes, %s)" % traffic_src,
-                "mfma_busy": mfma_busy,
-                "mfma_busy_unit": "SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE/8) of the weight-gradient "
-                                  "launches in the step's counter passes (dispatches serialized; %s)" % busy_src,
-                # the counter files record the hash of the kernel sources they were taken on
-                "counters_src_sha": {"kernel_sources": src_sha, "traffic": traffic_sha, "mfma_busy": busy_sha},
-                "counters_match_kernel": traffic_sha == src_sha and busy_sha == src_sha}
-    else:
-        roof = {"bound": "mfma", "kernel": "MLP weight-gradient pair (ping-pong kernel), standalone",
-                "achieved": round(k_tflops, 1), "peak": round(PEAK_BF16_TFLOPS, 1), "unit": "TFLOP/s",
-                "frac": round(k_tflops / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "kernel_ms": round(k_ms, 4),
-                "flop_per_launch": k_flop}
     out = {
         "metric": "images/sec ViT-B/16 224 train step bs=256 (whole job)",
         "value": round(value, 2),
@@ -588,22 +641,23 @@ def main(a):
                    "model": "vit_base_patch16_224", "global_batch": world * B, "per_gpu_batch": B,
                    "seq_len": 197, "parallelism": f"dp{world}", "launch": "hipgraph" if graph is not None else "eager",
                    "final_loss": round(final_loss, 4)},
-        "roofline": roof,
         "step_mfma": {"achieved_tflops": round(step_tflops, 1), "frac": round(step_tflops / PEAK_BF16_TFLOPS, 4),
                       "flop_per_img": STEP_FLOP_PER_IMG},
-        "box": box,
     }
+    if a.full:
+        out["roofline"] = roof
+        out["box"] = box
     if world > 1:
         out["per_rank_s"] = [round(v, 4) for v in per_rank]
         out["allreduce_exposed_ms_median"] = None if red_ms is None else round(red_ms, 3)
         out["allreduce"] = "overlapped per block (side stream)" if reducer is not None else "bucketed after backward"
-    if world == 1 and not a.no_c3:
+    if a.full and world == 1 and not a.no_c3:
         # extra key, not the headline: BASELINE configs[2] (C3) at the reference's fp32 and the bf16 opt-in
         out["c3"] = {"workload": "CLIP-HBA ViT-L/14 + DoRA train step (fwd+MSE+bwd+AdamW), BASELINE configs[2]",
                      "metric": "images/sec", "data": "synthetic images [64,3,224,224] + 66-D targets; random-init "
                                                      "weights (OpenAI weights absent offline)",
                      "f32": c3_leg(dev, "f32"), "bf16": c3_leg(dev, "bf16")}
-    if world == 1 and not a.no_cpu:
+    if a.full and world == 1 and not a.no_cpu:
         out["cpu_baseline"] = cpu_baseline(a.cpu_seconds)
     print(json.dumps(out), flush=True)
     if world > 1:

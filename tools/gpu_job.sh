@@ -5,7 +5,7 @@
 # steps:
 #   tests       pytest -m gpu (full GPU suite)         tests:<k>  only tests matching -k <k>
 #   smoke       __graft_entry__.smoke()
-#   bench       default bench line (bench.py, N=1)     bench:<args> with extra bench.py arguments
+#   bench       whole bench line (bench.py --full, N=1) bench:<args> with extra bench.py arguments
 #   prof        rocprofv3 kernel trace of the bench step + step summaries (trace_overlap, step_classes)
 #   pmc         counter passes over tools/step_probe.py: SQ/GRBM (with kernel trace), FETCH_SIZE,
 #               WRITE_SIZE -> pmc_step_classes.json (MFMA busy, HBM GB/s per kernel)
@@ -34,7 +34,7 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || fail smoke "$O/smoke.log"
       tail -1 "$O/smoke.log" ;;
     bench)
-      timeout -k 10 500 python -u bench.py $arg > "$O/bench.json" 2> "$O/bench.err" || fail bench "$O/bench.err"
+      timeout -k 10 500 python -u bench.py --full $arg > "$O/bench.json" 2> "$O/bench.err" || fail bench "$O/bench.err"
       cat "$O/bench.json" ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- \

@@ -8,7 +8,7 @@ O=gpurun_out/final
 rm -rf $O; mkdir -p $O
 bash tools/job_fulltest.sh || exit 1
 cp gpurun_out/pytest_gpu_full.log gpurun_out/smoke.log $O/
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \

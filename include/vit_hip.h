@@ -32,13 +32,18 @@ enum {
   VIT_EPI_GELU_BWD = 3,   /* C = acc * aux (aux = the gelu'(pre) BIAS_GELU saved) */
   VIT_EPI_PATCH = 4,      /* patch-embed row remap + pos_embed                 */
   VIT_EPI_BIAS_QGELU = 5, /* QuickGELU variant (OpenAI CLIP towers): C = qgelu'(pre) */
-  VIT_EPI_QGELU_BWD = 6
+  VIT_EPI_QGELU_BWD = 6,
+  /* 7 is taken inside the library (accumulate into C).  Additive to ABI 10, forward (RC x RC) layout only: */
+  VIT_EPI_BIAS_GELU_FWD = 8,  /* pre = acc+bias: C = gelu_erf(pre); nothing else written, aux_out ignored */
+  VIT_EPI_BIAS_QGELU_FWD = 9  /* the same with QuickGELU */
 };
 
 int vit_abi_version(void); /* 10 (round 6): vit_blaslt_workspace / vit_gemm_lib removed -- the plain bf16
                               * forward / input-gradient GEMMs run the hand-written 4-wave kernel (csrc/
                               * gemm_g4.hip), the library links no vendor BLAS; 9: those two hooks (hipBLASLt);
-                              * 8: vit_gemm_ms / vit_gemm_ms_config and the banded attention backward removed */
+                              * 8: vit_gemm_ms / vit_gemm_ms_config and the banded attention backward removed.
+                              * Additive to 10 (no entry point or argument changed): the act-only epilogue codes
+                              * VIT_EPI_BIAS_GELU_FWD / VIT_EPI_BIAS_QGELU_FWD and vit_eval_metrics */
 
 /* Generic MFMA GEMM C[i][j] = epi(sum_r P(i,r) Q(j,r)); layouts RC (r contiguous)
  * or CR (i/j contiguous).  Backs every nn.Linear of timm's ViT reached from
@@ -91,7 +96,10 @@ int vit_gemm_streamk_workspace(void* stream, float* part, int64_t part_bytes, in
 int vit_gemm_rc_chunk_rows(int M, int64_t ld);
 
 /* F.linear forward, Y = X W^T + b with fused epilogue (timm Attention.qkv/proj,
- * Mlp.fc1+GELU / fc2 + residual, head; under VIT:138-139 autocast). */
+ * Mlp.fc1+GELU / fc2 + residual, head; under VIT:138-139 autocast).  With VIT_EPI_BIAS_GELU_FWD /
+ * VIT_EPI_BIAS_QGELU_FWD (passes no backward follows: VIT:167-204's validate, frozen CLIP blocks) Y is the
+ * activation itself, bit for bit what the pair code stores into act_out on the same kernel path, and
+ * act_out may be NULL. */
 int vit_linear_fwd(int dtype, int out_dtype, int epi, int M, int N, int K, const void* X, int64_t ldx,
                    const void* W, const float* bias, void* Y, int64_t ldy, const void* resid,
                    void* act_out, void* stream);
@@ -234,6 +242,17 @@ int vit_cross_entropy_fwd(int B, int C, const float* logits, int64_t ld, const i
                           float* row_loss, float* loss, void* stream);
 int vit_cross_entropy_bwd(int dtype_out, int B, int C, const float* logits, int64_t ld, const int64_t* target,
                           const float* row_lse, const float* grad_loss, void* dlogits, int64_t ldd, void* stream);
+
+/* Validation metrics of one batch (VIT:167-204's validate: F.cross_entropy(outputs, targets).item(),
+ * outputs.max(1), predicted.eq(targets).sum().item() per batch) accumulated on the device: f32 logits
+ * [B][C] (row stride ld), int64 targets in [0, C).  Adds into acc[6] (f64; the caller zeroes it with
+ * vit_zero): [0] the batch's mean loss, [1] the sum of row losses, [2] rows whose target has rank 0
+ * (first-maximum argmax == target), [3] rows with rank < topk, [4] B, [5] 1, where rank = classes with a
+ * larger logit + classes with an equal logit and a smaller index.  A row whose log-sum-exp is not finite
+ * adds its non-finite loss and counts as wrong.  row_ws >= 2*B floats.  Fixed-order sums, no atomics:
+ * bitwise reproducible; successive calls on one stream accumulate. */
+int vit_eval_metrics(int B, int C, const float* logits, int64_t ld, const int64_t* target, int topk, float* row_ws,
+                     double* acc, void* stream);
 
 /* torch.optim.SGD(lr, momentum, weight_decay).step() over all parameters in one
  * launch (VIT:143-144, VIT:294-299).  tensors: {float* p; const float* g; float* buf;

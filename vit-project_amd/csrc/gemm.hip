@@ -73,21 +73,25 @@ __device__ __forceinline__ f32x4 epi4(const Epi& e, int i, int j, f32x4 v, int z
     TO* c = (TO*)e.C + (int64_t)i * e.ldc + j;
     store4<TO>(c, v + load4<TO>(c));
     return v;
-  } else if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU) {
+  } else if constexpr (epi_act(EPI)) {
     // act and act' of the pre-activation rounded to the storage type (the value a
-    // stored-pre design would have differentiated)
+    // stored-pre design would have differentiated); the act-only forms store act alone, as C
     f32x4 a, d;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const float pr = (float)(TO)v[t];
       float ga, gd;
-      if constexpr (EPI == EPI_BIAS_GELU) gelu_fast_both(pr, ga, gd);
+      if constexpr (epi_gelu(EPI)) gelu_fast_both(pr, ga, gd);
       else quick_gelu_both(pr, ga, gd);
       a[t] = ga;
       d[t] = gd;
     }
-    store4<TO>((TO*)e.C + (int64_t)i * e.ldc + j, d);
-    store4<TO>((TO*)e.aux_out + (int64_t)i * e.ldc + j, a);
+    if constexpr (epi_act_only(EPI)) {
+      store4<TO>((TO*)e.C + (int64_t)i * e.ldc + j, a);
+    } else {
+      store4<TO>((TO*)e.C + (int64_t)i * e.ldc + j, d);
+      store4<TO>((TO*)e.aux_out + (int64_t)i * e.ldc + j, a);
+    }
     return v;
   } else if constexpr (EPI == EPI_RESID) {
     f32x4 r = load4<float>((const float*)e.aux + (int64_t)i * e.ld_aux + j);
@@ -162,7 +166,7 @@ __device__ __forceinline__ void epi_vec(const Epi& e, int i, int j, VecF<V>& v, 
 #pragma unroll
     for (int q = 0; q < V / 4; ++q) o.q[q] += v.q[q];
     vstore<TO, V>(c, o);
-  } else if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU) {
+  } else if constexpr (epi_act(EPI)) {
     VecF<V> a, d;
 #pragma unroll
     for (int q = 0; q < V / 4; ++q)
@@ -170,13 +174,17 @@ __device__ __forceinline__ void epi_vec(const Epi& e, int i, int j, VecF<V>& v, 
       for (int t = 0; t < 4; ++t) {
         const float pr = (float)(TO)v.q[q][t];  // pre-activation rounded to the storage type
         float ga, gd;
-        if constexpr (EPI == EPI_BIAS_GELU) gelu_fast_both(pr, ga, gd);
+        if constexpr (epi_gelu(EPI)) gelu_fast_both(pr, ga, gd);
         else quick_gelu_both(pr, ga, gd);
         a.q[q][t] = ga;
         d.q[q][t] = gd;
       }
-    vstore<TO, V>((TO*)e.C + (int64_t)i * e.ldc + j, d);
-    vstore<TO, V>((TO*)e.aux_out + (int64_t)i * e.ldc + j, a);
+    if constexpr (epi_act_only(EPI)) {
+      vstore<TO, V>((TO*)e.C + (int64_t)i * e.ldc + j, a);
+    } else {
+      vstore<TO, V>((TO*)e.C + (int64_t)i * e.ldc + j, d);
+      vstore<TO, V>((TO*)e.aux_out + (int64_t)i * e.ldc + j, a);
+    }
   } else if constexpr (EPI == EPI_RESID) {
     VecF<V> r;
     vload<float, V>((const float*)e.aux + (int64_t)i * e.ld_aux + j, r);
@@ -223,14 +231,14 @@ template <int EPI, typename TO, typename TA>
 __device__ __forceinline__ f32x4 epi_val(const Epi& e, int i, int j, f32x4 v, bool ok, f32x4& o0, f32x4& o1,
                                          const f32x4& bias4) {
   v += bias4;  // this lane's 4 bias values (zero without bias), loaded once per column fragment
-  if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU) {
+  if constexpr (epi_act(EPI)) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const float pr = (float)(TO)v[t];  // pre-activation rounded to the storage type
       float ga, gd;
-      if constexpr (EPI == EPI_BIAS_GELU) gelu_fast_both(pr, ga, gd);
+      if constexpr (epi_gelu(EPI)) gelu_fast_both(pr, ga, gd);
       else quick_gelu_both(pr, ga, gd);
-      o0[t] = gd;
+      o0[t] = epi_act_only(EPI) ? ga : gd;  // act-only: the activation is the one output (C)
       o1[t] = ga;
     }
   } else if constexpr (EPI == EPI_GELU_BWD || EPI == EPI_QGELU_BWD) {
@@ -247,7 +255,7 @@ template <class C, int EPI, typename TO, typename TA>
 __device__ __forceinline__ void epilogue_swap(const Epi& e, const f32x4 (&acc)[C::AI][C::AJ], int i0, int j0, int wi,
                                               int wj, int lane, int M, int N) {
   static_assert(C::AJ % 2 == 0, "fragment pairs");
-  constexpr bool two = EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU;
+  constexpr bool two = epi_act(EPI) && !epi_act_only(EPI);
   const int g = lane >> 4;
   const int colsel = (g & 1) * 16 + (g >> 1) * 8;
   f32x4 cs[C::AJ], bias4[C::AJ];
@@ -415,7 +423,7 @@ __device__ __forceinline__ void epilogue_pair16(const Epi& e, const f32x4 (&acc)
         *reinterpret_cast<bf16x8*>((bf16*)e.C + (int64_t)i * e.ldc + j) = x;
       } else {
         VecF<8> av, dv;
-        if constexpr (EPI == EPI_BIAS_GELU) {  // two elements per call (packed FP32; same bits)
+        if constexpr (epi_gelu(EPI)) {  // two elements per call (packed FP32; same bits)
 #pragma unroll
           for (int q = 0; q < 8; q += 2) {
             f32x2 ga, gd;
@@ -434,8 +442,12 @@ __device__ __forceinline__ void epilogue_pair16(const Epi& e, const f32x4 (&acc)
             dv.q[q >> 2][q & 3] = gd;
           }
         }
-        vstore<bf16, 8>((bf16*)e.C + (int64_t)i * e.ldc + j, dv);
-        vstore<bf16, 8>((bf16*)e.aux_out + (int64_t)i * e.ldc + j, av);
+        if constexpr (epi_act_only(EPI)) {  // forward-only: the activation alone, as C
+          vstore<bf16, 8>((bf16*)e.C + (int64_t)i * e.ldc + j, av);
+        } else {
+          vstore<bf16, 8>((bf16*)e.C + (int64_t)i * e.ldc + j, dv);
+          vstore<bf16, 8>((bf16*)e.aux_out + (int64_t)i * e.ldc + j, av);
+        }
       }
     }
   }
@@ -450,13 +462,17 @@ __device__ __forceinline__ void epi1(const Epi& e, int i, int j, float v) {
   } else if constexpr (EPI == EPI_ACC) {
     TO* c = (TO*)e.C + (int64_t)i * e.ldc + j;
     *c = (TO)((float)*c + v);
-  } else if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU) {
+  } else if constexpr (epi_act(EPI)) {
     const float pf = (float)(TO)v;
     float a, d;
-    if constexpr (EPI == EPI_BIAS_GELU) gelu_erf_both(pf, a, d);
+    if constexpr (epi_gelu(EPI)) gelu_erf_both(pf, a, d);
     else quick_gelu_both(pf, a, d);
-    ((TO*)e.C)[(int64_t)i * e.ldc + j] = (TO)d;
-    ((TO*)e.aux_out)[(int64_t)i * e.ldc + j] = (TO)a;
+    if constexpr (epi_act_only(EPI)) {
+      ((TO*)e.C)[(int64_t)i * e.ldc + j] = (TO)a;
+    } else {
+      ((TO*)e.C)[(int64_t)i * e.ldc + j] = (TO)d;
+      ((TO*)e.aux_out)[(int64_t)i * e.ldc + j] = (TO)a;
+    }
   } else if constexpr (EPI == EPI_RESID) {
     ((TO*)e.C)[(int64_t)i * e.ldc + j] = (TO)(v + ((const float*)e.aux)[(int64_t)i * e.ld_aux + j]);
   } else if constexpr (EPI == EPI_GELU_BWD || EPI == EPI_QGELU_BWD) {
@@ -753,8 +769,7 @@ __device__ __forceinline__ void gemm_tile(const bf16* __restrict__ P, int64_t ld
   // (plain bf16 stores: fragment epilogue on every tile -- the qkv forward on the 256x256 tile runs 10 %
   // faster than through the LDS staging, tools/bench_kernels.py --sweep=5,1605; the GELU pair stays staged)
   if constexpr (sizeof(TO) == 2 && (EPI == EPI_STORE ||
-                                     (C::EPS == 1 && (EPI == EPI_STORE || EPI == EPI_BIAS_GELU ||
-                                                      EPI == EPI_BIAS_QGELU || EPI == EPI_GELU_BWD ||
+                                     (C::EPS == 1 && (EPI == EPI_STORE || epi_act(EPI) || EPI == EPI_GELU_BWD ||
                                                       EPI == EPI_QGELU_BWD)))) {
     if constexpr (EPI == EPI_STORE && C::EPS == 0 && C::BM == 256 && C::BN == 256 &&
                   Pair16<C>::BYTES <= (C::LDS > EpiLds<C, TO>::BYTES ? C::LDS : EpiLds<C, TO>::BYTES)) {
@@ -771,14 +786,14 @@ __device__ __forceinline__ void gemm_tile(const bf16* __restrict__ P, int64_t ld
       return;
     }
   }
-  if constexpr (sizeof(TO) == 2 && C::EPS == 0 && (EPI == EPI_STORE || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU ||
+  if constexpr (sizeof(TO) == 2 && C::EPS == 0 && (EPI == EPI_STORE || epi_act(EPI) ||
                                                     EPI == EPI_GELU_BWD || EPI == EPI_QGELU_BWD)) {
     if ((e.dbg & 16) && N % 32 == 0) {  // timing experiment: the fragment (permlane16) epilogue on any tile
       epilogue_swap<C, EPI, TO, TA>(e, acc, i0, j0, wi, wj, lane, M, N);
       return;
     }
   }
-  if constexpr (sizeof(TO) == 2 && C::EPS == 0 && (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU) &&
+  if constexpr (sizeof(TO) == 2 && C::EPS == 0 && epi_act(EPI) &&
                 Pair16<C>::BYTES <= (C::LDS > EpiLds<C, TO>::BYTES ? C::LDS : EpiLds<C, TO>::BYTES)) {
     if (VIT_PAIR16 && !e.csum && !(e.dbg & (8 | 128)) && N % 8 == 0) {  // dbg 128: the f32 band staging (A/B)
       epilogue_pair16<C, EPI>(e, acc, smem, i0, j0, wi, wj, lane, M, N);
@@ -1513,7 +1528,7 @@ static int launch_gen(const void* P, int64_t sPi, int64_t sPr, const void* Q, in
 template <int PL, int QL, int EPI, typename TO> constexpr bool fast_combo() {
   constexpr bool f32o = std::is_same<TO, float>::value;
   if (PL == LAY_RC && QL == LAY_RC)  // forward
-    return EPI == EPI_STORE || ((EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU) && !f32o) ||
+    return EPI == EPI_STORE || (epi_act(EPI) && !f32o) ||
            ((EPI == EPI_RESID || EPI == EPI_PATCH) && f32o);
   if (PL == LAY_RC && QL == LAY_CR) return EPI == EPI_STORE || EPI == EPI_GELU_BWD || EPI == EPI_QGELU_BWD;  // dgrad
   if (PL == LAY_CR && QL == LAY_CR) return EPI == EPI_STORE && f32o;  // wgrad (f32 slabs)
@@ -1526,6 +1541,9 @@ template <int EPI>
 static int gemm_dispatch(int dtype, int out_dtype, int pl, int ql, int M, int N, int R,
                          const void* P, int64_t ldp, const void* Q, int64_t ldq, int split,
                          const Epi& e, hipStream_t s, bool allow_fast) {
+  if constexpr (epi_act_only(EPI)) {  // the act-only forms exist for the RC x RC forward alone
+    if (pl != LAY_RC || ql != LAY_RC || split > 1) return (int)hipErrorInvalidValue;
+  }
   if (M <= 0 || N <= 0) return 0;
   if (allow_fast && fast_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) && (e.ldc % 4 == 0) && pl == LAY_RC) {
     // an RC P past the 32-bit staging offsets: launch row chunks with every row-indexed operand
@@ -1568,9 +1586,11 @@ static int gemm_dispatch(int dtype, int out_dtype, int pl, int ql, int M, int N,
   if (allow_fast && out_dtype == VIT_F32 && fast_f32_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) && (e.ldc % 4 == 0) &&
       ((uintptr_t)e.C & 15) == 0 && f32_grid_ok(M, N, split)) {
     if (pl == LAY_RC && ql == LAY_RC) return launch_f32<LAY_RC, LAY_RC, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
-    if (pl == LAY_RC && ql == LAY_CR) return launch_f32<LAY_RC, LAY_CR, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
-    if (pl == LAY_CR && ql == LAY_CR) return launch_f32<LAY_CR, LAY_CR, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
-    return launch_f32<LAY_CR, LAY_RC, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
+    if constexpr (!epi_act_only(EPI)) {  // (act-only: forward layout only, checked above)
+      if (pl == LAY_RC && ql == LAY_CR) return launch_f32<LAY_RC, LAY_CR, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
+      if (pl == LAY_CR && ql == LAY_CR) return launch_f32<LAY_CR, LAY_CR, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
+      return launch_f32<LAY_CR, LAY_RC, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
+    }
   }
   int64_t sPi = pl == LAY_RC ? ldp : 1, sPr = pl == LAY_RC ? 1 : ldp;
   int64_t sQj = ql == LAY_RC ? ldq : 1, sQr = ql == LAY_RC ? 1 : ldq;
@@ -1594,6 +1614,8 @@ static int gemm_any(int epi, int dtype, int out_dtype, int pl, int ql, int M, in
     case EPI_QGELU_BWD: return gemm_dispatch<EPI_QGELU_BWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
     case EPI_ACC: return gemm_dispatch<EPI_ACC>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
     case EPI_PATCH: return gemm_dispatch<EPI_PATCH>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
+    case EPI_BIAS_GELU_FWD: return gemm_dispatch<EPI_BIAS_GELU_FWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
+    case EPI_BIAS_QGELU_FWD: return gemm_dispatch<EPI_BIAS_QGELU_FWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
   }
   return (int)hipErrorInvalidValue;
 }
@@ -1678,7 +1700,8 @@ int vit_gemm_splitk(int p_layout, int q_layout, int M, int N, int R, const float
 
 // F.linear forward: Y[M,N] = X[M,K] W[N,K]^T + b with a fused epilogue
 //   epi = EPI_STORE (Y out_dtype), EPI_BIAS_GELU / EPI_BIAS_QGELU (Y = act'(pre), act_out = act(pre)),
-//   EPI_RESID (Y f32 = resid + X W^T + b; Y may alias resid).
+//   EPI_RESID (Y f32 = resid + X W^T + b; Y may alias resid),
+//   EPI_BIAS_GELU_FWD / EPI_BIAS_QGELU_FWD (Y = act(pre), the pair's act_out bits; act_out ignored, may be NULL).
 int vit_linear_fwd(int dtype, int out_dtype, int epi, int M, int N, int K, const void* X, int64_t ldx,
                    const void* W, const float* bias, void* Y, int64_t ldy, const void* resid,
                    void* act_out, void* stream) {

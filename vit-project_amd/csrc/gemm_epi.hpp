@@ -8,12 +8,19 @@
 // BIAS_GELU / BIAS_QGELU: C = act'(pre) (what the backward needs), aux_out = act(pre);
 // GELU_BWD / QGELU_BWD: C = acc * aux, aux = that saved act'(pre)  (same for both).
 enum { EPI_STORE = 0, EPI_BIAS_GELU = 1, EPI_RESID = 2, EPI_GELU_BWD = 3, EPI_PATCH = 4,
-       EPI_BIAS_QGELU = 5, EPI_QGELU_BWD = 6, EPI_ACC = 7 };
+       EPI_BIAS_QGELU = 5, EPI_QGELU_BWD = 6, EPI_ACC = 7,
+       // forward-only forms of the pair (no backward follows): C = act(pre), nothing else written, aux_out
+       // ignored.  The activation is computed by the pair's own routine with the act' half dropped, so the
+       // stored bits are the pair's aux_out bits on the same kernel path.
+       EPI_BIAS_GELU_FWD = 8, EPI_BIAS_QGELU_FWD = 9 };
+constexpr bool epi_act_only(int epi) { return epi == EPI_BIAS_GELU_FWD || epi == EPI_BIAS_QGELU_FWD; }
+constexpr bool epi_act(int epi) { return epi == EPI_BIAS_GELU || epi == EPI_BIAS_QGELU || epi_act_only(epi); }  // pair or act-only
+constexpr bool epi_gelu(int epi) { return epi == EPI_BIAS_GELU || epi == EPI_BIAS_GELU_FWD; }  // erf GELU (else QuickGELU)
 struct Epi {
   void* C; int64_t ldc;
   const float* bias;        // [N] or null
   const void* aux; int64_t ld_aux;  // EPI_RESID: f32 residual;  *_BWD: pre-activation (T)
-  void* aux_out;            // BIAS_GELU: activation output (T, ld = ldc)
+  void* aux_out;            // BIAS_GELU / BIAS_QGELU: activation output (T, ld = ldc); *_FWD: unused
   const float* pos;         // EPI_PATCH: pos_embed [seq, N]
   int n_patch;              // EPI_PATCH: patches per image (seq = n_patch + 1)
   int64_t slab;             // split-r: element offset of slab z

@@ -4,18 +4,22 @@ Compute runs only in ``lib/libvit_hip.so`` (C-ABI, include/vit_hip.h); this
 package is the host-side mirror of the reference's module/optimizer interface.
 """
 from . import _lib
-from .model import VisionTransformer, create_model, cross_entropy, set_wgrad_overlap
+from .model import (VisionTransformer, create_model, cross_entropy, set_wgrad_overlap, set_forward_only,
+                    block_forward_only)
 from .optim import FusedSGD, FusedAdamW, CosineAnnealingLRWithWarmup
 from .dora import DoRALayer, dora_weight
 from . import rsa
 from . import clip
 from . import sweep
 from . import data
+from . import evaluate
+from .evaluate import EvalMeter, validate
 from .clip import CLIPHBA, MSELoss, mse_loss, apply_dora_to_ViT, switch_dora_layers, count_trainable_parameters
 
 __all__ = ["VisionTransformer", "create_model", "cross_entropy", "set_wgrad_overlap", "FusedSGD", "FusedAdamW",
            "CosineAnnealingLRWithWarmup", "DoRALayer", "dora_weight", "rsa", "clip", "data", "CLIPHBA", "MSELoss",
-           "mse_loss", "apply_dora_to_ViT", "switch_dora_layers", "count_trainable_parameters"]
+           "mse_loss", "apply_dora_to_ViT", "switch_dora_layers", "count_trainable_parameters", "set_forward_only",
+           "block_forward_only", "evaluate", "EvalMeter", "validate"]
 
 
 def load_library(path=None):

@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("VIT_HIP_LIB", os.path.join(_HERE, "lib", "libvit_hip.
 F32, BF16 = 0, 1
 LAY_RC, LAY_CR = 0, 1
 EPI_STORE, EPI_BIAS_GELU, EPI_RESID, EPI_GELU_BWD, EPI_PATCH, EPI_BIAS_QGELU, EPI_QGELU_BWD = range(7)
+# act-only forms of the fc1 pair for passes no backward follows (7 is the library's internal accumulate code)
+EPI_BIAS_GELU_FWD, EPI_BIAS_QGELU_FWD = 8, 9
 
 i32, i64, f32, vp = C.c_int, C.c_int64, C.c_float, C.c_void_p
 
@@ -67,6 +69,7 @@ SIGNATURES = {
     "vit_pos_grad": [i32, i32, i32, vp, vp, vp, vp],
     "vit_cross_entropy_fwd": [i32, i32, vp, i64, vp, vp, vp, vp, vp],
     "vit_cross_entropy_bwd": [i32, i32, i32, vp, i64, vp, vp, vp, vp, i64, vp],
+    "vit_eval_metrics": [i32, i32, vp, i64, vp, i32, vp, vp, vp],
     "vit_sgd_step": [vp, vp, i32, vp, f32, f32, vp],
     "vit_sgd_chunk_size": [],
     "vit_sgd_tensor_bytes": [],

@@ -44,7 +44,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .dora import DoRALayer
-from .model import _FUSED_RESID_F32, _BlockFn, _Shadowed, _gout, _wt
+from .model import _FUSED_RESID_F32, _BlockFn, _Shadowed, _gout, _wt, run_block
 
 SOT, EOT = 49406, 49407
 
@@ -359,7 +359,7 @@ class CLIP(nn.Module):
             cfg = self._cfg(heads, False, frozen=i < first)
             if rs is not None:
                 cfg = dict(cfg, resid=rs, resid_last=i == len(blocks) - 1)
-            x = _BlockFn.apply(x, *blk.block_params(), cfg)
+            x = run_block(x, blk.block_params(), cfg)
         idx = self._cls_rows(B, npatch + 1, x.device)
         return _PoolHeadFn.apply(x, idx, v.ln_post.weight, v.ln_post.bias, v.proj, 1e-5)
 
@@ -390,7 +390,7 @@ class CLIP(nn.Module):
         x = x.reshape(S, Lq, -1)
         with torch.no_grad():
             for blk in blocks[:k]:
-                x = _BlockFn.apply(x, *blk.block_params(), self._cfg(blk.attn.num_heads, True, frozen=True))
+                x = run_block(x, blk.block_params(), self._cfg(blk.attn.num_heads, True, frozen=True))
         if self.cache_frozen_text:
             self._text_cache = (key, x)
         return x, k
@@ -401,7 +401,7 @@ class CLIP(nn.Module):
         text = text.reshape(-1, text.shape[-1])
         x, k = self._text_prefix(text)
         for blk in list(self.transformer.resblocks)[k:]:
-            x = _BlockFn.apply(x, *blk.block_params(), self._cfg(blk.attn.num_heads, True))
+            x = run_block(x, blk.block_params(), self._cfg(blk.attn.num_heads, True))
         c = getattr(self, "_idx_cache", {})
         key = ("eot", text.data_ptr(), text._version, tuple(text.shape))
         if key not in c:

@@ -83,6 +83,9 @@ _HOLD = {}
 # (+2.0 % over the EPI_RESID epilogue, round 2); fp32 keeps the epilogue add unless VIT_FUSED_RESID_F32=1
 # (bit-identical: the same f32 add, in the LayerNorm; C3 fp32 measured 607 vs 609 img/s)
 _FUSED_RESID_F32 = [os.environ.get("VIT_FUSED_RESID_F32", "0") == "1"]
+# blocks that no backward can follow (no-grad passes, all-frozen blocks) take the forward-only chain
+# (block_forward_only); VIT_FWD_ONLY=0 / set_forward_only(False) keeps them on the training chain
+_FWD_ONLY = [os.environ.get("VIT_FWD_ONLY", "1") != "0"]
 
 
 def set_wgrad_overlap(enable: bool):
@@ -262,6 +265,163 @@ class _PatchEmbedFn(torch.autograd.Function):
         return None, dw, db, dcls, dpos, None
 
 
+def _block_chain(x, params, cfg, fwd_only):
+    """The launch chain of one block's forward, shared by the autograd node (_BlockFn.forward) and the
+    forward-only path (block_forward_only).  Returns (xo [B, N, D], the tensors a backward would need,
+    the GEMM weight operands).  ``fwd_only``: fc1 runs the act-only epilogue and no act'(pre) tensor
+    exists; every other launch, the half-batch schedule and the fused-residual ``pending`` state are
+    the training chain's."""
+    n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
+    B, N, D = x.shape
+    H, T, eps = cfg["heads"], cfg["dtype"], cfg["eps"]
+    if fwd_only:
+        act_epi = L.EPI_BIAS_QGELU_FWD if cfg["quick_gelu"] else L.EPI_BIAS_GELU_FWD
+    else:
+        act_epi = L.EPI_BIAS_QGELU if cfg["quick_gelu"] else L.EPI_BIAS_GELU
+    M = B * N
+    dev = x.device
+    x2 = x.reshape(M, D)
+    F = fc1w.shape[0]
+    f32 = torch.float32
+    h1, h2 = torch.empty(M, D, dtype=T, device=dev), torch.empty(M, D, dtype=T, device=dev)
+    m1, r1, m2, r2 = (torch.empty(M, dtype=f32, device=dev) for _ in range(4))
+    qkv = torch.empty(M, 3 * D, dtype=T, device=dev)
+    o = torch.empty(M, D, dtype=T, device=dev)
+    lse = torch.empty(B * H * N, dtype=f32, device=dev)
+    xm, xo = torch.empty(M, D, dtype=f32, device=dev), torch.empty(M, D, dtype=f32, device=dev)
+    # fc1's epilogue writes act = GELU(pre) for fc2 and dact = GELU'(pre) for the backward
+    # (the erf is evaluated once; the fc2 dgrad epilogue is then a multiply); a forward-only pass has
+    # no backward to feed: no dact, and the act-only epilogue stores act alone (the same bits)
+    act = torch.empty(M, F, dtype=T, device=dev)
+    dact = None if fwd_only else torch.empty(M, F, dtype=T, device=dev)
+    Wqkv, Wproj, W1, W2 = _wt(qkvw, T), _wt(projw, T), _wt(fc1w, T), _wt(fc2w, T)
+    causal = bool(cfg.get("causal", False))
+    attn_fp8 = bool(cfg.get("attn_fp8", False))  # forward-only blocks (frozen prefix, no-grad passes)
+
+    # fused residual adds (bf16 ViT, VisionTransformer._tokens): proj / fc2 store their bf16 output
+    # (bias included) and the add into the f32 stream runs inside the next LayerNorm -- norm2 here,
+    # the next block's norm1 for fc2 (this block's output xo is then written by that kernel), or
+    # an add-only launch after the last block.  rs["pending"]: the previous block's (xm, fc2 out).
+    rs = cfg.get("resid")
+    pend = rs.get("pending") if rs is not None else None
+    pb = yb = None
+    if rs is not None:
+        pb, yb = torch.empty(M, D, dtype=T, device=dev), torch.empty(M, D, dtype=T, device=dev)
+
+    def fc1(sl):
+        if fwd_only:
+            return lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=act[sl])
+        return lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=dact[sl], act_out=act[sl])
+
+    def ln1(sl):
+        if pend is not None:
+            return lambda: ops.add_layer_norm_fwd(pend[0][sl], pend[1][sl], x2[sl], n1w.detach(), n1b.detach(), eps,
+                                                  out=h1[sl], mean=m1[sl], rstd=r1[sl])
+        return lambda: ops.layer_norm_fwd(x2[sl], n1w.detach(), n1b.detach(), eps, T, out=h1[sl], mean=m1[sl],
+                                          rstd=r1[sl])
+
+    def chain_fused(b0, b1):
+        sl = slice(b0 * N, b1 * N)
+        steps = [
+            ln1(sl),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
+            lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
+                                 fp8=attn_fp8),
+            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), out=pb[sl]),
+            lambda: ops.add_layer_norm_fwd(x2[sl], pb[sl], xm[sl], n2w.detach(), n2b.detach(), eps, out=h2[sl],
+                                           mean=m2[sl], rstd=r2[sl]),
+            fc1(sl),
+            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), out=yb[sl]),
+        ]
+        if cfg.get("resid_last"):
+            steps.append(lambda: ops.add_layer_norm_fwd(xm[sl], yb[sl], xo[sl]))
+        return steps
+
+    def chain(b0, b1):
+        """The block over images [b0, b1) (rows b0*N .. b1*N of every tensor) as its 7 launches."""
+        if rs is not None:
+            return chain_fused(b0, b1)
+        r0, r1_ = b0 * N, b1 * N
+        sl = slice(r0, r1_)
+        return [
+            lambda: ops.layer_norm_fwd(x2[sl], n1w.detach(), n1b.detach(), eps, T, out=h1[sl], mean=m1[sl],
+                                       rstd=r1[sl]),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
+            lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
+                                 fp8=attn_fp8),
+            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), epi=L.EPI_RESID, resid=x2[sl], out=xm[sl]),
+            lambda: ops.layer_norm_fwd(xm[sl], n2w.detach(), n2b.detach(), eps, T, out=h2[sl], mean=m2[sl],
+                                       rstd=r2[sl]),
+            fc1(sl),
+            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), epi=L.EPI_RESID, resid=xm[sl], out=xo[sl]),
+        ]
+
+    def run(steps):
+        for f in steps:
+            f()
+
+    side = _Side(dev)
+    if side.on and B >= 2 and T != torch.float32:
+        # two half-batch chains on two streams: one chain's GEMM epilogues (HBM-bound)
+        # overlap the other's MFMA main loops (side.run waits for everything the caller's stream
+        # has queued, so the side chain starts with the caller's)
+        hb = fwd_split(B)
+        mine, other = chain(0, hb), chain(hb, B)
+        side.run(lambda: run(other))
+        side.guard(x2, h1, m1, r1, qkv, o, lse, xm, h2, m2, r2, dact, act, xo,
+                   *(t for t in (pb, yb, *(pend or ())) if t is not None))
+        run(mine)
+        # each half only feeds the same half of the next block: a stack of blocks joins
+        # once after its last block (cfg "defer_join", ViT._tokens) instead of per block
+        if not cfg.get("defer_join"):
+            side.join()
+    else:
+        run(chain(0, B))
+    if rs is not None:
+        rs["pending"] = None if cfg.get("resid_last") else (xm, yb)
+    return xo.reshape(B, N, D), (x2, h1, m1, r1, qkv, o, lse, xm, h2, m2, r2, dact, act), (Wqkv, Wproj, W1, W2)
+
+
+def block_forward_only(x, params, cfg):
+    """One transformer block with no backward to follow (``torch.no_grad()`` passes, blocks whose
+    input and parameters are all frozen): the training chain's launches with fc1 on the act-only
+    epilogue -- no act'(pre) tensor is allocated or written -- and nothing saved.  ``params`` are the
+    12 tensors of ``block_params()``; returns the block output [B, N, D] (f32), bit for bit the
+    training chain's."""
+    with torch.no_grad():
+        return _block_chain(x, tuple(params), cfg, True)[0]
+
+
+def forward_only_enabled() -> bool:
+    return _FWD_ONLY[0]
+
+
+def set_forward_only(enable: bool) -> bool:
+    """Route blocks that no backward can follow to :func:`block_forward_only` (default; environment
+    ``VIT_FWD_ONLY=0`` starts with it off) or keep them on the training chain (A/B runs, the equality
+    tests).  Returns the previous setting."""
+    prev = _FWD_ONLY[0]
+    _FWD_ONLY[0] = bool(enable)
+    return prev
+
+
+def wants_forward_only(enabled: bool, grad_enabled: bool, input_requires_grad: bool,
+                       any_param_requires_grad: bool) -> bool:
+    """The routing rule, as a pure function: a block takes the forward-only chain when the switch is on
+    and no backward can follow -- autograd is off, or neither its input nor any of its parameters
+    requires a gradient."""
+    return bool(enabled) and (not grad_enabled or not (input_requires_grad or any_param_requires_grad))
+
+
+def run_block(x, params, cfg):
+    """A block through the forward-only chain when nothing can ask for its backward, else through the
+    autograd node."""
+    if wants_forward_only(_FWD_ONLY[0], torch.is_grad_enabled(), x.requires_grad,
+                          any(p.requires_grad for p in params)):
+        return block_forward_only(x, params, cfg)
+    return _BlockFn.apply(x, *params, cfg)
+
+
 class _BlockFn(torch.autograd.Function):
     """timm Block: x += proj(sdpa(qkv(norm1(x)))); x += fc2(gelu(fc1(norm2(x)))).
 
@@ -273,112 +433,21 @@ class _BlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b, cfg):
+        params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b)
+        xo, saved, wops = _block_chain(x, params, cfg, False)
         B, N, D = x.shape
-        H, T, eps = cfg["heads"], cfg["dtype"], cfg["eps"]
-        act_epi = L.EPI_BIAS_QGELU if cfg["quick_gelu"] else L.EPI_BIAS_GELU
-        M = B * N
-        dev = x.device
-        x2 = x.reshape(M, D)
-        F = fc1w.shape[0]
-        f32 = torch.float32
-        h1, h2 = torch.empty(M, D, dtype=T, device=dev), torch.empty(M, D, dtype=T, device=dev)
-        m1, r1, m2, r2 = (torch.empty(M, dtype=f32, device=dev) for _ in range(4))
-        qkv = torch.empty(M, 3 * D, dtype=T, device=dev)
-        o = torch.empty(M, D, dtype=T, device=dev)
-        lse = torch.empty(B * H * N, dtype=f32, device=dev)
-        xm, xo = torch.empty(M, D, dtype=f32, device=dev), torch.empty(M, D, dtype=f32, device=dev)
-        # fc1's epilogue writes act = GELU(pre) for fc2 and dact = GELU'(pre) for the backward
-        # (the erf is evaluated once; the fc2 dgrad epilogue is then a multiply)
-        dact, act = torch.empty(M, F, dtype=T, device=dev), torch.empty(M, F, dtype=T, device=dev)
-        Wqkv, Wproj, W1, W2 = _wt(qkvw, T), _wt(projw, T), _wt(fc1w, T), _wt(fc2w, T)
+        H, T = cfg["heads"], cfg["dtype"]
         causal = bool(cfg.get("causal", False))
-        attn_fp8 = bool(cfg.get("attn_fp8", False))  # forward-only blocks (frozen prefix, no-grad passes)
-
-        # fused residual adds (bf16 ViT, VisionTransformer._tokens): proj / fc2 store their bf16 output
-        # (bias included) and the add into the f32 stream runs inside the next LayerNorm -- norm2 here,
-        # the next block's norm1 for fc2 (this block's output xo is then written by that kernel), or
-        # an add-only launch after the last block.  rs["pending"]: the previous block's (xm, fc2 out).
-        rs = cfg.get("resid")
-        pend = rs.get("pending") if rs is not None else None
-        pb = yb = None
-        if rs is not None:
-            pb, yb = torch.empty(M, D, dtype=T, device=dev), torch.empty(M, D, dtype=T, device=dev)
-
-        def ln1(sl):
-            if pend is not None:
-                return lambda: ops.add_layer_norm_fwd(pend[0][sl], pend[1][sl], x2[sl], n1w.detach(), n1b.detach(), eps,
-                                                      out=h1[sl], mean=m1[sl], rstd=r1[sl])
-            return lambda: ops.layer_norm_fwd(x2[sl], n1w.detach(), n1b.detach(), eps, T, out=h1[sl], mean=m1[sl],
-                                              rstd=r1[sl])
-
-        def chain_fused(b0, b1):
-            sl = slice(b0 * N, b1 * N)
-            steps = [
-                ln1(sl),
-                lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
-                lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
-                                     fp8=attn_fp8),
-                lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), out=pb[sl]),
-                lambda: ops.add_layer_norm_fwd(x2[sl], pb[sl], xm[sl], n2w.detach(), n2b.detach(), eps, out=h2[sl],
-                                               mean=m2[sl], rstd=r2[sl]),
-                lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=dact[sl], act_out=act[sl]),
-                lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), out=yb[sl]),
-            ]
-            if cfg.get("resid_last"):
-                steps.append(lambda: ops.add_layer_norm_fwd(xm[sl], yb[sl], xo[sl]))
-            return steps
-
-        def chain(b0, b1):
-            """The block over images [b0, b1) (rows b0*N .. b1*N of every tensor) as its 7 launches."""
-            if rs is not None:
-                return chain_fused(b0, b1)
-            r0, r1_ = b0 * N, b1 * N
-            sl = slice(r0, r1_)
-            return [
-                lambda: ops.layer_norm_fwd(x2[sl], n1w.detach(), n1b.detach(), eps, T, out=h1[sl], mean=m1[sl],
-                                           rstd=r1[sl]),
-                lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
-                lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
-                                     fp8=attn_fp8),
-                lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), epi=L.EPI_RESID, resid=x2[sl], out=xm[sl]),
-                lambda: ops.layer_norm_fwd(xm[sl], n2w.detach(), n2b.detach(), eps, T, out=h2[sl], mean=m2[sl],
-                                           rstd=r2[sl]),
-                lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=dact[sl], act_out=act[sl]),
-                lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), epi=L.EPI_RESID, resid=xm[sl], out=xo[sl]),
-            ]
-
-        def run(steps):
-            for f in steps:
-                f()
-
-        side = _Side(dev)
-        if side.on and B >= 2 and T != torch.float32:
-            # two half-batch chains on two streams: one chain's GEMM epilogues (HBM-bound)
-            # overlap the other's MFMA main loops (side.run waits for everything the caller's stream
-            # has queued, so the side chain starts with the caller's)
-            hb = fwd_split(B)
-            mine, other = chain(0, hb), chain(hb, B)
-            side.run(lambda: run(other))
-            side.guard(x2, h1, m1, r1, qkv, o, lse, xm, h2, m2, r2, dact, act, xo,
-                       *(t for t in (pb, yb, *(pend or ())) if t is not None))
-            run(mine)
-            # each half only feeds the same half of the next block: a stack of blocks joins
-            # once after its last block (cfg "defer_join", ViT._tokens) instead of per block
-            if not cfg.get("defer_join"):
-                side.join()
-        else:
-            run(chain(0, B))
-        if rs is not None:
-            rs["pending"] = None if cfg.get("resid_last") else (xm, yb)
-        ctx.save_for_backward(x2, h1, m1, r1, qkv, o, lse, xm, h2, m2, r2, dact, act)
-        ctx.params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b)
-        ctx.wops = (Wqkv, Wproj, W1, W2)
+        attn_fp8 = bool(cfg.get("attn_fp8", False))
+        ctx.save_for_backward(*saved)
+        ctx.params = params
+        ctx.wops = wops
         ctx.meta = (B, N, D, H, T, cfg.get("compact_np", 0), cfg["quick_gelu"], causal)
         ctx.defer_bwd = bool(cfg.get("defer_bwd_join"))
         ctx.attn_fp8 = attn_fp8
         ctx.grad_hook = cfg.get("grad_hook")
         ctx.flat_span = cfg.get("flat_span")
-        return xo.reshape(B, N, D)
+        return xo
 
     @staticmethod
     def backward(ctx, dxo):
@@ -724,7 +793,7 @@ class VisionTransformer(nn.Module):
                 bcfg = dict(bcfg, resid_last=True)
             if hook is not None:
                 bcfg = dict(bcfg, grad_hook=hook, flat_span=blk._flat_span)
-            x = _BlockFn.apply(x, *blk.block_params(), bcfg)
+            x = run_block(x, blk.block_params(), bcfg)
         if cfg["defer_join"]:
             _Side(x.device).join()  # the side stream's half-batch chain of the last block
         return x

@@ -80,7 +80,8 @@ def register_capture_stream(stream, device=None):
 
 def linear_fwd(x2d, w, bias=None, epi=L.EPI_STORE, out=None, out_dtype=None, resid=None, act_out=None):
     """y = epi(x @ w^T + bias).  x2d [M,K] (row stride x2d.stride(0)), w [N,K] contiguous.
-    EPI_BIAS_GELU / EPI_BIAS_QGELU return (act'(pre), act(pre)) with pre = x @ w^T + bias."""
+    EPI_BIAS_GELU / EPI_BIAS_QGELU return (act'(pre), act(pre)) with pre = x @ w^T + bias;
+    EPI_BIAS_GELU_FWD / EPI_BIAS_QGELU_FWD (no backward follows) return act(pre) alone, the same bits."""
     L.require_gpu(x2d)
     M, K = x2d.shape
     N = w.shape[0]
@@ -487,6 +488,23 @@ def cross_entropy_bwd(logits, target, row_lse, grad_loss, out_dtype=torch.float3
     call("vit_cross_entropy_bwd", L.dt(d), B, C, ptr(logits), logits.stride(0), ptr(target), ptr(row_lse), ptr(g),
          ptr(d), d.stride(0), _s(logits))
     return d
+
+
+def eval_metrics(logits, target, acc, topk=5, row_ws=None):
+    """Add one batch's validation metrics into ``acc`` (f64 [6] on the device: mean loss, loss sum,
+    top-1 hits, top-k hits, rows, batches); nothing is synchronised.  ``row_ws``: f32 scratch of
+    >= 2 * B elements (taken from the allocator when absent)."""
+    L.require_gpu(logits)
+    B, C = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and target.dtype == torch.int64
+    assert target.is_contiguous() and target.numel() == B and target.device == logits.device
+    assert acc.dtype == torch.float64 and acc.numel() >= 6 and acc.is_contiguous() and acc.device == logits.device
+    if row_ws is None:
+        row_ws = torch.empty(2 * B, dtype=torch.float32, device=logits.device)
+    assert row_ws.dtype == torch.float32 and row_ws.numel() >= 2 * B
+    call("vit_eval_metrics", B, C, ptr(logits), logits.stride(0), ptr(target), int(topk), ptr(row_ws), ptr(acc),
+         _s(logits))
+    return acc
 
 
 def cast_bf16(src: torch.Tensor, dst: torch.Tensor):

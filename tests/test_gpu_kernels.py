@@ -280,6 +280,84 @@ def test_gemm_every_tile_config(variant):
         lib.vit_gemm_variant(-1)
 
 
+_FORM_SENTINEL = -512.0
+
+
+def _run_epilogue_forms(M, N, K, seed0):
+    """Every bf16 epilogue of an [M, N] output over K products into sentinel-padded [M + 3, N + 8]
+    buffers: {name: (C, aux_out or None)}."""
+    x = _rnd(M, K, seed=seed0, dtype=torch.bfloat16).to(DEV)
+    w = _rnd(N, K, seed=seed0 + 1, scale=K ** -0.5, dtype=torch.bfloat16).to(DEV)   # forward weight [N, K]
+    wt = _rnd(K, N, seed=seed0 + 2, scale=K ** -0.5, dtype=torch.bfloat16).to(DEV)  # dgrad weight: dX = dY wt
+    b = _rnd(N, seed=seed0 + 3, scale=0.5).to(DEV)
+    dactp = torch.zeros(M + 3, N + 8, dtype=torch.bfloat16, device=DEV)             # a saved act', ld = N + 8
+    dactp[:M, :N] = _gelu_grad(_rnd(M, N, seed=seed0 + 4)).to(torch.bfloat16).to(DEV)
+    s = L.stream_ptr(x.device)
+
+    def buf():
+        return torch.full((M + 3, N + 8), _FORM_SENTINEL, dtype=torch.bfloat16, device=DEV)
+
+    out = {}
+    for name, epi, bias, two in (("store", L.EPI_STORE, None, False), ("store+bias", L.EPI_STORE, b, False),
+                                 ("gelu pair", L.EPI_BIAS_GELU, b, True), ("qgelu pair", L.EPI_BIAS_QGELU, b, True),
+                                 ("gelu act", L.EPI_BIAS_GELU_FWD, b, False),
+                                 ("qgelu act", L.EPI_BIAS_QGELU_FWD, b, False)):
+        c, aux = buf(), (buf() if two else None)
+        L.call("vit_linear_fwd", L.BF16, L.BF16, epi, M, N, K, L.ptr(x), x.stride(0), L.ptr(w), L.ptr(bias), L.ptr(c),
+               c.stride(0), None, L.ptr(aux), s)
+        out[name] = (c, aux)
+    c = buf()
+    L.call("vit_linear_dgrad", L.BF16, L.BF16, L.EPI_GELU_BWD, M, K, N, L.ptr(x), x.stride(0), L.ptr(wt), L.ptr(c),
+           c.stride(0), L.ptr(dactp), None, None, 0, 0, s)
+    out["gelu' dgrad"] = (c, None)
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("N", [160, 136])
+@pytest.mark.parametrize("variant", [1, 2, 3, 5, 6, 7])
+def test_gemm_bf16_epilogue_forms_agree_bitwise(variant, N):
+    """The bf16 epilogue forms of big::gemm_tile -- MFMA-fragment stores, permlane16 fragment pairs, the f32
+    band staging and the bf16 tile image -- all apply the one epilogue definition (epi_vec and its
+    per-element core epi_act_pair), so within a tile configuration they write the same bits.  Each form is forced by
+    its timing bit (vit_gemm_variant(v + 100 * bits): 8 fragment, 16 permlane pairs, 64 / 128 band staging,
+    256 no bf16 image for the plain store); bits 1, 2 and 4 drop loads / barriers / the epilogue and are
+    not used.  M = 300 is ragged in every tile height; N = 160 is a multiple of 32 but of no tile width,
+    N = 136 a multiple of 8 only, so the permlane form declines and the fall-through runs; K = 128 is two
+    k-steps of the BK = 64 tiles.  Column sums are not compared (their summation order differs by form).
+    Measured on the commit before the epilogues were folded together: every pair agreed
+    (profiles/r08/epilogue_forms_parent.log)."""
+    lib = L.lib()
+    M, K = 300, 128
+    bits = (0, 8, 16, 64, 128, 256) if variant in (1, 2, 3, 5) else (0, 8)
+    bad = []
+    try:
+        ref = None
+        for bit in bits:
+            lib.vit_gemm_variant(variant + 100 * bit)
+            got = _run_epilogue_forms(M, N, K, seed0=60)
+            for name, pair in got.items():
+                for which, t in zip(("C", "aux_out"), pair):
+                    if t is None:
+                        continue
+                    what = f"variant {variant} bits {bit} {name} {which}"
+                    assert bool((t[:M, N:] == _FORM_SENTINEL).all()) and bool((t[M:] == _FORM_SENTINEL).all()), \
+                        what + ": wrote outside its [M, N] output"
+                    assert torch.isfinite(t[:M, :N].float()).all(), what
+                    assert not bool((t[:M, :N] == _FORM_SENTINEL).any()), what + ": output elements left unwritten"
+                    if ref is not None:
+                        r = ref[name][0 if which == "C" else 1]
+                        ndiff = int((t[:M, :N] != r[:M, :N]).sum())
+                        print(f"{what}: {ndiff} elements differ from bits 0")
+                        if not torch.equal(t[:M, :N], r[:M, :N]):
+                            bad.append(f"{what}: {ndiff} elements")
+            if ref is None:
+                ref = got
+    finally:
+        lib.vit_gemm_variant(-1)
+    assert not bad, "forms that differ from bits 0: " + "; ".join(bad)
+
+
 @pytest.mark.parametrize("M,N,K", [(197 * 3, 640, 448), (1024, 768, 96), (300, 132, 64)])
 def test_f32_mfma_gemm_every_layout_and_epilogue(M, N, K):
     """The fp32 MFMA kernel (v_mfma_f32_16x16x4_f32; the compute_dtype=float32 path and CLIP at

@@ -25,98 +25,23 @@
 
 #include "gemm_lds.hpp"
 #include "gemm_epi.hpp"
-// build-time switches of the bf16 epilogue forms (A/B builds: -DVIT_PAIR16=0 etc.)
-#ifndef VIT_PAIR16
-#define VIT_PAIR16 1
-#endif
-#ifndef VIT_PLAIN16
-#define VIT_PLAIN16 1
-#endif
-#ifndef VIT_GBWD_PREFETCH
-#define VIT_GBWD_PREFETCH 1
-#endif
-#ifndef VIT_SPLIT_ISSUE
-#define VIT_SPLIT_ISSUE 1
-#endif
-#ifndef VIT_SPLIT_ISSUE1
-#define VIT_SPLIT_ISSUE1 1
-#endif
 
-template <typename T> __device__ __forceinline__ void store4(T* p, f32x4 v);
-template <> __device__ __forceinline__ void store4<float>(float* p, f32x4 v) {
-  *reinterpret_cast<f32x4*>(p) = v;
+// act / act' of one pre-activation `pr`, already rounded to the storage type (the value a stored-pre design
+// would have differentiated) -- the per-element core of every epilogue form.  EXACT: the erf form of the
+// generic (parity) kernel; the MFMA kernels use the fast form.  (epilogue_pair16 runs the fast form on two
+// elements per call, gelu_fast_both2: the same operations, packed.)
+template <int EPI, bool EXACT = false>
+__device__ __forceinline__ void epi_act_pair(float pr, float& a, float& d) {
+  if constexpr (!epi_gelu(EPI)) quick_gelu_both(pr, a, d);
+  else if constexpr (EXACT) gelu_erf_both(pr, a, d);
+  else gelu_fast_both(pr, a, d);
 }
-template <> __device__ __forceinline__ void store4<bf16>(bf16* p, f32x4 v) {
-  bf16x4 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-  *reinterpret_cast<bf16x4*>(p) = o;
-}
-template <typename T> __device__ __forceinline__ f32x4 load4(const T* p);
-template <> __device__ __forceinline__ f32x4 load4<float>(const float* p) {
-  return *reinterpret_cast<const f32x4*>(p);
-}
-template <> __device__ __forceinline__ f32x4 load4<bf16>(const bf16* p) {
-  bf16x4 x = *reinterpret_cast<const bf16x4*>(p);
-  return f32x4{(float)x[0], (float)x[1], (float)x[2], (float)x[3]};
-}
-
-// Apply the epilogue to 4 consecutive output columns j..j+3 of row i.
-template <int EPI, typename TO, typename TA>
-__device__ __forceinline__ f32x4 epi4(const Epi& e, int i, int j, f32x4 v, int z = 0) {
-  if (e.bias) {
-    f32x4 b = *reinterpret_cast<const f32x4*>(e.bias + j);
-    v += b;
-  }
-  if constexpr (EPI == EPI_STORE) {
-    store4<TO>((TO*)e.C + e.slab * z + (int64_t)i * e.ldc + j, v);
-    return v;
-  } else if constexpr (EPI == EPI_ACC) {
-    TO* c = (TO*)e.C + (int64_t)i * e.ldc + j;
-    store4<TO>(c, v + load4<TO>(c));
-    return v;
-  } else if constexpr (epi_act(EPI)) {
-    // act and act' of the pre-activation rounded to the storage type (the value a
-    // stored-pre design would have differentiated); the act-only forms store act alone, as C
-    f32x4 a, d;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const float pr = (float)(TO)v[t];
-      float ga, gd;
-      if constexpr (epi_gelu(EPI)) gelu_fast_both(pr, ga, gd);
-      else quick_gelu_both(pr, ga, gd);
-      a[t] = ga;
-      d[t] = gd;
-    }
-    if constexpr (epi_act_only(EPI)) {
-      store4<TO>((TO*)e.C + (int64_t)i * e.ldc + j, a);
-    } else {
-      store4<TO>((TO*)e.C + (int64_t)i * e.ldc + j, d);
-      store4<TO>((TO*)e.aux_out + (int64_t)i * e.ldc + j, a);
-    }
-    return v;
-  } else if constexpr (EPI == EPI_RESID) {
-    f32x4 r = load4<float>((const float*)e.aux + (int64_t)i * e.ld_aux + j);
-    store4<TO>((TO*)e.C + (int64_t)i * e.ldc + j, v + r);
-    return v;
-  } else if constexpr (EPI == EPI_GELU_BWD || EPI == EPI_QGELU_BWD) {
-    v *= load4<TA>((const TA*)e.aux + (int64_t)i * e.ld_aux + j);
-    store4<TO>((TO*)e.C + (int64_t)i * e.ldc + j, v);
-  } else if constexpr (EPI == EPI_PATCH) {
-    int b = i / e.n_patch, p = i - b * e.n_patch;
-    int64_t row = (int64_t)b * (e.n_patch + 1) + 1 + p;
-    f32x4 ps = *reinterpret_cast<const f32x4*>(e.pos + (int64_t)(1 + p) * e.ldc + j);
-    store4<TO>((TO*)e.C + row * e.ldc + j, v + ps);
-    return v;
-  }
-  return v;
-}
-
-
 
 // ---------------------------------------------------------------------------
-// Row-contiguous epilogue (the bf16 fast kernels): V = 16 / sizeof(TO) consecutive
-// columns j..j+V-1 of row i per thread, so every global load and store is 16 B and
-// a wave's instruction covers whole 512-B row segments (the MFMA fragment layout
-// gives 8-B pieces of 16 different rows per instruction: store-issue-bound).
+// The epilogue, stated once (epi_vec below) for V consecutive columns j..j+V-1 of row i.  V = 4: an MFMA
+// fragment's 4 columns per lane (8-B bf16 / 16-B f32 pieces of 16 different rows per instruction).  V = 16 /
+// sizeof(TO): the row-contiguous sweeps of the bf16 fast kernels, where every global load and store is 16 B
+// and a wave's instruction covers whole 512-B row segments (the fragment layout is store-issue-bound).
 // ---------------------------------------------------------------------------
 template <int V> struct VecF { f32x4 q[V / 4]; };
 
@@ -137,9 +62,18 @@ template <> __device__ __forceinline__ void vload<bf16, 4>(const bf16* p, VecF<4
   const bf16x4 x = *reinterpret_cast<const bf16x4*>(p);
   v.q[0] = f32x4{(float)x[0], (float)x[1], (float)x[2], (float)x[3]};
 }
+template <typename T> __device__ __forceinline__ f32x4 load4(const T* p) {
+  VecF<4> v;
+  vload<T, 4>(p, v);
+  return v.q[0];
+}
 template <typename T, int V> __device__ __forceinline__ void vstore(T* p, const VecF<V>& v);
 template <> __device__ __forceinline__ void vstore<float, 4>(float* p, const VecF<4>& v) {
   *reinterpret_cast<f32x4*>(p) = v.q[0];
+}
+template <> __device__ __forceinline__ void vstore<bf16, 4>(bf16* p, const VecF<4>& v) {
+  const bf16x4 o = {(bf16)v.q[0][0], (bf16)v.q[0][1], (bf16)v.q[0][2], (bf16)v.q[0][3]};
+  *reinterpret_cast<bf16x4*>(p) = o;
 }
 template <> __device__ __forceinline__ void vstore<bf16, 8>(bf16* p, const VecF<8>& v) {
   const bf16x8 o = {(bf16)v.q[0][0], (bf16)v.q[0][1], (bf16)v.q[0][2], (bf16)v.q[0][3],
@@ -147,8 +81,9 @@ template <> __device__ __forceinline__ void vstore<bf16, 8>(bf16* p, const VecF<
   *reinterpret_cast<bf16x8*>(p) = o;
 }
 
-// Epilogue math on V columns; returns (in v) the value whose column sum a fused
-// bias gradient wants (what was stored as C, before a GELU activation).
+// Bias, then the per-EPI math, then the store(s); leaves in v the value whose column sum a fused bias
+// gradient wants (what was stored as C; the biased pre-activation for the activation epilogues).  z: the
+// split-r slab (EPI_STORE).
 template <int EPI, typename TO, typename TA, int V>
 __device__ __forceinline__ void epi_vec(const Epi& e, int i, int j, VecF<V>& v, int z) {
   if (e.bias) {
@@ -172,14 +107,12 @@ __device__ __forceinline__ void epi_vec(const Epi& e, int i, int j, VecF<V>& v, 
     for (int q = 0; q < V / 4; ++q)
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const float pr = (float)(TO)v.q[q][t];  // pre-activation rounded to the storage type
         float ga, gd;
-        if constexpr (epi_gelu(EPI)) gelu_fast_both(pr, ga, gd);
-        else quick_gelu_both(pr, ga, gd);
+        epi_act_pair<EPI>((float)(TO)v.q[q][t], ga, gd);
         a.q[q][t] = ga;
         d.q[q][t] = gd;
       }
-    if constexpr (epi_act_only(EPI)) {
+    if constexpr (epi_act_only(EPI)) {  // no backward follows: the activation alone, as C
       vstore<TO, V>((TO*)e.C + (int64_t)i * e.ldc + j, a);
     } else {
       vstore<TO, V>((TO*)e.C + (int64_t)i * e.ldc + j, d);
@@ -208,6 +141,30 @@ __device__ __forceinline__ void epi_vec(const Epi& e, int i, int j, VecF<V>& v, 
   }
 }
 
+// Fragment-layout epilogue of a wave's AI x AJ block of 16x16 accumulators `acc` at (IW, JW): acc[a][b] holds
+// C[i][j..j+3] with i = IW + 16 a + lane % 16, j = JW + 16 b + 4 (lane / 16); column sums are flushed per
+// 64-row group.  PRE_ROW runs in front of accumulator row a (w4 re-defines the row's registers there).  Uses
+// the caller's e, acc, lane, M, N, z and EPI / TO / TA, and declares cs in the caller's scope (it is each
+// kernel's last statement).  A macro because every function-shaped form of this loop changed the
+// instructions of the kernels around it (profiles/r08/README.md); the expansion is the text the four
+// kernels used to repeat.
+#define VIT_EPI_FRAG(AI, AJ, IW, JW, PRE_ROW)                                                         \
+  f32x4 cs[AJ];                                                                                       \
+  _Pragma("unroll") for (int b = 0; b < AJ; ++b) cs[b] = f32x4{0.f, 0.f, 0.f, 0.f};                   \
+  _Pragma("unroll") for (int a = 0; a < AI; ++a) {                                                    \
+    PRE_ROW;                                                                                          \
+    const int i = IW + a * 16 + (lane & 15);                                                          \
+    _Pragma("unroll") for (int b = 0; b < AJ; ++b) {                                                  \
+      const int j = JW + b * 16 + 4 * (lane >> 4);                                                    \
+      if (i < M && j < N) {                                                                           \
+        VecF<4> v{{acc[a][b]}};                                                                       \
+        epi_vec<EPI, TO, TA, 4>(e, i, j, v, z);                                                       \
+        if (e.csum) cs[b] += v.q[0];                                                                  \
+      }                                                                                               \
+    }                                                                                                 \
+    if (e.csum && (a & 3) == 3) csum_flush<AJ>(e, cs, IW + (a - 3) * 16, M, N, JW, lane);             \
+  }
+
 // LDS bytes the staged epilogue of a BM x BN tile needs: one WM-row band of f32
 // accumulators (rows padded by 16 B) + the column-sum reduction rows.
 template <class C, typename TO> struct EpiLds {
@@ -234,10 +191,8 @@ __device__ __forceinline__ f32x4 epi_val(const Epi& e, int i, int j, f32x4 v, bo
   if constexpr (epi_act(EPI)) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const float pr = (float)(TO)v[t];  // pre-activation rounded to the storage type
       float ga, gd;
-      if constexpr (epi_gelu(EPI)) gelu_fast_both(pr, ga, gd);
-      else quick_gelu_both(pr, ga, gd);
+      epi_act_pair<EPI>((float)(TO)v[t], ga, gd);
       o0[t] = epi_act_only(EPI) ? ga : gd;  // act-only: the activation is the one output (C)
       o1[t] = ga;
     }
@@ -306,7 +261,7 @@ __device__ __forceinline__ void epilogue_staged(const Epi& e, const f32x4 (&acc)
   // before band p's round, so their HBM latency hides under that round instead of stalling the next
   constexpr int NPRE = C::WM / EL::RL;
   constexpr bool PREF = (EPI == EPI_GELU_BWD || EPI == EPI_QGELU_BWD) && std::is_same<TA, bf16>::value &&
-                        V == 8 && NPRE <= 4 && VIT_GBWD_PREFETCH;
+                        V == 8 && NPRE <= 4;
   bf16x8 pre[PREF ? NPRE : 1], pre_next[PREF ? NPRE : 1];
   auto load_pre = [&](int p, bf16x8 (&dst)[PREF ? NPRE : 1]) {
 #pragma unroll
@@ -423,7 +378,7 @@ __device__ __forceinline__ void epilogue_pair16(const Epi& e, const f32x4 (&acc)
         *reinterpret_cast<bf16x8*>((bf16*)e.C + (int64_t)i * e.ldc + j) = x;
       } else {
         VecF<8> av, dv;
-        if constexpr (epi_gelu(EPI)) {  // two elements per call (packed FP32; same bits)
+        if constexpr (epi_gelu(EPI)) {  // epi_act_pair on two elements per call (packed FP32; same bits)
 #pragma unroll
           for (int q = 0; q < 8; q += 2) {
             f32x2 ga, gd;
@@ -437,7 +392,7 @@ __device__ __forceinline__ void epilogue_pair16(const Epi& e, const f32x4 (&acc)
 #pragma unroll
           for (int q = 0; q < 8; ++q) {
             float ga, gd;
-            quick_gelu_both((float)x[q], ga, gd);
+            epi_act_pair<EPI>((float)x[q], ga, gd);
             av.q[q >> 2][q & 3] = ga;
             dv.q[q >> 2][q & 3] = gd;
           }
@@ -453,7 +408,8 @@ __device__ __forceinline__ void epilogue_pair16(const Epi& e, const f32x4 (&acc)
   }
 }
 
-// Scalar form for the generic kernel (ragged edges).
+// Scalar form for the generic kernel (ragged edges, any alignment): epi_vec's branches one element at a
+// time, with the exact (erf) activation core -- the generic kernel is the parity path.
 template <int EPI, typename TO, typename TA>
 __device__ __forceinline__ void epi1(const Epi& e, int i, int j, float v) {
   if (e.bias) v += e.bias[j];
@@ -463,10 +419,8 @@ __device__ __forceinline__ void epi1(const Epi& e, int i, int j, float v) {
     TO* c = (TO*)e.C + (int64_t)i * e.ldc + j;
     *c = (TO)((float)*c + v);
   } else if constexpr (epi_act(EPI)) {
-    const float pf = (float)(TO)v;
     float a, d;
-    if constexpr (epi_gelu(EPI)) gelu_erf_both(pf, a, d);
-    else quick_gelu_both(pf, a, d);
+    epi_act_pair<EPI, true>((float)(TO)v, a, d);
     if constexpr (epi_act_only(EPI)) {
       ((TO*)e.C)[(int64_t)i * e.ldc + j] = (TO)a;
     } else {
@@ -489,9 +443,8 @@ __device__ __forceinline__ void epi1(const Epi& e, int i, int j, float v) {
 // Fast bf16 kernel, parametrised: BM x BN x BK tile, WI x WJ waves (each a
 // (BM/WI) x (BN/WJ) wave tile of 16x16 accumulators), an S-deep LDS ring filled
 // by global_load_lds with a counted vmcnt (S-2 k-steps stay in flight across the
-// single s_barrier per k-step), optional register double-buffering of the MFMA
-// fragments (DB: the next k-step's ds_reads overlap this k-step's MFMAs), OCC =
-// minimum waves per SIMD (sets the VGPR budget / workgroups per CU).
+// single s_barrier per k-step), OCC = minimum waves per SIMD (sets the VGPR budget /
+// workgroups per CU).
 // ----------------------------------------------------------------------------
 namespace big {
 
@@ -499,9 +452,8 @@ namespace big {
 // tile and the GELU epilogues), 1 = straight from the MFMA fragments (permlane16-widened 16-B bf16
 // stores, 16-B f32 stores) -- no LDS, so the kernel's LDS is its ring alone and two workgroups
 // share a CU: one's epilogue runs beside the other's MFMAs.
-template <int BM_, int BN_, int BK_, int WI_, int WJ_, int S_, bool DB_, int OCC_, int EPS_ = 0> struct Cfg {
+template <int BM_, int BN_, int BK_, int WI_, int WJ_, int S_, int OCC_, int EPS_ = 0> struct Cfg {
   static constexpr int BM = BM_, BN = BN_, BK = BK_, WI = WI_, WJ = WJ_, STAGES = S_, OCC = OCC_, EPS = EPS_;
-  static constexpr bool DB = DB_;
   static constexpr int WAVES = WI * WJ, THREADS = WAVES * 64;
   static constexpr int WM = BM / WI, WN = BN / WJ;
   static constexpr int AI = WM / 16, AJ = WN / 16, KS = BK / 32;
@@ -514,51 +466,6 @@ template <int BM_, int BN_, int BK_, int WI_, int WJ_, int S_, bool DB_, int OCC
   static_assert(AI % 4 == 0, "column-sum epilogue works on 64-row groups");
   static_assert(LDS <= 163840, "LDS");
 };
-
-
-// Stage a ROWS x BK operand tile into an LDS image; each wave issues G_OP 1-KiB
-// global_load_lds.  Rows (RC) / columns (CR) past `lim` are clamped to valid
-// memory; their outputs are never stored.
-template <int LAY, int ROWS, int BK, int G_OP>
-__device__ __forceinline__ void stage(char* img, const bf16* __restrict__ base, int64_t ld, int row0, int r0,
-                                      int lim, int wave, int lane) {
-#pragma unroll
-  for (int u = 0; u < G_OP; ++u) {
-    const int t = wave * G_OP + u;
-    const bf16* src;
-    if constexpr (LAY == LAY_RC) {
-      constexpr int CPR = BK / 8, RPI = 64 / CPR;
-      const int row = t * RPI + lane / CPR;
-      const int c = (lane % CPR) ^ rc_sw<BK>(row);
-      const int grow = min(row0 + row, lim - 1);
-      src = base + (int64_t)grow * ld + r0 + c * 8;
-    } else {
-      constexpr int CPR = ROWS / 8;  // 16-B chunks per r-row
-      constexpr int RPI = 64 / CPR;  // r-rows per wave-instruction
-      const int r = t * RPI + lane / CPR;
-      const int c = cr_swz(lane % CPR, r);
-      const int col = min(row0 + c * 8, lim - 8);
-      src = base + (int64_t)(r0 + r) * ld + col;
-    }
-    __builtin_amdgcn_global_load_lds((const void*)src, LDS_PTR(img + t * 1024), 16, 0, 0);
-  }
-}
-
-// fragment of rows s*16..s*16+15, k-substep kk (16x16x32 operand, natural k order)
-template <int LAY, int ROWS, int BK>
-__device__ __forceinline__ bf16x8 frag(const char* img, int s, int kk, int lane) {
-  if constexpr (LAY == LAY_RC) {
-    return *reinterpret_cast<const bf16x8*>(img + rc_off<BK>(s * 16 + (lane & 15), kk * 4 + (lane >> 4)));
-  } else {
-    const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-    const int c = 2 * s + (p >> 1);
-    const int r0 = kk * 32 + 8 * g + q;
-    bf16x4 lo = lds_read_tr(img + cr_off<ROWS>(r0, c) + (p & 1) * 8);
-    bf16x4 hi = lds_read_tr(img + cr_off<ROWS>(r0 + 4, c) + (p & 1) * 8);
-    return cat4(lo, hi);
-  }
-}
-
 
 // One output tile (unit w of the 1-D (split, tile) space) of the fast bf16 GEMM.
 template <class C, int PL, int QL, int EPI, typename TO, typename TA>
@@ -585,9 +492,9 @@ __device__ __forceinline__ void gemm_tile(const bf16* __restrict__ P, int64_t ld
 #pragma unroll
     for (int b = 0; b < C::AJ; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // staging sources: a k-independent per-lane byte offset of each 1-KiB piece (stage()'s
-  // addressing) plus a wave-uniform base advanced per k-step, so the loads take the SGPR-base
-  // form with no per-piece 64-bit address arithmetic (host side guarantees offsets < 2^32)
+  // staging sources: a k-independent per-lane byte offset of each 1-KiB piece plus a wave-uniform
+  // base advanced per k-step, so the loads take the SGPR-base form with no per-piece 64-bit address
+  // arithmetic (host side guarantees offsets < 2^32)
   uint32_t poff[C::GP], qoff[C::GQ];
   auto lane_offsets = [&](auto lay_tag, auto rows_tag, uint32_t* off, int G_OP, int64_t ld, int row0, int lim) {
     constexpr int LAY = decltype(lay_tag)::value, ROWS = decltype(rows_tag)::value;
@@ -633,16 +540,9 @@ __device__ __forceinline__ void gemm_tile(const bf16* __restrict__ P, int64_t ld
   // reads, its Q pieces before the second's, instead of all of them behind the barrier (the waves of a
   // SIMD reach the barrier together, so a burst of LDS-DMA issue there stalls both of their MFMA
   // streams at once: +3-8 % main loop, tools/lab/mf32_lab.py, profiles/r04/gemm_load_split_lab.jsonl)
-  constexpr bool SPLIT_ISSUE = C::KS == 2 && VIT_SPLIT_ISSUE;
+  constexpr bool SPLIT_ISSUE = C::KS == 2;
   // one k-substep (BK = 32): the P pieces behind the barrier, the Q pieces behind the MFMAs
-  constexpr bool SPLIT_ISSUE1 = C::KS == 1 && VIT_SPLIT_ISSUE1;
-  auto load_frags = [&](int k, int kk, bf16x8 (&pf)[C::AI], bf16x8 (&qf)[C::AJ]) {
-    const char* cur = smem + (k % S) * C::STAGE;
-#pragma unroll
-    for (int b = 0; b < C::AJ; ++b) qf[b] = frag<QL, BN, BK>(cur + C::PIMG, wj * C::AJ + b, kk, lane);
-#pragma unroll
-    for (int a = 0; a < C::AI; ++a) pf[a] = frag<PL, BM, BK>(cur, wi * C::AI + a, kk, lane);
-  };
+  constexpr bool SPLIT_ISSUE1 = C::KS == 1;
   auto mma = [&](const bf16x8 (&pf)[C::AI], const bf16x8 (&qf)[C::AJ]) {
 #pragma unroll
     for (int a = 0; a < C::AI; ++a)
@@ -674,82 +574,56 @@ __device__ __forceinline__ void gemm_tile(const bf16* __restrict__ P, int64_t ld
 #pragma unroll
     for (int k = 0; k < S - 1; ++k)
       if (k < nk && !dbg_noload) issue(k);
-    if constexpr (!C::DB) {
-      for (int kt = 0; kt < nk; ++kt) {
-        wait_stages<C::G, S>(min(S - 2, nk - 1 - kt));
-        if (!dbg_nobar) lds_barrier();
-        const bool more = kt + S - 1 < nk && !dbg_noload;
-        if (!SPLIT_ISSUE && more) issue(kt + S - 1, SPLIT_ISSUE1 ? 1 : 3);
-        Unroll<C::KS>::run([&](auto kkI) {
-          constexpr int kk = decltype(kkI)::value;
-          if constexpr (SPLIT_ISSUE) {
-            if (more) issue(kt + S - 1, kk + 1);
-          }
-          // asm fragment reads (no compiler vmcnt(0) for the in-flight ring loads);
-          // retired before the MFMAs, so they are also done before the next barrier (WAR)
-          const uint32_t cur = lds_addr(smem + (kt % S) * C::STAGE);
-          bf16x8 pf[C::AI], qf[C::AJ];
-          if constexpr (QL == LAY_RC) {  // fragment b = lane base + b * 16 rows (immediate)
-            const uint32_t qa = cur + C::PIMG + rc_lane[1][kk];
-            Unroll<C::AJ>::run([&](auto bI) {
-              constexpr int b = decltype(bI)::value;
-              qf[b] = asm_read128_off<b * 16 * BK * 2>(qa);
-            });
-          } else if constexpr (VIT_CR_HB) {
-            Unroll<C::AJ>::run([&](auto bI) {
-              constexpr int b = decltype(bI)::value;
-              qf[b] = frag_crh<BN, kk, b>(crh_q, cur);
-            });
-          } else {
-#pragma unroll
-            for (int b = 0; b < C::AJ; ++b) qf[b] = frag_asm<QL, BN, BK>(cur + C::PIMG, wj * C::AJ + b, kk, lane);
-          }
-          if constexpr (PL == LAY_RC) {
-            const uint32_t pa = cur + rc_lane[0][kk];
-            Unroll<C::AI>::run([&](auto aI) {
-              constexpr int a = decltype(aI)::value;
-              pf[a] = asm_read128_off<a * 16 * BK * 2>(pa);
-            });
-          } else if constexpr (VIT_CR_HB) {
-            Unroll<C::AI>::run([&](auto aI) {
-              constexpr int a = decltype(aI)::value;
-              pf[a] = frag_crh<BM, kk, a>(crh_p, cur);
-            });
-          } else {
-#pragma unroll
-            for (int a = 0; a < C::AI; ++a) pf[a] = frag_asm<PL, BM, BK>(cur, wi * C::AI + a, kk, lane);
-          }
-          lgkm_wait0();
-          mma(pf, qf);
-        });
-        if constexpr (SPLIT_ISSUE1) {
-          if (more) issue(kt + S - 1, 2);
+    for (int kt = 0; kt < nk; ++kt) {
+      wait_stages<C::G, S>(min(S - 2, nk - 1 - kt));
+      if (!dbg_nobar) lds_barrier();
+      const bool more = kt + S - 1 < nk && !dbg_noload;
+      if (!SPLIT_ISSUE && more) issue(kt + S - 1, SPLIT_ISSUE1 ? 1 : 3);
+      Unroll<C::KS>::run([&](auto kkI) {
+        constexpr int kk = decltype(kkI)::value;
+        if constexpr (SPLIT_ISSUE) {
+          if (more) issue(kt + S - 1, kk + 1);
         }
-      }
-    } else {
-      static_assert(C::KS == 1, "register double-buffering is built for BK = 32");
-      static_assert(!(VIT_CR_HB && (PL == LAY_CR || QL == LAY_CR)), "load_frags reads the swizzled CR image");
-      // step k: make stage k+1 readable, refill slot k%S with stage k+S-1... (ring of S, S-1 ahead)
-      auto step = [&](int k, const bf16x8 (&pc)[C::AI], const bf16x8 (&qc)[C::AJ], bf16x8 (&pn)[C::AI],
-                      bf16x8 (&qn)[C::AJ]) {
-        if (k + 1 < nk) {
-          wait_stages<C::G, S>(min(S - 3, nk - 2 - k));
-          lds_barrier();
-          if (k + S - 1 < nk) issue(k + S - 1);
-          load_frags(k + 1, 0, pn, qn);
+        // asm fragment reads (no compiler vmcnt(0) for the in-flight ring loads);
+        // retired before the MFMAs, so they are also done before the next barrier (WAR)
+        const uint32_t cur = lds_addr(smem + (kt % S) * C::STAGE);
+        bf16x8 pf[C::AI], qf[C::AJ];
+        if constexpr (QL == LAY_RC) {  // fragment b = lane base + b * 16 rows (immediate)
+          const uint32_t qa = cur + C::PIMG + rc_lane[1][kk];
+          Unroll<C::AJ>::run([&](auto bI) {
+            constexpr int b = decltype(bI)::value;
+            qf[b] = asm_read128_off<b * 16 * BK * 2>(qa);
+          });
+        } else if constexpr (VIT_CR_HB) {
+          Unroll<C::AJ>::run([&](auto bI) {
+            constexpr int b = decltype(bI)::value;
+            qf[b] = frag_crh<BN, kk, b>(crh_q, cur);
+          });
+        } else {
+#pragma unroll
+          for (int b = 0; b < C::AJ; ++b) qf[b] = frag_asm<QL, BN, BK>(cur + C::PIMG, wj * C::AJ + b, kk, lane);
         }
-        mma(pc, qc);
-      };
-      bf16x8 pA[C::AI], qA[C::AJ], pB[C::AI], qB[C::AJ];
-      wait_stages<C::G, S>(min(S - 2, nk - 1));
-      lds_barrier();
-      load_frags(0, 0, pA, qA);
-      int kt = 0;
-      for (; kt + 1 < nk; kt += 2) {
-        step(kt, pA, qA, pB, qB);
-        step(kt + 1, pB, qB, pA, qA);
+        if constexpr (PL == LAY_RC) {
+          const uint32_t pa = cur + rc_lane[0][kk];
+          Unroll<C::AI>::run([&](auto aI) {
+            constexpr int a = decltype(aI)::value;
+            pf[a] = asm_read128_off<a * 16 * BK * 2>(pa);
+          });
+        } else if constexpr (VIT_CR_HB) {
+          Unroll<C::AI>::run([&](auto aI) {
+            constexpr int a = decltype(aI)::value;
+            pf[a] = frag_crh<BM, kk, a>(crh_p, cur);
+          });
+        } else {
+#pragma unroll
+          for (int a = 0; a < C::AI; ++a) pf[a] = frag_asm<PL, BM, BK>(cur, wi * C::AI + a, kk, lane);
+        }
+        lgkm_wait0();
+        mma(pf, qf);
+      });
+      if constexpr (SPLIT_ISSUE1) {
+        if (more) issue(kt + S - 1, 2);
       }
-      if (kt < nk) step(kt, pA, qA, pB, qB);
     }
   }
   if (e.dbg & 4) {  // timing experiment: keep the accumulators live, skip the epilogue
@@ -759,70 +633,61 @@ __device__ __forceinline__ void gemm_tile(const bf16* __restrict__ P, int64_t ld
       for (int b = 0; b < C::AJ; ++b) asm volatile("" ::"v"(acc[a][b]));
     return;
   }
-  // bf16 outputs: row-contiguous epilogue through LDS (16-B stores; dbg bit 8 forces the
-  // fragment-layout one, for timing).  f32 fragments already store 16 B per lane.
-  // bf16 outputs: plain stores of the smaller tiles go out as fragment pairs widened to 16-B
-  // stores by permlane16_swap (N % 32 == 0; +2-5 % over staging on the N = 768 outputs); the
-  // 256x256 tile and the GELU / GELU' epilogues are faster through the row-contiguous LDS
-  // staging (tools/bench_kernels.py --sweep: v vs 6400 + v).  Timing flags: dbg 64 forces the
-  // staged epilogue, dbg 8 the plain fragment-layout one below (8-B stores).
-  // (plain bf16 stores: fragment epilogue on every tile -- the qkv forward on the 256x256 tile runs 10 %
-  // faster than through the LDS staging, tools/bench_kernels.py --sweep=5,1605; the GELU pair stays staged)
+  // The epilogue takes one of four forms, all applying epi_vec / epi_act_pair (same bits).  f32 outputs
+  // always take the fragment form (a lane's 4 columns are already a 16-B store).  bf16 outputs:
+  //   fragment (VIT_EPI_FRAG): 8-B stores straight from the MFMA fragments; what is left when no other form
+  //     applies (N % 32 != 0 on the fragment-style configurations); timing bit 8 forces it.
+  //   permlane pairs (epilogue_swap): fragment pairs widened to 16-B stores by permlane16_swap, no LDS;
+  //     needs N % 32 == 0.  The default of the plain store on every tile (+2-5 % over staging on the N = 768
+  //     outputs, 10 % on the qkv forward's 256x256 tile) and of every epilogue of the fragment-style
+  //     configurations (EPS = 1: V6, V7); timing bit 16 forces it on the staged-style ones.
+  //   f32 band staging (epilogue_staged): accumulators through LDS one WM-row band at a time, row-contiguous
+  //     16-B sweeps, fused column sums.  The staged-style configurations' form for every epilogue no other
+  //     form takes (GELU'; a GELU pair with column sums or N % 8 != 0; ...); timing bit 64 forces it over the
+  //     plain store's forms, 128 over the activation image.
+  //   bf16 image (epilogue_pair16): bf16(acc + bias) of the whole tile through one LDS image, one barrier;
+  //     needs N % 8 == 0, no column sums and room in the kernel's LDS.  The default of the activation
+  //     epilogues on the staged-style configurations and of the plain store on their 256x256 tile (+1-4 %
+  //     standalone over the pairs, profiles/r03/gemm_plain_store_bf16_stage_sweep.jsonl); timing bit 256
+  //     sends that plain store back to the pairs.
+  // (tools/bench_kernels.py --sweep: v against 800 / 1600 / 6400 / 12800 / 25600 + v.)  The conditions below
+  // are tried in order; folding them into one choice function changed the code of 63 bf16 kernels (it
+  // merges the two inlined copies of epilogue_swap), so the cascade stays until that is timed.
+  constexpr bool IMG_FITS = Pair16<C>::BYTES <= (C::LDS > EpiLds<C, TO>::BYTES ? C::LDS : EpiLds<C, TO>::BYTES);
   if constexpr (sizeof(TO) == 2 && (EPI == EPI_STORE ||
                                      (C::EPS == 1 && (EPI == EPI_STORE || epi_act(EPI) || EPI == EPI_GELU_BWD ||
                                                       EPI == EPI_QGELU_BWD)))) {
-    if constexpr (EPI == EPI_STORE && C::EPS == 0 && C::BM == 256 && C::BN == 256 &&
-                  Pair16<C>::BYTES <= (C::LDS > EpiLds<C, TO>::BYTES ? C::LDS : EpiLds<C, TO>::BYTES)) {
-      // the 256x256 tile: the plain bf16 store through the bf16 LDS image of the tile as well (+1-4 %
-      // standalone over the fragment stores, profiles/r03/gemm_plain_store_bf16_stage_sweep.jsonl);
-      // dbg 256 forces the fragment stores (A/B)
-      if (VIT_PLAIN16 && !(e.dbg & (8 | 64 | 256)) && !e.csum && N % 8 == 0) {
+    if constexpr (EPI == EPI_STORE && C::EPS == 0 && C::BM == 256 && C::BN == 256 && IMG_FITS) {
+      if (!(e.dbg & (8 | 64 | 256)) && !e.csum && N % 8 == 0) {  // plain store, 256x256 tile: bf16 image
         epilogue_pair16<C, EPI>(e, acc, smem, i0, j0, wi, wj, lane, M, N);
         return;
       }
     }
-    if (!(e.dbg & (8 | 64)) && N % 32 == 0) {
+    if (!(e.dbg & (8 | 64)) && N % 32 == 0) {  // plain store / fragment-style configuration: permlane pairs
       epilogue_swap<C, EPI, TO, TA>(e, acc, i0, j0, wi, wj, lane, M, N);
       return;
     }
   }
   if constexpr (sizeof(TO) == 2 && C::EPS == 0 && (EPI == EPI_STORE || epi_act(EPI) ||
                                                     EPI == EPI_GELU_BWD || EPI == EPI_QGELU_BWD)) {
-    if ((e.dbg & 16) && N % 32 == 0) {  // timing experiment: the fragment (permlane16) epilogue on any tile
+    if ((e.dbg & 16) && N % 32 == 0) {  // timing bit 16: permlane pairs on a staged-style configuration
       epilogue_swap<C, EPI, TO, TA>(e, acc, i0, j0, wi, wj, lane, M, N);
       return;
     }
   }
-  if constexpr (sizeof(TO) == 2 && C::EPS == 0 && epi_act(EPI) &&
-                Pair16<C>::BYTES <= (C::LDS > EpiLds<C, TO>::BYTES ? C::LDS : EpiLds<C, TO>::BYTES)) {
-    if (VIT_PAIR16 && !e.csum && !(e.dbg & (8 | 128)) && N % 8 == 0) {  // dbg 128: the f32 band staging (A/B)
+  if constexpr (sizeof(TO) == 2 && C::EPS == 0 && epi_act(EPI) && IMG_FITS) {
+    if (!e.csum && !(e.dbg & (8 | 128)) && N % 8 == 0) {  // activation epilogues: bf16 image
       epilogue_pair16<C, EPI>(e, acc, smem, i0, j0, wi, wj, lane, M, N);
       return;
     }
   }
   if constexpr (sizeof(TO) == 2 && C::EPS == 0) {
-    if (!(e.dbg & 8)) {
+    if (!(e.dbg & 8)) {  // staged-style configuration: f32 band staging
       epilogue_staged<C, EPI, TO, TA>(e, acc, smem, i0, j0, wi, wj, lane, M, N, z);
       return;
     }
   }
-  // epilogue: acc[a][b] holds C[i][j..j+3] with i = lane&15, j = 4*(lane>>4)
-  f32x4 cs[C::AJ];
-#pragma unroll
-  for (int b = 0; b < C::AJ; ++b) cs[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int a = 0; a < C::AI; ++a) {
-    const int i = i0 + wi * C::WM + a * 16 + (lane & 15);
-#pragma unroll
-    for (int b = 0; b < C::AJ; ++b) {
-      const int j = j0 + wj * C::WN + b * 16 + 4 * (lane >> 4);
-      if (i < M && j < N) {
-        const f32x4 v = epi4<EPI, TO, TA>(e, i, j, acc[a][b], z);
-        if (e.csum) cs[b] += v;
-      }
-    }
-    if (e.csum && (a & 3) == 3) csum_flush<C::AJ>(e, cs, i0 + wi * C::WM + (a - 3) * 16, M, N, j0 + wj * C::WN, lane);
-  }
+  VIT_EPI_FRAG(C::AI, C::AJ, i0 + wi * C::WM, j0 + wj * C::WN, )
 }
 
 // 1-D grid over (split, tile): consecutive ids share an XCD after the remap, so a split's
@@ -1039,22 +904,7 @@ __device__ __forceinline__ void pp_tile(const bf16* __restrict__ P, int64_t ldp,
       for (int b = 0; b < 4; ++b) asm volatile("" ::"v"(acc[a][b]));
     return;
   }
-  f32x4 cs[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) cs[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int a = 0; a < 8; ++a) {
-    const int i = i0 + grp * 128 + a * 16 + (lane & 15);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int j = j0 + wj * 64 + b * 16 + 4 * (lane >> 4);
-      if (i < M && j < N) {
-        const f32x4 v = epi4<EPI, TO, TA>(e, i, j, acc[a][b], z);
-        if (e.csum) cs[b] += v;
-      }
-    }
-    if (e.csum && (a & 3) == 3) csum_flush<4>(e, cs, i0 + grp * 128 + (a - 3) * 16, M, N, j0 + wj * 64, lane);
-  }
+  VIT_EPI_FRAG(8, 4, i0 + grp * 128, j0 + wj * 64, )
 }
 
 template <int S, int PL, int QL, int EPI, typename TO, typename TA>
@@ -1089,16 +939,16 @@ __global__ __launch_bounds__(512, 1) void pp_kernel2(PPProb a, PPProb b) {
 // double-buffering (1 WG/CU; wgrad 360-400 TF), 128x128x32 S4, 256x128x64 S3, 128x256x32 S4,
 // 256x256x32 S3 / S4 (V5's waves, deeper ring: qkv forward +6 % standalone, the other shapes flat
 // or slower; as the in-step weight gradient -0.4 .. -0.7 % step rate vs the ping-pong kernel).
-//            BM   BN  BK WI WJ  S  DB    OCC
-using V1 = Cfg<256, 128, 32, 4, 2, 3, false, 4>;  //  72 KiB, 2 WG/CU: dgrad
-using V2 = Cfg<128, 128, 64, 2, 2, 2, false, 2>;  //  64 KiB, 2 WG/CU (4 waves): N = 768 forward
-using V5 = Cfg<256, 256, 64, 2, 4, 2, false, 2>;  // 128 KiB, 1 WG/CU: wide forward, wgrad
-using V3 = Cfg<128, 256, 32, 2, 2, 3, false, 2>;  //  72 KiB, 2 WG/CU (4 waves of 64x128)
-using V4 = Cfg<256, 128, 32, 4, 2, 4, false, 4>;  //  96 KiB, 1 WG/CU, 4-deep ring
+//            BM   BN  BK WI WJ  S OCC
+using V1 = Cfg<256, 128, 32, 4, 2, 3, 4>;  //  72 KiB, 2 WG/CU: dgrad
+using V2 = Cfg<128, 128, 64, 2, 2, 2, 2>;  //  64 KiB, 2 WG/CU (4 waves): N = 768 forward
+using V5 = Cfg<256, 256, 64, 2, 4, 2, 2>;  // 128 KiB, 1 WG/CU: wide forward, wgrad
+using V3 = Cfg<128, 256, 32, 2, 2, 3, 2>;  //  72 KiB, 2 WG/CU (4 waves of 64x128)
+using V4 = Cfg<256, 128, 32, 4, 2, 4, 4>;  //  96 KiB, 1 WG/CU, 4-deep ring
 // 4 waves of 128x64 (V5's wave tile), 3-deep ring, epilogue from the fragments: 72 KiB -> 2
 // workgroups per CU (one wave per SIMD each), whose epilogues overlap each other's MFMAs
-using V6 = Cfg<256, 128, 32, 2, 2, 3, false, 2, 1>;
-using V7 = Cfg<128, 256, 32, 2, 2, 3, false, 2, 1>;  // 4 waves of 64x128
+using V6 = Cfg<256, 128, 32, 2, 2, 3, 2, 1>;
+using V7 = Cfg<128, 256, 32, 2, 2, 3, 2, 1>;  // 4 waves of 64x128
 }  // namespace big
 
 #include "gemm_f32.inc"
@@ -1297,64 +1147,51 @@ static int r_chunk_for(int R, int split, int bk) {
   return c > 0 ? c : bk;
 }
 
-template <class C, int PL, int QL, int EPI, typename TO, typename TA>
-static int launch_big(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
-                      const Epi& e, hipStream_t s) {
-  constexpr int lds = (C::EPS == 1 || C::LDS > EpiLds<C, TO>::BYTES) ? C::LDS : EpiLds<C, TO>::BYTES;
-  static_assert(lds <= 163840, "LDS");
+// Launch `units` workgroups of a 1-D-grid kernel with LDS bytes of dynamic shared memory (raising the
+// kernel's limit once per instantiation).
+template <auto KERNEL, int THREADS, int LDS, class... A>
+static int launch_1d(int units, hipStream_t s, const A&... args) {
+  static_assert(LDS <= 163840, "LDS");
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)big::gemm_kernel<C, PL, QL, EPI, TO, TA>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     attr = true;
   }
-  if (R % C::BK) return (int)hipErrorInvalidValue;
-  const int r_chunk = r_chunk_for(R, split, 64);  // one chunking for every variant (wgrad counts slabs)
-  const int nz = (R + r_chunk - 1) / r_chunk;
-  dim3 grid(((M + C::BM - 1) / C::BM) * ((N + C::BN - 1) / C::BN) * nz);
-  hipLaunchKernelGGL((big::gemm_kernel<C, PL, QL, EPI, TO, TA>), grid, dim3(C::THREADS), lds, s,
-                     (const bf16*)P, ldp, (const bf16*)Q, ldq, M, N, R, r_chunk, e);
+  hipLaunchKernelGGL(KERNEL, dim3(units), dim3(THREADS), LDS, s, args...);
   VIT_CHECK_LAUNCH();
   return 0;
 }
-
+// The bf16 kernels over the (split, tile) space of BM x BN tiles with BK-row k-steps.  One chunking of the
+// reduction for every kernel (the weight gradient's callers count slabs: vit_linear_wgrad_nslabs).
+template <auto KERNEL, int THREADS, int LDS, int BM, int BN, int BK>
+static int launch_tiles(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
+                        const Epi& e, hipStream_t s) {
+  if (R % BK) return (int)hipErrorInvalidValue;
+  const int r_chunk = r_chunk_for(R, split, 64);
+  const int nz = (R + r_chunk - 1) / r_chunk;
+  return launch_1d<KERNEL, THREADS, LDS>(((M + BM - 1) / BM) * ((N + BN - 1) / BN) * nz, s, (const bf16*)P, ldp,
+                                         (const bf16*)Q, ldq, M, N, R, r_chunk, e);
+}
+template <class C, int PL, int QL, int EPI, typename TO, typename TA>
+static int launch_big(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
+                      const Epi& e, hipStream_t s) {
+  // the ring, or the staged epilogue's band + column-sum rows where that is larger
+  constexpr int lds = (C::EPS == 1 || C::LDS > EpiLds<C, TO>::BYTES) ? C::LDS : EpiLds<C, TO>::BYTES;
+  return launch_tiles<big::gemm_kernel<C, PL, QL, EPI, TO, TA>, C::THREADS, lds, C::BM, C::BN, C::BK>(
+      P, ldp, Q, ldq, M, N, R, split, e, s);
+}
 template <int S, int PL, int QL, int EPI, typename TO, typename TA>
 static int launch_pp(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
                      const Epi& e, hipStream_t s) {
   using C = big::PP<S>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)big::pp_kernel<S, PL, QL, EPI, TO, TA>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    attr = true;
-  }
-  if (R % C::BK) return (int)hipErrorInvalidValue;
-  const int r_chunk = r_chunk_for(R, split, 64);
-  const int nz = (R + r_chunk - 1) / r_chunk;
-  dim3 grid(((M + 255) / 256) * ((N + 255) / 256) * nz);
-  hipLaunchKernelGGL((big::pp_kernel<S, PL, QL, EPI, TO, TA>), grid, dim3(C::THREADS), C::LDS, s,
-                     (const bf16*)P, ldp, (const bf16*)Q, ldq, M, N, R, r_chunk, e);
-  VIT_CHECK_LAUNCH();
-  return 0;
+  return launch_tiles<big::pp_kernel<S, PL, QL, EPI, TO, TA>, C::THREADS, C::LDS, C::BM, C::BN, C::BK>(
+      P, ldp, Q, ldq, M, N, R, split, e, s);
 }
-
 template <class C, int PL, int QL, int EPI, typename TO, typename TA>
 static int launch_w4(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
                      const Epi& e, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)w4::kernel<C, PL, QL, EPI, TO, TA>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    attr = true;
-  }
-  if (R % w4::BK) return (int)hipErrorInvalidValue;
-  const int r_chunk = r_chunk_for(R, split, 64);
-  const int nz = (R + r_chunk - 1) / r_chunk;
-  dim3 grid(((M + 255) / 256) * ((N + 255) / 256) * nz);
-  hipLaunchKernelGGL((w4::kernel<C, PL, QL, EPI, TO, TA>), grid, dim3(C::THREADS), C::LDS, s, (const bf16*)P, ldp,
-                     (const bf16*)Q, ldq, M, N, R, r_chunk, e);
-  VIT_CHECK_LAUNCH();
-  return 0;
+  return launch_tiles<w4::kernel<C, PL, QL, EPI, TO, TA>, C::THREADS, C::LDS, 256, 256, w4::BK>(
+      P, ldp, Q, ldq, M, N, R, split, e, s);
 }
 
 static int num_cus() {
@@ -1882,37 +1719,20 @@ int vit_linear_wgrad_partials2(int M, int split, int Na, int Ka, const void* dYa
   const big::PPProb a = prob(dYa, lddya, Xa, ldxa, Na, Ka, slabs_a), b = prob(dYb, lddyb, Xb, ldxb, Nb, Kb, slabs_b);
   // the weight-gradient kernel pick_variant chooses: 11-15 = w4 and its ring / load-placement siblings (as
   // launch_fast maps them), anything else the ping-pong kernel (8, the default; VIT_GEMM_WGRAD A/B)
+  const int units = a.nwg + b.nwg;
   auto pair_w4 = [&](auto cfg_tag) {
     using C = decltype(cfg_tag);
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)w4::kernel2<C, LAY_CR, LAY_CR, EPI_STORE, float, bf16>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-      attr = true;
-    }
-    hipLaunchKernelGGL((w4::kernel2<C, LAY_CR, LAY_CR, EPI_STORE, float, bf16>), dim3(a.nwg + b.nwg),
-                       dim3(C::THREADS), C::LDS, s, a, b);
+    return launch_1d<w4::kernel2<C, LAY_CR, LAY_CR, EPI_STORE, float, bf16>, C::THREADS, C::LDS>(units, s, a, b);
   };
   switch (pick_variant(LAY_CR, LAY_CR, Na, Ka, M, split, false)) {
-    case 11: pair_w4(w4::Default{}); break;
-    case 12: pair_w4(w4::Cfg<4, 0>{}); break;
-    case 13: pair_w4(w4::Cfg<4, 2>{}); break;
-    case 14: pair_w4(w4::Cfg<3, 1>{}); break;
-    case 15: pair_w4(w4::Cfg<5, 1>{}); break;
-    default: {
-      using C = big::PP<4>;
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void*)big::pp_kernel2<4, LAY_CR, LAY_CR, EPI_STORE, float, bf16>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        attr = true;
-      }
-      hipLaunchKernelGGL((big::pp_kernel2<4, LAY_CR, LAY_CR, EPI_STORE, float, bf16>), dim3(a.nwg + b.nwg),
-                         dim3(C::THREADS), C::LDS, s, a, b);
-    }
+    case 11: return pair_w4(w4::Default{});
+    case 12: return pair_w4(w4::Cfg<4, 0>{});
+    case 13: return pair_w4(w4::Cfg<4, 2>{});
+    case 14: return pair_w4(w4::Cfg<3, 1>{});
+    case 15: return pair_w4(w4::Cfg<5, 1>{});
   }
-  VIT_CHECK_LAUNCH();
-  return 0;
+  using C = big::PP<4>;
+  return launch_1d<big::pp_kernel2<4, LAY_CR, LAY_CR, EPI_STORE, float, bf16>, C::THREADS, C::LDS>(units, s, a, b);
 }
 
 // Column sum (bias grads): out[N] (f32) = sum_i X[i*ld + j]; partial buffer >= S*N floats

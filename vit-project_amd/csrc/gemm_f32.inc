@@ -6,7 +6,7 @@
 //   filled by global_load_lds (16 B/lane), 64 KiB -> 2 workgroups per CU.
 //
 // As in the bf16 kernels the MFMA computes C^T (Q is the A operand) so a lane owns C[i][j..j+3]
-// (i = lane&15, j = 4*(lane>>4)) and the epilogue stores 16 B per lane (epi4).  The reduction
+// (i = lane&15, j = 4*(lane>>4)) and the epilogue stores 16 B per lane (epi_vec, V = 4).  The reduction
 // order inside a 16-deep k block is permuted identically for both operands: lane group
 // g = lane>>4 feeds k = 16h + 4g + t to MFMA t (t = 0..3), so an r-contiguous (RC) operand row
 // gives a lane its four k values with one ds_read_b128; an r-strided (CR) operand takes four
@@ -125,22 +125,7 @@ template <int EPI, typename TO, typename TA>
 __device__ __forceinline__ void epilogue(const Epi& e, const f32x4 (&acc)[AI][AJ], int M, int N, int i0, int j0,
                                          int z, int wave, int lane) {
   const int wi = wave >> 1, wj = wave & 1;
-  f32x4 cs[AJ];
-#pragma unroll
-  for (int b = 0; b < AJ; ++b) cs[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int a = 0; a < AI; ++a) {
-    const int i = i0 + wi * 64 + a * 16 + (lane & 15);
-#pragma unroll
-    for (int b = 0; b < AJ; ++b) {
-      const int j = j0 + wj * 64 + b * 16 + 4 * (lane >> 4);
-      if (i < M && j < N) {
-        const f32x4 v = epi4<EPI, TO, TA>(e, i, j, acc[a][b], z);
-        if (e.csum) cs[b] += v;
-      }
-    }
-    if (e.csum && (a & 3) == 3) csum_flush<AJ>(e, cs, i0 + wi * 64 + (a - 3) * 16, M, N, j0 + wj * 64, lane);
-  }
+  VIT_EPI_FRAG(AI, AJ, i0 + wi * 64, j0 + wj * 64, )
 }
 
 template <int PL, int QL, int EPI, typename TO, typename TA>

@@ -85,7 +85,7 @@ template <int OFF> __device__ __forceinline__ bf16x4 asm_read_tr_off(uint32_t a)
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(OFF));
   return __builtin_bit_cast(bf16x4, v);
 }
-// Half-blocked CR image (gemm_tile, pp_tile; VIT_CR_HB=0 restores the swizzled rows of stage/frag):
+// Half-blocked CR image (gemm_tile, pp_tile; VIT_CR_HB=0 restores the swizzled rows of cr_off / frag_asm):
 // one 1-KiB piece per (16-row k-block, 32-column fragment pair) -- the piece one global_load_lds
 // fills, reading 16 rows x 64 contiguous bytes like the RC staging.  Inside a piece k-row rr owns
 // 64 B; fragment h (0 / 1) of the pair sits in 32-B half h ^ (rr >> 3 & 1), which puts each

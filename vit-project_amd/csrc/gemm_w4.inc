@@ -211,26 +211,11 @@ __device__ __forceinline__ void tile(const bf16* __restrict__ P, int64_t ldp, co
     return;
   }
   // epilogue straight from the fragments: acc[a][b] holds C[i][j..j+3], i = 16a + lane%16, j = 16b + 4*(lane/16)
-  f32x4 cs[8];
-#pragma unroll
-  for (int b = 0; b < 8; ++b) cs[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int a = 0; a < 8; ++a) {
-    // re-define accumulator row a here, so its AGPR -> VGPR copies are made at this row and not all 256
-    // at once after the loop (which spilled)
-    asm volatile("" : "+a"(acc[a][0]), "+a"(acc[a][1]), "+a"(acc[a][2]), "+a"(acc[a][3]), "+a"(acc[a][4]),
-                      "+a"(acc[a][5]), "+a"(acc[a][6]), "+a"(acc[a][7]));
-    const int i = i0 + wi * 128 + a * 16 + (lane & 15);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const int j = j0 + wj * 128 + b * 16 + 4 * (lane >> 4);
-      if (i < M && j < N) {
-        const f32x4 v = epi4<EPI, TO, TA>(e, i, j, acc[a][b], z);
-        if (e.csum) cs[b] += v;
-      }
-    }
-    if (e.csum && (a & 3) == 3) csum_flush<8>(e, cs, i0 + wi * 128 + (a - 3) * 16, M, N, j0 + wj * 128, lane);
-  }
+  // accumulator row a is re-defined in front of its stores, so its AGPR -> VGPR copies are made at this row
+  // and not all 256 at once after the loop (which spilled)
+  VIT_EPI_FRAG(8, 8, i0 + wi * 128, j0 + wj * 128,
+               asm volatile("" : "+a"(acc[a][0]), "+a"(acc[a][1]), "+a"(acc[a][2]), "+a"(acc[a][3]),
+                                 "+a"(acc[a][4]), "+a"(acc[a][5]), "+a"(acc[a][6]), "+a"(acc[a][7])))
 }
 
 template <class C, int PL, int QL, int EPI, typename TO, typename TA>

@@ -1,0 +1,97 @@
+"""Attention past 288 tokens: the streamed MFMA kernels against the generic kernels
+(vit_sdpa_long_config(1) / (0)) at --n tokens, forward and backward (with the qkv-bias gradient, as the
+step runs it), and the resident kernels at --n-resident tokens with the same B and H for the cost of
+streaming per score.  The variants alternate over --rounds rounds; the medians are reported.
+
+    python tools/bench_attn_long.py [--batch 64] [--heads 12] [--n 577] [--n-resident 257] [--reps 20]
+
+Prints one JSON line per (variant, round) and a final summary line.  --no-generic / --no-streamed skip a
+variant (a tree without the streamed kernels can still time its resident kernels with --n 0).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "vit-project_amd"))
+
+import torch  # noqa: E402
+
+from vit_amd import _lib as L  # noqa: E402
+from vit_amd import ops  # noqa: E402
+from tools.bench_kernels import timeit  # noqa: E402
+
+
+def case(B, H, N, dev="cuda"):
+    D = H * 64
+    g = torch.Generator(device=dev).manual_seed(1)
+    qkv = torch.randn(B * N, 3 * D, device=dev, generator=g).to(torch.bfloat16)
+    do = torch.randn(B * N, D, device=dev, generator=g).to(torch.bfloat16)
+    o, lse = ops.sdpa_fwd(qkv, B, H, N)
+    return dict(B=B, H=H, N=N, qkv=qkv, do=do, o=o, lse=lse, dq=torch.empty_like(qkv),
+                dbias=torch.empty(3 * D, device=dev))
+
+
+def time_case(c, reps):
+    B, H, N = c["B"], c["H"], c["N"]
+    tf = timeit(lambda: ops.sdpa_fwd(c["qkv"], B, H, N, o=c["o"], lse=c["lse"]), reps)
+    tb = timeit(lambda: ops.sdpa_bwd(c["qkv"], c["o"], c["do"], c["lse"], B, H, N, dqkv=c["dq"], dbias=c["dbias"]),
+                reps)
+    fl = 4.0 * B * H * N * N * 64  # forward: QK^T and PV; the backward has 5 such products
+    return {"fwd_ms": round(tf * 1e3, 4), "bwd_ms": round(tb * 1e3, 4), "fwd_tflops": round(fl / tf / 1e12, 1),
+            "bwd_tflops": round(2.5 * fl / tb / 1e12, 1),
+            "fwd_us_per_head": round(tf * 1e6 / (B * H), 4), "bwd_us_per_head": round(tb * 1e6 / (B * H), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--heads", type=int, default=12)
+    ap.add_argument("--n", type=int, default=577, help="0: skip the long variants")
+    ap.add_argument("--n-resident", type=int, default=257, help="0: skip the resident kernels")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--reps-generic", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--no-generic", action="store_true")
+    ap.add_argument("--no-streamed", action="store_true")
+    a = ap.parse_args()
+    lib = L.lib()
+    variants = []
+    if a.n:
+        long_case = case(a.batch, a.heads, a.n)
+        if not a.no_streamed:
+            variants.append(("streamed", 1, long_case, a.reps))
+        if not a.no_generic:
+            variants.append(("generic", 0, long_case, a.reps_generic))
+    if a.n_resident:
+        variants.append(("resident", None, case(a.batch, a.heads, a.n_resident), a.reps))
+    res = {name: [] for name, *_ in variants}
+    try:
+        for rnd in range(a.rounds):
+            for name, mode, c, reps in variants:
+                if mode is not None:
+                    lib.vit_sdpa_long_config(mode)
+                r = time_case(c, reps)
+                res[name].append(r)
+                print(json.dumps({"variant": name, "round": rnd, "N": c["N"], "batch": a.batch, "heads": a.heads, **r}),
+                      flush=True)
+    finally:
+        if a.n:
+            lib.vit_sdpa_long_config(-1)
+    med = {name: {k: statistics.median(r[k] for r in rs) for k in ("fwd_ms", "bwd_ms")} for name, rs in res.items()}
+    out = {"summary": True, "batch": a.batch, "heads": a.heads, "n": a.n, "n_resident": a.n_resident, "median_ms": med}
+    if "streamed" in med and "generic" in med:
+        out["generic_over_streamed"] = {k: round(med["generic"][k] / med["streamed"][k], 2) for k in ("fwd_ms", "bwd_ms")}
+    if "streamed" in med and "resident" in med:
+        # same B and H, so the per-(b, h) time ratio is the ratio of the call times
+        out["streamed_over_resident"] = {k: round(med["streamed"][k] / med["resident"][k], 2)
+                                         for k in ("fwd_ms", "bwd_ms")}
+        out["score_work_ratio"] = round((a.n / a.n_resident) ** 2, 2)
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

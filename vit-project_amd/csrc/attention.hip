@@ -1,14 +1,17 @@
 // Scaled-dot-product attention for timm Attention: per (batch, head)
-// softmax(q k^T * hd^-0.5) v, N <= 288 tokens (197 for ViT-B/16, 257 for CLIP
-// ViT-L/14, 77 for the CLIP text tower), head_dim 64; unmasked or causal (the
-// text tower's build_attention_mask: key > query gets -inf).
+// softmax(q k^T * hd^-0.5) v, head_dim 64, any token count; unmasked or causal (the
+// text tower's build_attention_mask: key > query gets -inf).  Up to 288 tokens (197
+// for ViT-B/16, 257 for CLIP ViT-L/14, 77 for the CLIP text tower) the resident
+// kernels below run; past 288 (384-pixel fine-tuning: 577, patch 8: 785) the
+// streamed bf16 kernels (attn_*_stream), and for f32, causal or misaligned operands
+// the generic scalar kernels -- a causal and an f32 streamed form are out of scope.
 //
 // q/k/v are read in place from the fused qkv GEMM output [B*N, 3*D] (row stride
 // ld_qkv), the output o is written as [B*N, D] (the proj GEMM operand), and the
 // backward writes dq/dk/dv into a [B*N, 3*D] buffer laid out like qkv so the
 // qkv dgrad/wgrad GEMMs consume it directly.
 //
-// bf16 path: one workgroup (4 waves) per (b, h); the whole K and V of the head
+// resident bf16 path: one workgroup (4 waves) per (b, h); the whole K and V of the head
 // live in LDS (<= 2 x 36 KiB); S^T = K Q^T with v_mfma_f32_16x16x32_bf16 so each
 // lane owns one query column and the softmax row-max/row-sum are in-lane plus two
 // cross-lane shuffles; P stays in registers and feeds the PV MFMA as its
@@ -1424,6 +1427,346 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const T* __restrict__ o
 }
 
 // ---------------------------------------------------------------------------
+// Streamed bf16 attention: no compile-time bound on N (the path for N > 288).  The resident kernels'
+// operand algebra -- S^T = K Q^T with a lane per query column, P / dS in registers as the B operand,
+// the swizzled 128-B row image read by rowf / trf -- with the streamed operand passing through a
+// double-buffered LDS ring of 64-row chunks instead of living there whole.
+//   grid (B*H, ceil(N / 128)): a workgroup owns 128 queries (keys in the dkv kernel), a wave 16 of them,
+//   held in registers for the whole kernel.  Per chunk: the next chunk's global loads are issued first
+//   (one 16-B piece of each of the two images per thread), the MFMA work on the current chunk runs
+//   under their latency, then the pieces go to the other buffer; one barrier per chunk.
+//   fwd : K, V chunks; online softmax (running max m, per-lane partial sum l, o rescaled per chunk).
+//   dq  : K, V chunks; writes delta and dq.          dkv : Q, dO chunks + lse / delta; writes dk, dv.
+// Rows past N: loads are clamped to row N - 1 and the piece is zeroed in registers (at_load's rule);
+// a key past N gets score -inf (p = 0 exactly), a query past N gets lse = +inf (p = 0 exactly).
+// Every output element has one owner and every sum a fixed order: runs are bitwise repeatable.
+// LDS: 2 x 16 KiB (+ 1 KiB lse / delta in dkv); 128-VGPR budget, so two workgroups share a CU.
+// Out of scope: a causal and an f32 streamed form (those take the generic kernels past 288 tokens).
+// ---------------------------------------------------------------------------
+constexpr int ST_CH = 64;             // rows per streamed chunk
+constexpr int ST_QB = AT_WAVES * 16;  // queries (keys) per workgroup
+constexpr int ST_IMG = ST_CH * 128;   // bytes per chunk image
+static_assert(ST_CH * 8 == AT_THREADS, "one 16-B piece of a chunk image per thread");
+
+struct StPiece { bf16x8 a, b; };
+// this thread's piece of rows [j0, j0 + 64) of two head slices (clamped to row N - 1)
+__device__ __forceinline__ StPiece st_fetch(const bf16* sa, int64_t lda, const bf16* sb, int64_t ldb, int j0, int N) {
+  const int row = min(j0 + (int)(threadIdx.x >> 3), N - 1), c = threadIdx.x & 7;
+  StPiece p;
+  p.a = *reinterpret_cast<const bf16x8*>(sa + (int64_t)row * lda + c * 8);
+  p.b = *reinterpret_cast<const bf16x8*>(sb + (int64_t)row * ldb + c * 8);
+  return p;
+}
+__device__ __forceinline__ void st_commit(char* buf, StPiece p, int j0, int N) {
+  const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
+  if (j0 + r >= N) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t) { p.a[t] = (bf16)0.f; p.b[t] = (bf16)0.f; }
+  }
+  *reinterpret_cast<bf16x8*>(buf + at_off(r, c)) = p.a;
+  *reinterpret_cast<bf16x8*>(buf + ST_IMG + at_off(r, c)) = p.b;
+}
+
+__global__ __launch_bounds__(AT_THREADS, 2) void attn_fwd_stream(const bf16* __restrict__ qkv, int64_t ld_qkv, int D, int H,
+                                                                int N, float scale, bf16* __restrict__ o, int64_t ld_o,
+                                                                float* __restrict__ lse) {
+  __shared__ __attribute__((aligned(16))) char smem[2][2 * ST_IMG];  // [buffer][K | V]
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const bf16* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const int q = blockIdx.y * ST_QB + wave * 16 + (lane & 15);
+  bf16x8 qf[2];
+  {
+    const int qq = min(q, N - 1);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) qf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)qq * ld_qkv + kk * 32 + g * 8);
+  }
+  const AtOffsets off(lane);
+  const int nc = (N + ST_CH - 1) / ST_CH;
+  StPiece pc = st_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, 0, N);
+  st_commit(smem[0], pc, 0, N);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  float m = -INFINITY, l = 0.f;  // running max (raw scores, all 4 lanes of a query agree); this lane's part of the sum
+  f32x4 oacc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const char* Kc = smem[c & 1];
+    const char* Vc = Kc + ST_IMG;
+    const int j0 = c * ST_CH;
+    const bool more = c + 1 < nc;
+    if (more) pc = st_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0 + ST_CH, N);
+    f32x4 s[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) s[kt] = mfma16(rowf(Kc, kt * 16, off.row[kk]), qf[kk], s[kt]);
+    }
+    if (j0 + ST_CH > N) {  // wave-uniform: only the last chunk holds keys >= N
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (j0 + kt * 16 + 4 * g + r >= N) s[kt][r] = -INFINITY;
+    }
+    float mt = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kt][r]);
+    mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
+    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+    const float mn = fmaxf(m, mt);                // finite from the first chunk on: key 0 is never masked
+    const float alpha = fexp2((m - mn) * c2);     // first chunk: m = -inf -> 0
+    m = mn;
+    const float mc = m * c2;
+    float lt = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { const float p = fexp2(fmaf(s[kt][r], c2, -mc)); s[kt][r] = p; lt += p; }
+    l = fmaf(l, alpha, lt);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) oacc[dt] *= alpha;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const bf16x8 pf = pack8(s[2 * ks], s[2 * ks + 1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) oacc[dt] = mfma16(trf(Vc, ks * 32, off.tr[dt]), pf, oacc[dt]);
+    }
+    if (more) st_commit(smem[(c + 1) & 1], pc, j0 + ST_CH, N);
+    __syncthreads();
+  }
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (q < N) {
+    const float inv = 1.0f / l;
+    bf16* orow = o + ((int64_t)b * N + q) * ld_o + h * 64;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      bf16x4 ov = {(bf16)(oacc[dt][0] * inv), (bf16)(oacc[dt][1] * inv), (bf16)(oacc[dt][2] * inv),
+                   (bf16)(oacc[dt][3] * inv)};
+      *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * g) = ov;
+    }
+    if (g == 0) lse[(int64_t)bh * N + q] = (m * c2 + __log2f(l)) * LN2;
+  }
+}
+
+// query-parallel half of the streamed backward: delta = rowsum(dO * O) and dQ (attn_bwd_dq's loop per chunk)
+__global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dq_stream(const bf16* __restrict__ qkv, int64_t ld_qkv, int D, int H,
+                                                                   int N, float scale, const bf16* __restrict__ o,
+                                                                   int64_t ld_o, const bf16* __restrict__ dout,
+                                                                   int64_t ld_do, const float* __restrict__ lse,
+                                                                   float* __restrict__ delta_out, bf16* __restrict__ dqkv,
+                                                                   int64_t ld_dqkv) {
+  __shared__ __attribute__((aligned(16))) char smem[2][2 * ST_IMG];  // [buffer][K | V]
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const bf16* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const int q = blockIdx.y * ST_QB + wave * 16 + (lane & 15);
+  const int qc = min(q, N - 1);
+  bf16x8 qf[2], of[2];
+  float dl = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    qf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)qc * ld_qkv + kk * 32 + g * 8);
+    of[kk] = *reinterpret_cast<const bf16x8*>(dout + ((int64_t)b * N + qc) * ld_do + h * 64 + kk * 32 + g * 8);
+    const bf16x8 ov = *reinterpret_cast<const bf16x8*>(o + ((int64_t)b * N + qc) * ld_o + h * 64 + kk * 32 + g * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dl = fmaf((float)of[kk][e], (float)ov[e], dl);
+  }
+  dl += __shfl_xor(dl, 16, 64);
+  dl += __shfl_xor(dl, 32, 64);
+  const float l2 = lse[(int64_t)bh * N + qc] * LOG2E;
+  if (g == 0 && q < N) delta_out[(int64_t)bh * N + q] = dl;
+  const AtOffsets off(lane);
+  const int nc = (N + ST_CH - 1) / ST_CH;
+  StPiece pc = st_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, 0, N);
+  st_commit(smem[0], pc, 0, N);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  f32x4 dq[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const char* Kc = smem[c & 1];
+    const char* Vc = Kc + ST_IMG;
+    const int j0 = c * ST_CH;
+    const bool more = c + 1 < nc;
+    if (more) pc = st_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0 + ST_CH, N);
+    const bool edge = j0 + ST_CH > N;  // wave-uniform: only the last chunk holds keys >= N
+#pragma unroll
+    for (int kp = 0; kp < 2; ++kp) {
+      f32x4 ds[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int kt = 2 * kp + u;
+        f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          sacc = mfma16(rowf(Kc, kt * 16, off.row[kk]), qf[kk], sacc);
+          dpacc = mfma16(rowf(Vc, kt * 16, off.row[kk]), of[kk], dpacc);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float pv = fexp2(fmaf(sacc[r], c2, -l2));
+          if (edge && j0 + kt * 16 + 4 * g + r >= N) pv = 0.f;
+          ds[u][r] = pv * (dpacc[r] - dl);
+        }
+      }
+      const bf16x8 dsf = pack8(ds[0], ds[1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma16(trf(Kc, kp * 32, off.tr[dt]), dsf, dq[dt]);
+    }
+    if (more) st_commit(smem[(c + 1) & 1], pc, j0 + ST_CH, N);
+    __syncthreads();
+  }
+  if (q < N) {
+    bf16* row = dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      bf16x4 qv = {(bf16)(dq[dt][0] * scale), (bf16)(dq[dt][1] * scale), (bf16)(dq[dt][2] * scale),
+                   (bf16)(dq[dt][3] * scale)};
+      *reinterpret_cast<bf16x4*>(row + dt * 16 + 4 * g) = qv;
+    }
+  }
+}
+
+// key-parallel half: dK, dV of the workgroup's 128 keys (K, V rows in registers) over streamed Q / dO chunks
+__global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dkv_stream(const bf16* __restrict__ qkv, int64_t ld_qkv, int D,
+                                                                    int H, int N, float scale,
+                                                                    const bf16* __restrict__ dout, int64_t ld_do,
+                                                                    const float* __restrict__ lse,
+                                                                    const float* __restrict__ delta_in,
+                                                                    bf16* __restrict__ dqkv, int64_t ld_dqkv) {
+  constexpr int BUF = 2 * ST_IMG + 2 * ST_CH * 4;  // Q | dO | lse * log2(e) | delta
+  __shared__ __attribute__((aligned(16))) char smem[2][BUF];
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
+  const bf16* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const bf16* dob = dout + (int64_t)b * N * ld_do + h * 64;
+  const int key = blockIdx.y * ST_QB + wave * 16 + (lane & 15);
+  const bool kvalid = key < N;
+  const int kc = min(key, N - 1);
+  bf16x8 kf[2], vf[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    kf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)kc * ld_qkv + D + kk * 32 + g * 8);
+    vf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)kc * ld_qkv + 2 * D + kk * 32 + g * 8);
+  }
+  // row constants of a chunk: threads 0..63 carry lse * log2(e) (+inf past N: p = 0), 64..127 delta (0 past N)
+  auto stat_fetch = [&](int j0) -> float {
+    if (tid >= 2 * ST_CH) return 0.f;
+    const int i = j0 + (tid & (ST_CH - 1));
+    if (tid < ST_CH) return i < N ? lse[(int64_t)bh * N + i] * LOG2E : INFINITY;
+    return i < N ? delta_in[(int64_t)bh * N + i] : 0.f;
+  };
+  auto stat_commit = [&](char* buf, float v) {
+    if (tid < 2 * ST_CH) reinterpret_cast<float*>(buf + 2 * ST_IMG)[tid] = v;
+  };
+  const AtOffsets off(lane);
+  const int nc = (N + ST_CH - 1) / ST_CH;
+  StPiece pc = st_fetch(base, ld_qkv, dob, ld_do, 0, N);
+  float sv = stat_fetch(0);
+  st_commit(smem[0], pc, 0, N);
+  stat_commit(smem[0], sv);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  f32x4 dv[4], dk[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) { dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[dt] = dv[dt]; }
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const char* Qc = smem[c & 1];
+    const char* Oc = Qc + ST_IMG;  // dO
+    const float* lse2 = reinterpret_cast<const float*>(Qc + 2 * ST_IMG);
+    const float* delta = lse2 + ST_CH;
+    const int j0 = c * ST_CH;
+    const bool more = c + 1 < nc;
+    if (more) {
+      pc = st_fetch(base, ld_qkv, dob, ld_do, j0 + ST_CH, N);
+      sv = stat_fetch(j0 + ST_CH);
+    }
+#pragma unroll 1
+    for (int qp = 0; qp < 2; ++qp) {
+      f32x4 p[2], ds[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int qt = 2 * qp + u;
+        f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          sacc = mfma16(rowf(Qc, qt * 16, off.row[kk]), kf[kk], sacc);
+          dpacc = mfma16(rowf(Oc, qt * 16, off.row[kk]), vf[kk], dpacc);
+        }
+        const f32x4 l2 = *reinterpret_cast<const f32x4*>(lse2 + qt * 16 + 4 * g);
+        const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + qt * 16 + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pv = kvalid ? fexp2(fmaf(sacc[r], c2, -l2[r])) : 0.f;
+          p[u][r] = pv;
+          ds[u][r] = pv * (dpacc[r] - dl[r]);
+        }
+      }
+      const bf16x8 pf = pack8(p[0], p[1]), dsf = pack8(ds[0], ds[1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        dv[dt] = mfma16(trf(Oc, qp * 32, off.tr[dt]), pf, dv[dt]);
+        dk[dt] = mfma16(trf(Qc, qp * 32, off.tr[dt]), dsf, dk[dt]);
+      }
+    }
+    if (more) {
+      st_commit(smem[(c + 1) & 1], pc, j0 + ST_CH, N);
+      stat_commit(smem[(c + 1) & 1], sv);
+    }
+    __syncthreads();
+  }
+  if (kvalid) {
+    bf16* row = dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      bf16x4 kv = {(bf16)(dk[dt][0] * scale), (bf16)(dk[dt][1] * scale), (bf16)(dk[dt][2] * scale),
+                   (bf16)(dk[dt][3] * scale)};
+      bf16x4 vv = {(bf16)dv[dt][0], (bf16)dv[dt][1], (bf16)dv[dt][2], (bf16)dv[dt][3]};
+      *reinterpret_cast<bf16x4*>(row + D + dt * 16 + 4 * g) = kv;
+      *reinterpret_cast<bf16x4*>(row + 2 * D + dt * 16 + 4 * g) = vv;
+    }
+  }
+}
+
+// qkv-bias gradient partials past 288 tokens: part[b][c] = sum over the image's N rows of dqkv[.][c], one
+// thread per column, rows in a fixed order (8 interleaved chains) -- the [B][3D] layout the resident
+// kernels leave.  It reads dqkv once, a few percent of the bytes the two backward kernels move.
+__global__ __launch_bounds__(256) void attn_bias_image(const bf16* __restrict__ dqkv, int64_t ld, int N, int C,
+                                                       float* __restrict__ part) {
+  const int b = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= C) return;
+  const bf16* p = dqkv + (int64_t)b * N * ld + c;
+  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int n = 0;
+  for (; n + 8 <= N; n += 8)
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a[u] += (float)p[(int64_t)(n + u) * ld];
+  for (; n < N; ++n) a[0] += (float)p[(int64_t)n * ld];
+  part[(int64_t)b * C + c] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+}
+
+// Past 288 tokens (vit_sdpa_long_config / VIT_ATTN_LONG): 1 = the streamed MFMA kernels (default),
+// 0 = the generic kernels.  g_long_count: vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed kernels.
+static int g_long_mode = -1;
+static int g_long_count = 0;
+static bool attn_long_stream() {
+  if (g_long_mode >= 0) return g_long_mode != 0;
+  static const int v = [] { const char* e = getenv("VIT_ATTN_LONG"); return e && *e == '0' ? 0 : 1; }();
+  return v != 0;
+}
+constexpr int AT_RESIDENT_MAX = 288;  // the resident kernels' token limit (NT_CASES)
+
+// ---------------------------------------------------------------------------
 template <int NT>
 static int fwd_mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal, void* o,
                     int64_t ld_o, float* lse, hipStream_t s) {
@@ -1549,6 +1892,21 @@ int vit_sdpa_bwd_variant(int v) {
   return 0;
 }
 
+// Kernel choice past 288 tokens (bf16, non-causal, aligned): -1 = from the environment (VIT_ATTN_LONG=0|1,
+// default 1), 0 = the generic kernels, 1 = the streamed MFMA kernels.  Returns the previous mode.
+int vit_sdpa_long_config(int mode) {
+  const int prev = g_long_mode;
+  g_long_mode = mode < 0 ? -1 : (mode != 0);
+  return prev;
+}
+// Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed kernels (one per call: the
+// backward's two kernels count once); reset != 0 zeroes it after reading.
+int vit_sdpa_long_count(int reset) {
+  const int c = g_long_count;
+  if (reset) g_long_count = 0;
+  return c;
+}
+
 // F.scaled_dot_product_attention(q, k, v) (no dropout) for head_dim 64; causal = 1
 // masks key > query (OpenAI CLIP text tower attn_mask, additive -inf above the diagonal).
 // qkv: [B*N, ld_qkv] with q at column h*64, k at D + h*64, v at 2D + h*64.
@@ -1556,9 +1914,17 @@ int vit_sdpa_bwd_variant(int v) {
 int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o,
                  int64_t ld_o, float* lse, float scale, int causal, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (head_dim != 64 || N <= 0 || N > 288) return (int)hipErrorInvalidValue;
+  if (head_dim != 64 || N <= 0) return (int)hipErrorInvalidValue;
   const int D = H * 64;
-  if (dtype == VIT_BF16 && (ld_qkv % 8 == 0) && (ld_o % 4 == 0)) {
+  const bool resident = N <= AT_RESIDENT_MAX;
+  if (!resident && dtype == VIT_BF16 && !causal && (ld_qkv % 8 == 0) && (ld_o % 4 == 0) && attn_long_stream()) {
+    hipLaunchKernelGGL(attn_fwd_stream, dim3(B * H, (N + ST_QB - 1) / ST_QB), dim3(AT_THREADS), 0, s,
+                       (const bf16*)qkv, ld_qkv, D, H, N, scale, (bf16*)o, ld_o, lse);
+    VIT_CHECK_LAUNCH();
+    ++g_long_count;
+    return 0;
+  }
+  if (resident && dtype == VIT_BF16 && (ld_qkv % 8 == 0) && (ld_o % 4 == 0)) {
     int nt = (N + 15) / 16;
     switch (nt) {
 #define CASE(n) case n: return fwd_mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
@@ -1566,7 +1932,7 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
 #undef CASE
     }
   }
-  if (dtype == VIT_F32 && (ld_qkv % 4 == 0) && (ld_o % 4 == 0) && !attn_f32_generic()) {
+  if (resident && dtype == VIT_F32 && (ld_qkv % 4 == 0) && (ld_o % 4 == 0) && !attn_f32_generic()) {
     int nt = (N + 15) / 16;
     switch (nt) {
 #define CASE(n) case n: return fwd_f32mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
@@ -1574,6 +1940,7 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
 #undef CASE
     }
   }
+  if ((int64_t)B * H > 65535) return (int)hipErrorInvalidValue;  // the generic kernels put b*h on grid.y
   dim3 grid((N + 63) / 64, B * H);
   if (dtype == VIT_BF16)
     hipLaunchKernelGGL(attn_fwd_generic<bf16>, grid, dim3(256), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale, (bf16*)o, ld_o, lse, causal);
@@ -1623,16 +1990,49 @@ int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
                  float* delta_ws, float scale, int causal, float* dbias, float* partial, int64_t partial_floats,
                  void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (head_dim != 64 || N <= 0 || N > 288) return (int)hipErrorInvalidValue;
+  if (head_dim != 64 || N <= 0) return (int)hipErrorInvalidValue;
   const int D = H * 64;
+  const bool resident = N <= AT_RESIDENT_MAX;
   if (!delta_ws) return (int)hipErrorInvalidValue;
   // dbias == null with a partial buffer: leave the per-image [B][3D] partials for the caller (bf16 path)
   const bool part_only = !dbias && partial;
   if ((dbias || part_only) && (partial == nullptr || partial_floats < vit_sdpa_bwd_partial_floats(B, N, D)))
     return (int)hipErrorInvalidValue;
   const bool mfma_ok = dtype == VIT_BF16 && (ld_qkv % 8 == 0) && (ld_do % 8 == 0) && (ld_dqkv % 4 == 0) && (ld_o % 4 == 0);
+  if (!resident && dtype == VIT_BF16) {
+    // streamed MFMA kernels, or the generic ones (causal, misaligned, vit_sdpa_long_config(0)); the bias
+    // partials come from a per-image column-sum pass over dqkv either way
+    if (mfma_ok && !causal && attn_long_stream()) {
+      const dim3 grid(B * H, (N + ST_QB - 1) / ST_QB);
+      hipLaunchKernelGGL(attn_bwd_dq_stream, grid, dim3(AT_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
+                         (const bf16*)o, ld_o, (const bf16*)dout, ld_do, lse, delta_ws, (bf16*)dqkv, ld_dqkv);
+      VIT_CHECK_LAUNCH();
+      hipLaunchKernelGGL(attn_bwd_dkv_stream, grid, dim3(AT_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
+                         (const bf16*)dout, ld_do, lse, (const float*)delta_ws, (bf16*)dqkv, ld_dqkv);
+      VIT_CHECK_LAUNCH();
+      ++g_long_count;
+    } else {
+      if ((int64_t)B * H > 65535) return (int)hipErrorInvalidValue;  // the generic kernels put b*h on grid.y
+      const dim3 grid((N + 63) / 64, B * H);
+      hipLaunchKernelGGL(attn_bwd_dq_generic<bf16>, grid, dim3(256), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
+                         (const bf16*)o, ld_o, (const bf16*)dout, ld_do, lse, delta_ws, (bf16*)dqkv, ld_dqkv, causal);
+      VIT_CHECK_LAUNCH();
+      hipLaunchKernelGGL(attn_bwd_dkv_generic<bf16>, grid, dim3(256), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
+                         (const bf16*)dout, ld_do, lse, delta_ws, (bf16*)dqkv, ld_dqkv, causal);
+      VIT_CHECK_LAUNCH();
+    }
+    if (!dbias && !part_only) return 0;
+    hipLaunchKernelGGL(attn_bias_image, dim3(B, (3 * D + 255) / 256), dim3(256), 0, s, (const bf16*)dqkv, ld_dqkv, N,
+                       3 * D, partial);
+    VIT_CHECK_LAUNCH();
+    if (dbias) {
+      launch_colreduce(partial, B, 3 * D, dbias, 0, s, partial + (int64_t)B * 3 * D);
+      VIT_CHECK_LAUNCH();
+    }
+    return 0;
+  }
   if (part_only && !mfma_ok) return (int)hipErrorInvalidValue;
-  if (mfma_ok) {
+  if (resident && mfma_ok) {
     int nt = (N + 15) / 16;
     int rc = (int)hipErrorInvalidValue;
     switch (nt) {
@@ -1645,7 +2045,7 @@ int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
     VIT_CHECK_LAUNCH();
     return 0;
   }
-  if (dtype == VIT_F32 && (ld_qkv % 4 == 0) && (ld_do % 4 == 0) && (ld_dqkv % 4 == 0) && (ld_o % 4 == 0) &&
+  if (resident && dtype == VIT_F32 && (ld_qkv % 4 == 0) && (ld_do % 4 == 0) && (ld_dqkv % 4 == 0) && (ld_o % 4 == 0) &&
       !attn_f32_generic()) {
     int nt = (N + 15) / 16, rc = (int)hipErrorInvalidValue;
     switch (nt) {
@@ -1657,6 +2057,7 @@ int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
     if (dbias) return vit_colsum(dtype, B * N, 3 * D, dqkv, ld_dqkv, dbias, partial, partial_floats, 0, stream);
     return 0;
   }
+  if ((int64_t)B * H > 65535) return (int)hipErrorInvalidValue;  // the generic kernels put b*h on grid.y
   dim3 grid((N + 63) / 64, B * H);
 #define GEN(T)                                                                                               \
   hipLaunchKernelGGL(attn_bwd_dq_generic<T>, grid, dim3(256), 0, s, (const T*)qkv, ld_qkv, D, H, N, scale,    \

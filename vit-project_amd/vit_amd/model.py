@@ -297,6 +297,8 @@ def _block_chain(x, params, cfg, fwd_only):
     Wqkv, Wproj, W1, W2 = _wt(qkvw, T), _wt(projw, T), _wt(fc1w, T), _wt(fc2w, T)
     causal = bool(cfg.get("causal", False))
     attn_fp8 = bool(cfg.get("attn_fp8", False))  # forward-only blocks (frozen prefix, no-grad passes)
+    if attn_fp8:
+        ops.check_fp8_tokens(N)  # before anything is queued on the side stream
 
     # fused residual adds (bf16 ViT, VisionTransformer._tokens): proj / fc2 store their bf16 output
     # (bias included) and the add into the f32 stream runs inside the next LayerNorm -- norm2 here,
@@ -821,6 +823,10 @@ _MODEL_CFGS = {
     "vit_base_patch16_224": dict(img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12),
     "vit_large_patch16_224": dict(img_size=224, patch_size=16, embed_dim=1024, depth=24, num_heads=16),
     "vit_small_patch16_224": dict(img_size=224, patch_size=16, embed_dim=384, depth=12, num_heads=6),
+    # past 288 tokens (577 / 785): attention runs the streamed kernels
+    "vit_base_patch16_384": dict(img_size=384, patch_size=16, embed_dim=768, depth=12, num_heads=12),
+    "vit_large_patch16_384": dict(img_size=384, patch_size=16, embed_dim=1024, depth=24, num_heads=16),
+    "vit_base_patch8_224": dict(img_size=224, patch_size=8, embed_dim=768, depth=12, num_heads=12),
 }
 
 

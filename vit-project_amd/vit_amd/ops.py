@@ -392,9 +392,22 @@ def layer_norm_bwd(x, ldx, dy, w, mean, rstd, dx, lddx, rows, dres=None, ldres=0
 # attention
 # ----------------------------------------------------------------------------
 
+FP8_ATTN_MAX_TOKENS = 320  # vit_sdpa_fwd_fp8 holds the head's quantised K and V in LDS
+
+
+def check_fp8_tokens(N):
+    """The fp8 attention kernel has no streamed form: refuse, never fall back to another precision."""
+    if N > FP8_ATTN_MAX_TOKENS:
+        raise ValueError(f"fp8 attention (vit_sdpa_fwd_fp8) supports at most {FP8_ATTN_MAX_TOKENS} tokens, got "
+                         f"{N}: switch it off (set_attention_fp8(False)) for this model")
+
+
 def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=False):
-    """softmax(q k^T * scale) v per (b, h) from the fused qkv [B*N, 3D]; fp8: the block-scaled e4m3
-    MFMA kernel (forward only: its lse is not the bf16 backward's)."""
+    """softmax(q k^T * scale) v per (b, h) from the fused qkv [B*N, 3D], any N (past 288 tokens the
+    streamed bf16 kernels, or the generic ones for f32 / causal); fp8: the block-scaled e4m3
+    MFMA kernel (forward only: its lse is not the bf16 backward's; N <= 320)."""
+    if fp8:
+        check_fp8_tokens(N)
     D = H * 64
     if o is None:
         o = torch.empty(B * N, D, dtype=qkv2d.dtype, device=qkv2d.device)

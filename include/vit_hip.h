@@ -213,9 +213,10 @@ int vit_layer_norm_bwd_blocks(int rows); /* partial rows: the [nblk][D] partial 
 /* F.scaled_dot_product_attention(q,k,v) (timm Attention, head_dim 64, any N) reading q/k/v in
  * place from the qkv GEMM output; lse [B*H*N] f32.  causal = 1 masks key > query: the CLIP text
  * tower's nn.MultiheadAttention attn_mask (NEWP:298 through the CLIP-HBA fork, external).
- * N <= 288: the kernels that hold a head's K and V in LDS.  N > 288: bf16, non-causal, ld_qkv % 8 == 0
- * and ld_o % 4 == 0 take the streamed MFMA kernels; f32, causal or misaligned operands the generic
- * scalar kernels (slow; B*H <= 65535). */
+ * N <= 288: the kernels that hold a head's K and V in LDS.  N > 288, non-causal: bf16 with
+ * ld_qkv % 8 == 0 and ld_o % 4 == 0, and f32 with every row stride % 4 == 0, take the streamed MFMA
+ * kernels of their dtype; causal or misaligned operands the generic scalar kernels (slow;
+ * B*H <= 65535). */
 int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o,
                  int64_t ld_o, float* lse, float scale, int causal, void* stream);
 /* fp8 scaled-dot-product attention forward (BASELINE configs[4]: the sweep's frozen CLIP tower blocks
@@ -230,19 +231,23 @@ int vit_sdpa_fwd_fp8(int dtype, int B, int H, int N, int head_dim, const void* q
  * partial >= vit_sdpa_bwd_partial_floats(B, N, H*64).  dbias == NULL with partial != NULL (bf16
  * only): the kernels leave the per-image [B][3*H*64] partial sums in `partial` for the caller to
  * reduce (vit_colreduce_batch).  N > 288 (bf16): the partials come from a per-image column-sum pass
- * over dqkv after the two kernels; same layout, fixed summation order. */
+ * over dqkv after the two kernels; same layout, fixed summation order.  N > 288 (f32, non-causal,
+ * every row stride % 4 == 0): the streamed f32 MFMA kernels, dbias by a column sum over dqkv. */
 int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, const void* o,
                  int64_t ld_o, const void* dout, int64_t ld_do, const float* lse, void* dqkv, int64_t ld_dqkv,
                  float* delta_ws, float scale, int causal, float* dbias, float* partial, int64_t partial_floats,
                  void* stream);
 int vit_sdpa_bwd_partial_floats(int B, int N, int D);
 /* Kernel choice of vit_sdpa_fwd / vit_sdpa_bwd past 288 tokens where the streamed MFMA kernels apply:
- * -1 = from the environment (VIT_ATTN_LONG=0|1, default 1), 0 = the generic kernels, 1 = streamed.
+ * -1 = from the environment (VIT_ATTN_LONG=0|1, default 1), 0 = the generic kernels, 1 = streamed
+ * (bf16 and f32 alike; VIT_ATTN_F32_GENERIC=1 also keeps f32 on the generic kernels).
  * Returns the previous mode. */
 int vit_sdpa_long_config(int mode);
-/* Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed kernels, so a test can
- * see which kernel ran (reset != 0 zeroes it after reading). */
+/* Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed bf16 kernels, so a test
+ * can see which kernel ran (reset != 0 zeroes it after reading). */
 int vit_sdpa_long_count(int reset);
+/* The same count for the streamed f32 kernels (additive to ABI 10). */
+int vit_sdpa_long_f32_count(int reset);
 /* Tuning hook: the bf16 backward form for N <= 224 (-1 = from VIT_ATTN_BWD_SPLIT, 1 = whole-head fused
  * (the default), 2 = two kernels; 0, round 4's banded form, was removed in ABI 8: hipErrorInvalidValue).
  * The two forms agree to bf16 rounding (some f32 sums are ordered differently). */

@@ -1,9 +1,11 @@
 """Attention past 288 tokens: the streamed MFMA kernels against the generic kernels
-(vit_sdpa_long_config(1) / (0)) at --n tokens, forward and backward (with the qkv-bias gradient, as the
-step runs it), and the resident kernels at --n-resident tokens with the same B and H for the cost of
-streaming per score.  The variants alternate over --rounds rounds; the medians are reported.
+(vit_sdpa_long_config(1) / (0)) at --n tokens, in bf16 or f32 (--dtype), forward and backward (with the
+qkv-bias gradient, as the step runs it), and the resident kernels at --n-resident tokens with the same B and H
+for the cost of streaming per score.  The variants alternate over --rounds rounds; the medians and each
+variant's round-to-round spread are reported.
 
-    python tools/bench_attn_long.py [--batch 64] [--heads 12] [--n 577] [--n-resident 257] [--reps 20]
+    python tools/bench_attn_long.py [--dtype bf16|f32] [--batch 64] [--heads 12] [--n 577] [--n-resident 257]
+                                    [--reps 20]
 
 Prints one JSON line per (variant, round) and a final summary line.  --no-generic / --no-streamed skip a
 variant (a tree without the streamed kernels can still time its resident kernels with --n 0).
@@ -25,11 +27,11 @@ from vit_amd import ops  # noqa: E402
 from tools.bench_kernels import timeit  # noqa: E402
 
 
-def case(B, H, N, dev="cuda"):
+def case(B, H, N, dtype=torch.bfloat16, dev="cuda"):
     D = H * 64
     g = torch.Generator(device=dev).manual_seed(1)
-    qkv = torch.randn(B * N, 3 * D, device=dev, generator=g).to(torch.bfloat16)
-    do = torch.randn(B * N, D, device=dev, generator=g).to(torch.bfloat16)
+    qkv = torch.randn(B * N, 3 * D, device=dev, generator=g).to(dtype)
+    do = torch.randn(B * N, D, device=dev, generator=g).to(dtype)
     o, lse = ops.sdpa_fwd(qkv, B, H, N)
     return dict(B=B, H=H, N=N, qkv=qkv, do=do, o=o, lse=lse, dq=torch.empty_like(qkv),
                 dbias=torch.empty(3 * D, device=dev))
@@ -48,6 +50,7 @@ def time_case(c, reps):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--n", type=int, default=577, help="0: skip the long variants")
@@ -59,15 +62,16 @@ def main():
     ap.add_argument("--no-streamed", action="store_true")
     a = ap.parse_args()
     lib = L.lib()
+    dtype = torch.float32 if a.dtype == "f32" else torch.bfloat16
     variants = []
     if a.n:
-        long_case = case(a.batch, a.heads, a.n)
+        long_case = case(a.batch, a.heads, a.n, dtype)
         if not a.no_streamed:
             variants.append(("streamed", 1, long_case, a.reps))
         if not a.no_generic:
             variants.append(("generic", 0, long_case, a.reps_generic))
     if a.n_resident:
-        variants.append(("resident", None, case(a.batch, a.heads, a.n_resident), a.reps))
+        variants.append(("resident", None, case(a.batch, a.heads, a.n_resident, dtype), a.reps))
     res = {name: [] for name, *_ in variants}
     try:
         for rnd in range(a.rounds):
@@ -76,13 +80,17 @@ def main():
                     lib.vit_sdpa_long_config(mode)
                 r = time_case(c, reps)
                 res[name].append(r)
-                print(json.dumps({"variant": name, "round": rnd, "N": c["N"], "batch": a.batch, "heads": a.heads, **r}),
-                      flush=True)
+                print(json.dumps({"variant": name, "dtype": a.dtype, "round": rnd, "N": c["N"], "batch": a.batch,
+                                  "heads": a.heads, **r}), flush=True)
     finally:
         if a.n:
             lib.vit_sdpa_long_config(-1)
     med = {name: {k: statistics.median(r[k] for r in rs) for k in ("fwd_ms", "bwd_ms")} for name, rs in res.items()}
-    out = {"summary": True, "batch": a.batch, "heads": a.heads, "n": a.n, "n_resident": a.n_resident, "median_ms": med}
+    # round-to-round spread of each variant: (max - min) / median over the rounds
+    spread = {name: {k: round((max(r[k] for r in rs) - min(r[k] for r in rs)) / med[name][k], 4)
+                     for k in ("fwd_ms", "bwd_ms")} for name, rs in res.items()}
+    out = {"summary": True, "dtype": a.dtype, "batch": a.batch, "heads": a.heads, "n": a.n,
+           "n_resident": a.n_resident, "median_ms": med, "spread": spread}
     if "streamed" in med and "generic" in med:
         out["generic_over_streamed"] = {k: round(med["generic"][k] / med["streamed"][k], 2) for k in ("fwd_ms", "bwd_ms")}
     if "streamed" in med and "resident" in med:

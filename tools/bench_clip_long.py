@@ -1,0 +1,84 @@
+"""CLIP-HBA ViT-L/14@336px + DoRA fp32 train step (config C3's recipe -- r = 32 on the last two visual blocks
+and the last text block, MSE, AdamW -- on the 336-pixel tower: 577 visual tokens), with attention past 288
+tokens on the streamed f32 kernels against the generic ones (vit_sdpa_long_config(1) / (0)), alternated over
+--rounds rounds in one process.  Prints one JSON line: the median images/s of each variant and their ratio.
+
+    python tools/bench_clip_long.py [--batch 16] [--steps 5] [--warmup 2] [--rounds 3] [--steps-generic 2]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "vit-project_amd"))
+
+import torch  # noqa: E402
+
+import vit_amd  # noqa: E402
+from vit_amd import _lib as L  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps-generic", type=int, default=2)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--prompts", type=int, default=66)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    lib = L.lib()
+    torch.manual_seed(0)
+    m = vit_amd.CLIPHBA([f"c{i}" for i in range(a.prompts)], "ViT-L/14@336px", pos_embedding=True)
+    vit_amd.apply_dora_to_ViT(m, n_vision_layers=2, n_transformer_layers=1, r=32)
+    vit_amd.switch_dora_layers(m, freeze_all=True, dora_state=True)
+    m = m.to(dev)
+    opt = vit_amd.FusedAdamW([p for p in m.parameters() if p.requires_grad], lr=3e-4)
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(a.batch, 3, 336, 336, generator=g).to(dev)
+    y = (torch.randn(a.batch, a.prompts, generator=g) * 0.5 + 1.0).to(dev)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = vit_amd.mse_loss(m(x), y)
+        loss.backward()
+        opt.step()
+        return loss
+
+    def run(mode, steps, warmup):
+        lib.vit_sdpa_long_config(mode)
+        for _ in range(warmup):
+            step()
+        torch.cuda.synchronize()
+        c0 = lib.vit_sdpa_long_f32_count(0)
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            loss = step()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert torch.isfinite(loss)
+        return a.batch * steps / dt, lib.vit_sdpa_long_f32_count(0) - c0
+
+    ips = {"streamed": [], "generic": []}
+    try:
+        for rnd in range(a.rounds):
+            for name, mode, steps in (("streamed", 1, a.steps), ("generic", 0, a.steps_generic)):
+                r, calls = run(mode, steps, a.warmup if rnd == 0 and mode else 1)
+                assert (calls > 0) == bool(mode), (name, calls)
+                ips[name].append(round(r, 2))
+    finally:
+        lib.vit_sdpa_long_config(-1)
+    med = {k: statistics.median(v) for k, v in ips.items()}
+    print(json.dumps({"metric": "images/sec CLIP-HBA ViT-L/14@336px + DoRA fp32 train step", "batch": a.batch,
+                      "steps": a.steps, "steps_generic": a.steps_generic, "rounds": a.rounds, "images_per_sec": ips,
+                      "median": med, "streamed_over_generic": round(med["streamed"] / med["generic"], 2),
+                      "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -3,8 +3,8 @@
 // text tower's build_attention_mask: key > query gets -inf).  Up to 288 tokens (197
 // for ViT-B/16, 257 for CLIP ViT-L/14, 77 for the CLIP text tower) the resident
 // kernels below run; past 288 (384-pixel fine-tuning: 577, patch 8: 785) the
-// streamed bf16 kernels (attn_*_stream), and for f32, causal or misaligned operands
-// the generic scalar kernels -- a causal and an f32 streamed form are out of scope.
+// streamed kernels (bf16 attn_*_stream, f32 attn_*_stream_f32), and for causal or
+// misaligned operands the generic scalar kernels -- a causal streamed form is out of scope.
 //
 // q/k/v are read in place from the fused qkv GEMM output [B*N, 3*D] (row stride
 // ld_qkv), the output o is written as [B*N, D] (the proj GEMM operand), and the
@@ -1441,7 +1441,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const T* __restrict__ o
 // a key past N gets score -inf (p = 0 exactly), a query past N gets lse = +inf (p = 0 exactly).
 // Every output element has one owner and every sum a fixed order: runs are bitwise repeatable.
 // LDS: 2 x 16 KiB (+ 1 KiB lse / delta in dkv); 128-VGPR budget, so two workgroups share a CU.
-// Out of scope: a causal and an f32 streamed form (those take the generic kernels past 288 tokens).
+// Out of scope: a causal streamed form (it takes the generic kernels past 288 tokens); f32: attn_*_stream_f32.
 // ---------------------------------------------------------------------------
 constexpr int ST_CH = 64;             // rows per streamed chunk
 constexpr int ST_QB = AT_WAVES * 16;  // queries (keys) per workgroup
@@ -1738,6 +1738,309 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dkv_stream(const bf16*
   }
 }
 
+// ---------------------------------------------------------------------------
+// Streamed f32 attention (N > 288 at the reference's fp32 precision: CLIP ViT-L/14@336px, 577 tokens): the
+// resident f32 kernels' operand algebra -- v_mfma_f32_16x16x4_f32, a lane holding the 16 head dims
+// [16g, 16g + 16) of its query (key), P / dS fed from registers, the kswz row image read by rows
+// (f32_row16) and by columns (f32_chunk) -- on the streamed kernels' schedule: grid (B*H, ceil(N / 128)),
+// a two-buffer LDS ring of 64-row chunks, the next chunk's global loads issued before the MFMA work on
+// the current one and committed after it, one barrier per chunk.  An f32 chunk image is 64 x 256 B =
+// 16 KiB, so a thread moves two 16-B pieces of each of the two images per chunk and the ring takes
+// 64 KiB (+ 1 KiB of lse * log2(e) / delta strips in dkv).  Ragged ends, ownership and summation order
+// follow the bf16 streamed kernels: one owner per output element, no atomics, bitwise repeatable.
+// ---------------------------------------------------------------------------
+constexpr int SF_IMG = ST_CH * 64;  // floats per f32 chunk image
+static_assert(ST_CH * 16 == 2 * AT_THREADS, "two 16-B pieces of an f32 chunk image per thread");
+
+struct SfPiece { f32x4 a[2], b[2]; };
+// this thread's two pieces (rows r and r + 32 of the chunk) of rows [j0, j0 + 64) of two head slices
+__device__ __forceinline__ SfPiece sf_fetch(const float* sa, int64_t lda, const float* sb, int64_t ldb, int j0, int N) {
+  const int c = threadIdx.x & 15;
+  SfPiece p;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int row = min(j0 + u * 32 + (int)(threadIdx.x >> 4), N - 1);
+    p.a[u] = *reinterpret_cast<const f32x4*>(sa + (int64_t)row * lda + c * 4);
+    p.b[u] = *reinterpret_cast<const f32x4*>(sb + (int64_t)row * ldb + c * 4);
+  }
+  return p;
+}
+__device__ __forceinline__ void sf_commit(float* buf, SfPiece p, int j0, int N) {
+  const int c = threadIdx.x & 15;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int r = u * 32 + (int)(threadIdx.x >> 4);
+    if (j0 + r >= N) { p.a[u] = f32x4{0.f, 0.f, 0.f, 0.f}; p.b[u] = p.a[u]; }
+    const int at = r * 64 + ((c ^ kswz(r)) << 2);
+    *reinterpret_cast<f32x4*>(buf + at) = p.a[u];
+    *reinterpret_cast<f32x4*>(buf + SF_IMG + at) = p.b[u];
+  }
+}
+constexpr int SF_LDS = 2 * 2 * SF_IMG * 4;                      // fwd, dq: [buffer][K | V]
+constexpr int SF_BUF_DKV = 2 * SF_IMG + 2 * ST_CH;              // floats: Q | dO | lse * log2(e) | delta
+constexpr int SF_LDS_DKV = 2 * SF_BUF_DKV * 4;
+
+__global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_stream_f32(const float* __restrict__ qkv, int64_t ld_qkv, int D,
+                                                                    int H, int N, float scale, float* __restrict__ o,
+                                                                    int64_t ld_o, float* __restrict__ lse) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* ring = reinterpret_cast<float*>(smem);
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, l15 = lane & 15;
+  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const int q = blockIdx.y * ST_QB + wave * 16 + l15;
+  float qf[16];
+  f32_glob16(base + (int64_t)min(q, N - 1) * ld_qkv + 16 * g, qf);
+  const int nc = (N + ST_CH - 1) / ST_CH;
+  SfPiece pc = sf_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, 0, N);
+  sf_commit(ring, pc, 0, N);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  float m = -INFINITY, l = 0.f;  // running max (raw scores, all 4 lanes of a query agree); this lane's part of the sum
+  f32x4 oacc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const float* Kc = ring + (c & 1) * 2 * SF_IMG;
+    const float* Vc = Kc + SF_IMG;
+    const int j0 = c * ST_CH;
+    const bool more = c + 1 < nc;
+    if (more) pc = sf_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0 + ST_CH, N);
+    f32x4 s[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {  // one key tile's K rows live at a time: the 128-register budget
+      float kf[16];
+      f32_row16(Kc, kt * 16 + l15, g, kf);
+      s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) s[kt] = mfma4(kf[ks], qf[ks], s[kt]);  // S^T[key 4g + r][query l15]
+      if (kt % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // bound K-row hoisting (VGPRs)
+    }
+    if (j0 + ST_CH > N) {  // wave-uniform: only the last chunk holds keys >= N
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (j0 + kt * 16 + 4 * g + r >= N) s[kt][r] = -INFINITY;
+    }
+    float mt = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kt][r]);
+    mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
+    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+    const float mn = fmaxf(m, mt);             // finite from the first chunk on: key 0 is never masked
+    const float alpha = fexp2((m - mn) * c2);  // first chunk: m = -inf -> 0
+    m = mn;
+    const float mc = m * c2;
+    float lt = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { const float p = fexp2(fmaf(s[kt][r], c2, -mc)); s[kt][r] = p; lt += p; }
+    l = fmaf(l, alpha, lt);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) oacc[dt] *= alpha;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const f32x4 v = f32_chunk(Vc, kt * 16 + 4 * g + r, l15);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) oacc[dt] = mfma4(v[dt], s[kt][r], oacc[dt]);
+      }
+    if (more) sf_commit(ring + ((c + 1) & 1) * 2 * SF_IMG, pc, j0 + ST_CH, N);
+    __syncthreads();
+  }
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (q < N) {
+    const float inv = 1.0f / l;
+    float* orow = o + ((int64_t)b * N + q) * ld_o + h * 64 + 16 * g;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+      *reinterpret_cast<f32x4*>(orow + 4 * rr) =
+          f32x4{oacc[0][rr] * inv, oacc[1][rr] * inv, oacc[2][rr] * inv, oacc[3][rr] * inv};
+    if (g == 0 && lse) lse[(int64_t)bh * N + q] = (m * c2 + __log2f(l)) * LN2;
+  }
+}
+
+// query-parallel half of the streamed f32 backward: delta = rowsum(dO * O) and dQ (attn_bwd_dq_f32mfma's loop per chunk)
+__global__ __launch_bounds__(AT_THREADS, 4) void attn_bwd_dq_stream_f32(
+    const float* __restrict__ qkv, int64_t ld_qkv, int D, int H, int N, float scale, const float* __restrict__ o,
+    int64_t ld_o, const float* __restrict__ dout, int64_t ld_do, const float* __restrict__ lse,
+    float* __restrict__ delta_out, float* __restrict__ dqkv, int64_t ld_dqkv) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* ring = reinterpret_cast<float*>(smem);
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, l15 = lane & 15;
+  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const int q = blockIdx.y * ST_QB + wave * 16 + l15, qc = min(q, N - 1);
+  float qf[16], df[16];
+  float dl = 0.f;
+  {
+    float of[16];
+    f32_glob16(base + (int64_t)qc * ld_qkv + 16 * g, qf);
+    f32_glob16(dout + ((int64_t)b * N + qc) * ld_do + h * 64 + 16 * g, df);
+    f32_glob16(o + ((int64_t)b * N + qc) * ld_o + h * 64 + 16 * g, of);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) dl = fmaf(df[j], of[j], dl);
+  }
+  dl += __shfl_xor(dl, 16, 64);
+  dl += __shfl_xor(dl, 32, 64);
+  if (q < N && g == 0) delta_out[(int64_t)bh * N + q] = dl;
+  const float l2 = lse[(int64_t)bh * N + qc] * LOG2E;
+  const int nc = (N + ST_CH - 1) / ST_CH;
+  SfPiece pc = sf_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, 0, N);
+  sf_commit(ring, pc, 0, N);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  f32x4 dq[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const float* Kc = ring + (c & 1) * 2 * SF_IMG;
+    const float* Vc = Kc + SF_IMG;
+    const int j0 = c * ST_CH;
+    const bool more = c + 1 < nc;
+    if (more) pc = sf_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0 + ST_CH, N);
+#pragma unroll 1
+    for (int kt = 0; kt < 4; ++kt) {
+      float kf[16], vf[16];
+      f32_row16(Kc, kt * 16 + l15, g, kf);
+      f32_row16(Vc, kt * 16 + l15, g, vf);
+      f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = st;
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) {
+        st = mfma4(kf[ks], qf[ks], st);  // S^T[key 4g + r][query l15]
+        dpt = mfma4(vf[ks], df[ks], dpt);
+      }
+      f32x4 ds;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = j0 + kt * 16 + 4 * g + r < N ? fexp2(fmaf(st[r], c2, -l2)) : 0.f;
+        ds[r] = p * (dpt[r] - dl);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const f32x4 a = f32_chunk(Kc, kt * 16 + 4 * g + r, l15);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma4(a[dt], ds[r], dq[dt]);
+      }
+    }
+    if (more) sf_commit(ring + ((c + 1) & 1) * 2 * SF_IMG, pc, j0 + ST_CH, N);
+    __syncthreads();
+  }
+  if (q < N) {
+    float* row = dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64 + 16 * g;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+      *reinterpret_cast<f32x4*>(row + 4 * rr) =
+          f32x4{dq[0][rr] * scale, dq[1][rr] * scale, dq[2][rr] * scale, dq[3][rr] * scale};
+  }
+}
+
+// key-parallel half: dK, dV of the workgroup's 128 keys (K, V rows in registers) over streamed Q / dO chunks.
+// kf, vf, dk, dv are 64 live values per lane before the chunk's own operands: one workgroup per CU
+// (256-register budget), where the other two kernels keep the 128-register budget of two.
+__global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dkv_stream_f32(
+    const float* __restrict__ qkv, int64_t ld_qkv, int D, int H, int N, float scale, const float* __restrict__ dout,
+    int64_t ld_do, const float* __restrict__ lse, const float* __restrict__ delta_in, float* __restrict__ dqkv,
+    int64_t ld_dqkv) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* ring = reinterpret_cast<float*>(smem);
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
+  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const float* dob = dout + (int64_t)b * N * ld_do + h * 64;
+  const int key = blockIdx.y * ST_QB + wave * 16 + l15, kc = min(key, N - 1);
+  const bool kvalid = key < N;
+  float kf[16], vf[16];
+  f32_glob16(base + (int64_t)kc * ld_qkv + D + 16 * g, kf);
+  f32_glob16(base + (int64_t)kc * ld_qkv + 2 * D + 16 * g, vf);
+  // row constants of a chunk: threads 0..63 carry lse * log2(e) (+inf past N: p = 0), 64..127 delta (0 past N)
+  auto stat_fetch = [&](int j0) -> float {
+    if (tid >= 2 * ST_CH) return 0.f;
+    const int i = j0 + (tid & (ST_CH - 1));
+    if (tid < ST_CH) return i < N ? lse[(int64_t)bh * N + i] * LOG2E : INFINITY;
+    return i < N ? delta_in[(int64_t)bh * N + i] : 0.f;
+  };
+  auto stat_commit = [&](float* buf, float v) {
+    if (tid < 2 * ST_CH) buf[2 * SF_IMG + tid] = v;
+  };
+  const int nc = (N + ST_CH - 1) / ST_CH;
+  SfPiece pc = sf_fetch(base, ld_qkv, dob, ld_do, 0, N);
+  float sv = stat_fetch(0);
+  sf_commit(ring, pc, 0, N);
+  stat_commit(ring, sv);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = dk[dt]; }
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const float* Qc = ring + (c & 1) * SF_BUF_DKV;
+    const float* Oc = Qc + SF_IMG;  // dO
+    const float* l2s = Qc + 2 * SF_IMG;
+    const float* dls = l2s + ST_CH;
+    const int j0 = c * ST_CH;
+    const bool more = c + 1 < nc;
+    if (more) {
+      pc = sf_fetch(base, ld_qkv, dob, ld_do, j0 + ST_CH, N);
+      sv = stat_fetch(j0 + ST_CH);
+    }
+#pragma unroll 1
+    for (int qt = 0; qt < 4; ++qt) {
+      float qf[16], df[16];
+      f32_row16(Qc, qt * 16 + l15, g, qf);
+      f32_row16(Oc, qt * 16 + l15, g, df);
+      f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dpc = sc;
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) {
+        sc = mfma4(qf[ks], kf[ks], sc);  // S[query 4g + r][key l15]
+        dpc = mfma4(df[ks], vf[ks], dpc);
+      }
+      const f32x4 l2 = *reinterpret_cast<const f32x4*>(l2s + qt * 16 + 4 * g);
+      const f32x4 dl = *reinterpret_cast<const f32x4*>(dls + qt * 16 + 4 * g);
+      f32x4 p, ds;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float pv = kvalid ? fexp2(fmaf(sc[r], c2, -l2[r])) : 0.f;
+        p[r] = pv;
+        ds[r] = pv * (dpc[r] - dl[r]);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const f32x4 ao = f32_chunk(Oc, qt * 16 + 4 * g + r, l15), aq = f32_chunk(Qc, qt * 16 + 4 * g + r, l15);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          dv[dt] = mfma4(ao[dt], p[r], dv[dt]);
+          dk[dt] = mfma4(aq[dt], ds[r], dk[dt]);
+        }
+      }
+    }
+    if (more) {
+      float* nb = ring + ((c + 1) & 1) * SF_BUF_DKV;
+      sf_commit(nb, pc, j0 + ST_CH, N);
+      stat_commit(nb, sv);
+    }
+    __syncthreads();
+  }
+  if (kvalid) {
+    float* row = dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64 + 16 * g;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      *reinterpret_cast<f32x4*>(row + D + 4 * rr) =
+          f32x4{dk[0][rr] * scale, dk[1][rr] * scale, dk[2][rr] * scale, dk[3][rr] * scale};
+      *reinterpret_cast<f32x4*>(row + 2 * D + 4 * rr) = f32x4{dv[0][rr], dv[1][rr], dv[2][rr], dv[3][rr]};
+    }
+  }
+}
+
 // qkv-bias gradient partials past 288 tokens: part[b][c] = sum over the image's N rows of dqkv[.][c], one
 // thread per column, rows in a fixed order (8 interleaved chains) -- the [B][3D] layout the resident
 // kernels leave.  It reads dqkv once, a few percent of the bytes the two backward kernels move.
@@ -1758,13 +2061,24 @@ __global__ __launch_bounds__(256) void attn_bias_image(const bf16* __restrict__ 
 // Past 288 tokens (vit_sdpa_long_config / VIT_ATTN_LONG): 1 = the streamed MFMA kernels (default),
 // 0 = the generic kernels.  g_long_count: vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed kernels.
 static int g_long_mode = -1;
-static int g_long_count = 0;
+static int g_long_count = 0;      // bf16 streamed calls
+static int g_long_f32_count = 0;  // f32 streamed calls
 static bool attn_long_stream() {
   if (g_long_mode >= 0) return g_long_mode != 0;
   static const int v = [] { const char* e = getenv("VIT_ATTN_LONG"); return e && *e == '0' ? 0 : 1; }();
   return v != 0;
 }
 constexpr int AT_RESIDENT_MAX = 288;  // the resident kernels' token limit (NT_CASES)
+
+// the streamed f32 kernels' rings are past the 64 KiB static limit: dynamic LDS, raised once
+static void stream_f32_attrs() {
+  static bool attr = false;
+  if (attr) return;
+  (void)hipFuncSetAttribute((const void*)attn_fwd_stream_f32, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS);
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_stream_f32, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS);
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_stream_f32, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS_DKV);
+  attr = true;
+}
 
 // ---------------------------------------------------------------------------
 template <int NT>
@@ -1892,18 +2206,25 @@ int vit_sdpa_bwd_variant(int v) {
   return 0;
 }
 
-// Kernel choice past 288 tokens (bf16, non-causal, aligned): -1 = from the environment (VIT_ATTN_LONG=0|1,
-// default 1), 0 = the generic kernels, 1 = the streamed MFMA kernels.  Returns the previous mode.
+// Kernel choice past 288 tokens (bf16 or f32, non-causal, aligned): -1 = from the environment
+// (VIT_ATTN_LONG=0|1, default 1), 0 = the generic kernels, 1 = the streamed MFMA kernels of the dtype
+// (f32 also stays generic under VIT_ATTN_F32_GENERIC=1).  Returns the previous mode.
 int vit_sdpa_long_config(int mode) {
   const int prev = g_long_mode;
   g_long_mode = mode < 0 ? -1 : (mode != 0);
   return prev;
 }
-// Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed kernels (one per call: the
-// backward's two kernels count once); reset != 0 zeroes it after reading.
+// Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed bf16 kernels (one per call:
+// the backward's two kernels count once); reset != 0 zeroes it after reading.
 int vit_sdpa_long_count(int reset) {
   const int c = g_long_count;
   if (reset) g_long_count = 0;
+  return c;
+}
+// The same count for the streamed f32 kernels.
+int vit_sdpa_long_f32_count(int reset) {
+  const int c = g_long_f32_count;
+  if (reset) g_long_f32_count = 0;
   return c;
 }
 
@@ -1922,6 +2243,15 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
                        (const bf16*)qkv, ld_qkv, D, H, N, scale, (bf16*)o, ld_o, lse);
     VIT_CHECK_LAUNCH();
     ++g_long_count;
+    return 0;
+  }
+  if (!resident && dtype == VIT_F32 && !causal && (ld_qkv % 4 == 0) && (ld_o % 4 == 0) && attn_long_stream() &&
+      !attn_f32_generic()) {
+    stream_f32_attrs();
+    hipLaunchKernelGGL(attn_fwd_stream_f32, dim3(B * H, (N + ST_QB - 1) / ST_QB), dim3(AT_THREADS), SF_LDS, s,
+                       (const float*)qkv, ld_qkv, D, H, N, scale, (float*)o, ld_o, lse);
+    VIT_CHECK_LAUNCH();
+    ++g_long_f32_count;
     return 0;
   }
   if (resident && dtype == VIT_BF16 && (ld_qkv % 8 == 0) && (ld_o % 4 == 0)) {
@@ -2054,6 +2384,20 @@ int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
 #undef CASE
     }
     if (rc) return rc;
+    if (dbias) return vit_colsum(dtype, B * N, 3 * D, dqkv, ld_dqkv, dbias, partial, partial_floats, 0, stream);
+    return 0;
+  }
+  if (!resident && dtype == VIT_F32 && !causal && (ld_qkv % 4 == 0) && (ld_do % 4 == 0) && (ld_dqkv % 4 == 0) &&
+      (ld_o % 4 == 0) && attn_long_stream() && !attn_f32_generic()) {
+    stream_f32_attrs();
+    const dim3 grid(B * H, (N + ST_QB - 1) / ST_QB);
+    hipLaunchKernelGGL(attn_bwd_dq_stream_f32, grid, dim3(AT_THREADS), SF_LDS, s, (const float*)qkv, ld_qkv, D, H, N,
+                       scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta_ws, (float*)dqkv, ld_dqkv);
+    VIT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(attn_bwd_dkv_stream_f32, grid, dim3(AT_THREADS), SF_LDS_DKV, s, (const float*)qkv, ld_qkv, D, H,
+                       N, scale, (const float*)dout, ld_do, lse, (const float*)delta_ws, (float*)dqkv, ld_dqkv);
+    VIT_CHECK_LAUNCH();
+    ++g_long_f32_count;
     if (dbias) return vit_colsum(dtype, B * N, 3 * D, dqkv, ld_dqkv, dbias, partial, partial_floats, 0, stream);
     return 0;
   }

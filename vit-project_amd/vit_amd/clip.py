@@ -312,7 +312,9 @@ class CLIP(nn.Module):
         """Block-scaled e4m3 attention (vit_sdpa_fwd_fp8, BASELINE configs[4]) in every block whose
         forward needs no backward: the frozen blocks in front of the first trainable one in each
         tower (CLIP-HBA trains only the DoRA blocks 22-23 / 11, NEWP:484-544) and all blocks of a
-        no-grad pass (evaluation, behavioural RSA).  Trainable blocks keep bf16/f32 attention."""
+        no-grad pass (evaluation, behavioural RSA).  Trainable blocks keep bf16/f32 attention.
+        The fp8 kernel holds at most 320 tokens: on ``ViT-L/14@336px`` (577 visual tokens) a forward
+        with fp8 attention enabled raises ``ValueError``; leave it off there."""
         self.attention_fp8 = bool(enable)
 
     def _cfg(self, heads, causal, frozen=False):
@@ -419,6 +421,9 @@ class CLIP(nn.Module):
 _BACKBONES = {
     "ViT-L/14": dict(embed_dim=768, image_resolution=224, vision_layers=24, vision_width=1024, vision_patch_size=14,
                      transformer_width=768, transformer_heads=12, transformer_layers=12),
+    # 24 x 24 patches + cls = 577 visual tokens: attention takes the streamed kernels (bf16 or f32)
+    "ViT-L/14@336px": dict(embed_dim=768, image_resolution=336, vision_layers=24, vision_width=1024,
+                           vision_patch_size=14, transformer_width=768, transformer_heads=12, transformer_layers=12),
     "ViT-B/16": dict(embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=16,
                      transformer_width=512, transformer_heads=8, transformer_layers=12),
     "ViT-B/32": dict(embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=32,

@@ -404,7 +404,7 @@ def check_fp8_tokens(N):
 
 def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=False):
     """softmax(q k^T * scale) v per (b, h) from the fused qkv [B*N, 3D], any N (past 288 tokens the
-    streamed bf16 kernels, or the generic ones for f32 / causal); fp8: the block-scaled e4m3
+    streamed bf16 or f32 kernels, or the generic ones for causal / misaligned rows); fp8: the block-scaled e4m3
     MFMA kernel (forward only: its lse is not the bf16 backward's; N <= 320)."""
     if fp8:
         check_fp8_tokens(N)
@@ -423,7 +423,9 @@ def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=Fal
 def sdpa_bwd(qkv2d, o, do, lse, B, H, N, dqkv=None, scale=None, dbias=None, causal=False, ws="", reduce_on=None):
     """dbias [3*H*64] (optional) receives the column sums of dqkv (the qkv bias gradient).
     ``ws``: workspace-name suffix (calls running concurrently on different streams need their own).
-    ``reduce_on`` (a ColBatch, bf16): the per-image bias partials are left for that batch to reduce."""
+    ``reduce_on`` (a ColBatch, bf16): the per-image bias partials are left for that batch to reduce.
+    Past 288 tokens: the streamed kernels of the dtype (bf16 or f32; generic for causal / misaligned rows);
+    in f32 dbias is a column sum over dqkv after the two kernels."""
     if dqkv is None:
         dqkv = torch.empty_like(qkv2d)
     scale = 64 ** -0.5 if scale is None else scale

@@ -207,6 +207,16 @@ int vit_layer_norm_bwd(int dtype_x, int dtype_dy, int rows, int D, const void* x
 /* defer_reduce = 1: dgamma / dbeta / dsum are not written; `partial` keeps their
  * [ceil(rows/64)][D] partials at float offsets 0, nblk*D, 2*nblk*D (followed by the
  * vit_colreduce scratch) for the caller to reduce with vit_colreduce. */
+/* Additive to ABI 10: the same backward with a compact residual gradient.  dres holds one row (stride ldres)
+ * per res_every rows of dx and is added to rows 0, res_every, 2 * res_every, ...; every other row adds zero
+ * (bit for bit the dense form over a dres that is zero outside those rows, which is then neither allocated,
+ * zero-filled nor read).  The class-token head (timm global_pool='token', VIT:139) sends a gradient into the
+ * last block that is non-zero on each image's row 0 alone: res_every = tokens per image. */
+int vit_layer_norm_bwd_cls(int dtype_x, int dtype_dy, int rows, int D, const void* x, int64_t ldx,
+                           const void* dy, int64_t lddy, const float* w, const float* mean, const float* rstd,
+                           const float* dres, int64_t ldres, int res_every, float* dx, int64_t lddx, void* dx_copy,
+                           int64_t ld_copy, int dtype_copy, int compact_np, float* dgamma, float* dbeta, float* dsum,
+                           float* partial, int64_t partial_floats, int defer_reduce, void* stream);
 int vit_layer_norm_bwd_partial_floats(int rows, int D);
 int vit_layer_norm_bwd_blocks(int rows); /* partial rows: the [nblk][D] partial blocks' nblk */
 
@@ -219,6 +229,15 @@ int vit_layer_norm_bwd_blocks(int rows); /* partial rows: the [nblk][D] partial 
  * B*H <= 65535). */
 int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o,
                  int64_t ld_o, float* lse, float scale, int causal, void* stream);
+/* Additive to ABI 10: the query-limited forward for a block whose output is read in row 0 of each image alone
+ * (timm global_pool='token' after the last block, VIT:139).  bf16, N <= 288, ld_qkv % 8 == 0, ld_o % 4 == 0: the
+ * resident MFMA kernel on query tile 0 -- rows 0..15 of every image keep vit_sdpa_fwd's bits in o and lse, every
+ * other row gets o = 0 and lse = +inf (a backward over those rows then sees p = 0 and delta = 0 exactly).  Any
+ * other dtype / N / alignment: vit_sdpa_fwd unmasked, all rows.  vit_sdpa_cls_count: host-side count of calls
+ * that took the query-limited kernel (reset != 0 zeroes it after reading). */
+int vit_sdpa_fwd_cls(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o,
+                     int64_t ld_o, float* lse, float scale, void* stream);
+int vit_sdpa_cls_count(int reset);
 /* fp8 scaled-dot-product attention forward (BASELINE configs[4]: the sweep's frozen CLIP tower blocks
  * and the RSA evaluation forward; replaces the same F.scaled_dot_product_attention call as
  * vit_sdpa_fwd): q/k/v quantised in-kernel to block-scaled OCP e4m3 (E8M0 scale per 32 values),

@@ -121,7 +121,10 @@ static unsigned long long* g_attn_stamps = nullptr;
 // ---------------------------------------------------------------------------
 // bf16 forward
 // ---------------------------------------------------------------------------
-template <int NT, bool STAMP = false, bool CAUSAL = false>  // key/query tiles of 16: NT = ceil(N/16)
+// CLS (the class-token tail's last block: only query 0 of each head is read): query tile 0 alone, on the
+// same arithmetic, so o and lse of rows 0..15 keep their bits; the rows that are not computed get o = 0 and
+// lse = +inf, so a backward over them sees p = exp(s - inf) = 0 and delta = 0 exactly.
+template <int NT, bool STAMP = false, bool CAUSAL = false, bool CLS = false>  // key/query tiles of 16: NT = ceil(N/16)
 __global__ __launch_bounds__(AT_THREADS, NT <= 14 ? 4 : 2) void attn_fwd_mfma(const bf16* __restrict__ qkv, int64_t ld_qkv, int D,
                                                      int H, int N, float scale, bf16* __restrict__ o,
                                                      int64_t ld_o, float* __restrict__ lse, int causal,
@@ -144,7 +147,13 @@ __global__ __launch_bounds__(AT_THREADS, NT <= 14 ? 4 : 2) void attn_fwd_mfma(co
   __syncthreads();
   AT_STAMP(1)
   const float c2 = scale * LOG2E;
-  for (int qt = wave; qt < NT; qt += AT_WAVES) {
+  if constexpr (CLS) {
+    for (int i = 16 * 16 + threadIdx.x; i < N * 16; i += AT_THREADS)  // rows 16 .. N - 1: 16 pieces of 4
+      *reinterpret_cast<bf16x4*>(o + ((int64_t)b * N + (i >> 4)) * ld_o + h * 64 + (i & 15) * 4) =
+          bf16x4{(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+    for (int r = 16 + threadIdx.x; r < N; r += AT_THREADS) lse[(int64_t)bh * N + r] = INFINITY;
+  }
+  for (int qt = wave; qt < (CLS ? 1 : NT); qt += AT_WAVES) {
     const int q = qt * 16 + (lane & 15);
     bf16x8 qf[2];
     {
@@ -2187,6 +2196,16 @@ static int bwd_mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N,
   return 0;
 }
 
+template <int NT>
+static int fwd_mfma_cls(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, void* o, int64_t ld_o,
+                        float* lse, hipStream_t s) {
+  hipLaunchKernelGGL((attn_fwd_mfma<NT, false, false, true>), dim3(B * H), dim3(AT_THREADS), 0, s, (const bf16*)qkv,
+                     ld_qkv, D, H, N, scale, (bf16*)o, ld_o, lse, 0, nullptr);
+  VIT_CHECK_LAUNCH();
+  return 0;
+}
+static int g_cls_count = 0;
+
 #define NT_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18)
 
 extern "C" {
@@ -2278,6 +2297,30 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
     hipLaunchKernelGGL(attn_fwd_generic<float>, grid, dim3(256), 0, s, (const float*)qkv, ld_qkv, D, H, N, scale, (float*)o, ld_o, lse, causal);
   VIT_CHECK_LAUNCH();
   return 0;
+}
+
+// Query-limited forward: only query 0 of every (b, h) will be read.  bf16, N <= 288, aligned rows: the
+// resident kernel on query tile 0 (rows 0..15 of each image bit for bit vit_sdpa_fwd's; every other row
+// o = 0, lse = +inf).  Anything else: vit_sdpa_fwd, unmasked (all rows).
+int vit_sdpa_fwd_cls(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o,
+                     int64_t ld_o, float* lse, float scale, void* stream) {
+  if (head_dim != 64 || N <= 0) return (int)hipErrorInvalidValue;
+  if (N <= AT_RESIDENT_MAX && dtype == VIT_BF16 && (ld_qkv % 8 == 0) && (ld_o % 4 == 0) && lse && !g_attn_stamps) {
+    const int nt = (N + 15) / 16;
+    ++g_cls_count;
+    switch (nt) {
+#define CASE(n) case n: return fwd_mfma_cls<n>(qkv, ld_qkv, H * 64, B, H, N, scale, o, ld_o, lse, (hipStream_t)stream);
+      NT_CASES(CASE)
+#undef CASE
+    }
+  }
+  return vit_sdpa_fwd(dtype, B, H, N, head_dim, qkv, ld_qkv, o, ld_o, lse, scale, 0, stream);
+}
+// Host-side count of vit_sdpa_fwd_cls calls that took the query-limited kernel (reset != 0 zeroes it).
+int vit_sdpa_cls_count(int reset) {
+  const int n = g_cls_count;
+  if (reset) g_cls_count = 0;
+  return n;
 }
 
 // fp8 (block-scaled OCP e4m3) forward, head_dim 64, N <= 320: see attn_fwd_fp8.  qkv / o bf16

@@ -142,6 +142,16 @@ __device__ __forceinline__ bool copy_row(int row, int compact_np, int64_t& orow)
   return true;
 }
 
+// The residual-gradient row added to dx row `row`: dense (every == 0: row `row` of dres), or compact
+// (every > 0: dres holds one row per `every` rows of dx, added to the rows that are a multiple of it -- a
+// gradient that is non-zero on each image's class-token row alone; null = the row adds zero).
+__device__ __forceinline__ const float* res_row(const float* dres, int64_t ldres, int every, int row) {
+  if (!dres) return nullptr;
+  if (every <= 0) return dres + (int64_t)row * ldres;
+  const int q = row / every;
+  return row == q * every ? dres + (int64_t)q * ldres : nullptr;
+}
+
 // Backward: block = 4 waves over rows [blk*rows_per, ...), wave-strided.
 template <int NV, typename TX, typename TD, typename TC>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(
@@ -149,7 +159,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
     const float* __restrict__ w, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ dres, int64_t ldres, float* __restrict__ dx, int64_t lddx,
     TC* __restrict__ dxc, int64_t ldc, int compact_np, float* __restrict__ part_g,
-    float* __restrict__ part_b, float* __restrict__ part_s, int rows, int D, int rows_per) {
+    float* __restrict__ part_b, float* __restrict__ part_s, int rows, int D, int rows_per, int res_every) {
   constexpr int NP = NV > 0 ? NV * 4 : LN_SMAX;  // partial slots per lane
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float pg[NP], pb[NP], ps[NP];
@@ -169,9 +179,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
       float s1 = 0.f, s2 = 0.f;
       // the residual gradient is loaded with x and dy, so a row costs one memory round trip
       if (dres) {
+        const float* rr = res_row(dres, ldres, res_every, row);
 #pragma unroll
         for (int k = 0; k < NV; ++k)
-          rv[k] = *reinterpret_cast<const f32x4*>(dres + (int64_t)row * ldres + col4(lane, k));
+          rv[k] = rr ? *reinterpret_cast<const f32x4*>(rr + col4(lane, k)) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
       for (int k = 0; k < NV; ++k) {
@@ -203,6 +214,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
       }
     } else {
       float s1 = 0.f, s2 = 0.f;
+      const float* rr = res_row(dres, ldres, res_every, row);
 #pragma unroll
       for (int k = 0; k < LN_SMAX; ++k) {
         int c = lane + 64 * k;
@@ -220,7 +232,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
         if (c >= D) break;
         float xh = ((float)xr[c] - mu) * rs, g = (float)dyr[c] * w[c];
         float o = rs * (g - s1 - xh * s2);
-        if (dres) o += dres[(int64_t)row * ldres + c];
+        if (dres) o += rr ? rr[c] : 0.f;
         ps[k] += o;
         dxr[c] = o;
         if (keep) dxc[orow * ldc + c] = (TC)o;
@@ -289,7 +301,7 @@ __global__ __launch_bounds__(256) void ln_bwd_pipe_kernel(
     const float* __restrict__ w, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ dres, int64_t ldres, float* __restrict__ dx, int64_t lddx,
     TC* __restrict__ dxc, int64_t ldc, int compact_np, float* __restrict__ part_g,
-    float* __restrict__ part_b, float* __restrict__ part_s, int rows, int D, int rows_per) {
+    float* __restrict__ part_b, float* __restrict__ part_s, int rows, int D, int rows_per, int res_every) {
   constexpr int NP = NV * 4;
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float pg[NP], pb[NP], ps[NP];
@@ -301,13 +313,14 @@ __global__ __launch_bounds__(256) void ln_bwd_pipe_kernel(
   const int r0 = blockIdx.x * rows_per, r1 = min(rows, r0 + rows_per);
   using Row = LnRow<NV, TX, TD>;
   auto load = [&](int row, Row& R) {
+    const float* rr = res_row(dres, ldres, res_every, row);
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int c = col4(lane, k);
       R.x[k] = ld4<TX>(x + (int64_t)row * ldx + c);
       if constexpr (std::is_same<TD, float>::value) R.d[k] = *reinterpret_cast<const f32x4*>(dy + (int64_t)row * lddy + c);
       else R.d[k] = *reinterpret_cast<const bf16x4*>(dy + (int64_t)row * lddy + c);
-      R.r[k] = dres ? *reinterpret_cast<const f32x4*>(dres + (int64_t)row * ldres + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+      R.r[k] = rr ? *reinterpret_cast<const f32x4*>(rr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     R.mu = mean[row];
     R.rs = rstd[row];
@@ -405,9 +418,9 @@ template <typename TX, typename TD, typename TC>
 static void launch_bwd(int nv, int nblk, hipStream_t s, const void* x, int64_t ldx, const void* dy, int64_t lddy,
                        const float* w, const float* mean, const float* rstd, const float* dres, int64_t ldres,
                        float* dx, int64_t lddx, void* dxc, int64_t ldc, int compact_np, float* pg, float* pb,
-                       float* ps, int rows, int D, int rows_per) {
+                       float* ps, int rows, int D, int rows_per, int res_every) {
 #define B(K, NV) hipLaunchKernelGGL((K<NV, TX, TD, TC>), dim3(nblk), dim3(64 * LN_WAVES), 0, s, (const TX*)x, ldx, \
-                                 (const TD*)dy, lddy, w, mean, rstd, dres, ldres, dx, lddx, (TC*)dxc, ldc, compact_np, pg, pb, ps, rows, D, rows_per)
+                                 (const TD*)dy, lddy, w, mean, rstd, dres, ldres, dx, lddx, (TC*)dxc, ldc, compact_np, pg, pb, ps, rows, D, rows_per, res_every)
   if (g_ln_pipe < 0) { const char* v = getenv("VIT_LN_BWD_PIPE"); g_ln_pipe = v ? atoi(v) : 1; }
   const int pipe = g_ln_pipe;
   switch (nv) {
@@ -492,13 +505,17 @@ int vit_layer_norm_bwd_partial_floats(int rows, int D) {
   return (int)(3 * (int64_t)nblk * D + 3 * colreduce_scratch_floats(nblk, D));
 }
 
-int vit_layer_norm_bwd(int dtype_x, int dtype_dy, int rows, int D, const void* x, int64_t ldx,
-                       const void* dy, int64_t lddy, const float* w, const float* mean, const float* rstd,
-                       const float* dres, int64_t ldres, float* dx, int64_t lddx, void* dx_copy, int64_t ld_copy,
-                       int dtype_copy, int compact_np, float* dgamma, float* dbeta, float* dsum, float* partial,
-                       int64_t partial_floats, int defer_reduce, void* stream) {
+// res_every > 0 (vit_layer_norm_bwd_cls): dres is compact, one row (stride ldres) per res_every rows of dx,
+// added to rows 0, res_every, 2 * res_every, ...; every other row adds zero -- the same f32 adds as the
+// dense form over a dres that is zero outside those rows, without reading (or zero-filling) it.
+static int ln_bwd(int dtype_x, int dtype_dy, int rows, int D, const void* x, int64_t ldx,
+                  const void* dy, int64_t lddy, const float* w, const float* mean, const float* rstd,
+                  const float* dres, int64_t ldres, int res_every, float* dx, int64_t lddx, void* dx_copy,
+                  int64_t ld_copy, int dtype_copy, int compact_np, float* dgamma, float* dbeta, float* dsum,
+                  float* partial, int64_t partial_floats, int defer_reduce, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (rows <= 0) return 0;
+  if (res_every < 0) return (int)hipErrorInvalidValue;
   if (D > 64 * LN_SMAX) return (int)hipErrorInvalidValue;
   const int rows_per = ln_bwd_rows();
   const int nblk = vit_layer_norm_bwd_blocks(rows);
@@ -513,8 +530,8 @@ int vit_layer_norm_bwd(int dtype_x, int dtype_dy, int rows, int D, const void* x
              (ld_copy % 4 == 0);
   int nv = vec ? D / 256 : 0;
 #define LB(TX, TD) \
-  if (dtype_copy == VIT_BF16) launch_bwd<TX, TD, bf16>(nv, nblk, s, x, ldx, dy, lddy, w, mean, rstd, dres, ldres, dx, lddx, dx_copy, ld_copy, compact_np, pg, pb, ps, rows, D, rows_per); \
-  else launch_bwd<TX, TD, float>(nv, nblk, s, x, ldx, dy, lddy, w, mean, rstd, dres, ldres, dx, lddx, dx_copy, ld_copy, compact_np, pg, pb, ps, rows, D, rows_per);
+  if (dtype_copy == VIT_BF16) launch_bwd<TX, TD, bf16>(nv, nblk, s, x, ldx, dy, lddy, w, mean, rstd, dres, ldres, dx, lddx, dx_copy, ld_copy, compact_np, pg, pb, ps, rows, D, rows_per, res_every); \
+  else launch_bwd<TX, TD, float>(nv, nblk, s, x, ldx, dy, lddy, w, mean, rstd, dres, ldres, dx, lddx, dx_copy, ld_copy, compact_np, pg, pb, ps, rows, D, rows_per, res_every);
   if (dtype_x == VIT_F32 && dtype_dy == VIT_F32) { LB(float, float) }
   else if (dtype_x == VIT_F32) { LB(float, bf16) }
   else if (dtype_dy == VIT_BF16) { LB(bf16, bf16) }
@@ -530,6 +547,29 @@ int vit_layer_norm_bwd(int dtype_x, int dtype_dy, int rows, int D, const void* x
   }
   VIT_CHECK_LAUNCH();
   return 0;
+}
+
+int vit_layer_norm_bwd(int dtype_x, int dtype_dy, int rows, int D, const void* x, int64_t ldx,
+                       const void* dy, int64_t lddy, const float* w, const float* mean, const float* rstd,
+                       const float* dres, int64_t ldres, float* dx, int64_t lddx, void* dx_copy, int64_t ld_copy,
+                       int dtype_copy, int compact_np, float* dgamma, float* dbeta, float* dsum, float* partial,
+                       int64_t partial_floats, int defer_reduce, void* stream) {
+  return ln_bwd(dtype_x, dtype_dy, rows, D, x, ldx, dy, lddy, w, mean, rstd, dres, ldres, 0, dx, lddx, dx_copy,
+                ld_copy, dtype_copy, compact_np, dgamma, dbeta, dsum, partial, partial_floats, defer_reduce, stream);
+}
+
+// The same with a compact residual gradient: dres [ceil(rows / res_every)][D] (row stride ldres) is added to
+// rows 0, res_every, 2 * res_every, ... of dx (each image's class-token row when res_every = tokens per
+// image), nothing to the others.
+int vit_layer_norm_bwd_cls(int dtype_x, int dtype_dy, int rows, int D, const void* x, int64_t ldx,
+                           const void* dy, int64_t lddy, const float* w, const float* mean, const float* rstd,
+                           const float* dres, int64_t ldres, int res_every, float* dx, int64_t lddx, void* dx_copy,
+                           int64_t ld_copy, int dtype_copy, int compact_np, float* dgamma, float* dbeta, float* dsum,
+                           float* partial, int64_t partial_floats, int defer_reduce, void* stream) {
+  if (res_every < 1 || !dres) return (int)hipErrorInvalidValue;
+  return ln_bwd(dtype_x, dtype_dy, rows, D, x, ldx, dy, lddy, w, mean, rstd, dres, ldres, res_every, dx, lddx,
+                dx_copy, ld_copy, dtype_copy, compact_np, dgamma, dbeta, dsum, partial, partial_floats, defer_reduce,
+                stream);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@ package is the host-side mirror of the reference's module/optimizer interface.
 """
 from . import _lib
 from .model import (VisionTransformer, create_model, cross_entropy, set_wgrad_overlap, set_forward_only,
-                    block_forward_only)
+                    set_cls_tail, block_forward_only)
 from .pos_embed import resample_abs_pos_embed, adapt_state_dict
 from .optim import FusedSGD, FusedAdamW, CosineAnnealingLRWithWarmup
 from .dora import DoRALayer, dora_weight
@@ -20,7 +20,7 @@ from .clip import CLIPHBA, MSELoss, mse_loss, apply_dora_to_ViT, switch_dora_lay
 __all__ = ["VisionTransformer", "create_model", "cross_entropy", "set_wgrad_overlap", "FusedSGD", "FusedAdamW",
            "CosineAnnealingLRWithWarmup", "DoRALayer", "dora_weight", "rsa", "clip", "data", "CLIPHBA", "MSELoss",
            "mse_loss", "apply_dora_to_ViT", "switch_dora_layers", "count_trainable_parameters", "set_forward_only",
-           "block_forward_only", "evaluate", "EvalMeter", "validate", "resample_abs_pos_embed", "adapt_state_dict"]
+           "set_cls_tail", "block_forward_only", "evaluate", "EvalMeter", "validate", "resample_abs_pos_embed", "adapt_state_dict"]
 
 
 def load_library(path=None):

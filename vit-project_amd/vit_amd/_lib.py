@@ -54,11 +54,15 @@ SIGNATURES = {
     "vit_add_layer_norm_fwd": [i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, f32, vp],
     "vit_layer_norm_bwd": [i32, i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, i32,
                            i32, vp, vp, vp, vp, i64, i32, vp],
+    "vit_layer_norm_bwd_cls": [i32, i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, i64, i32, vp, i64, vp, i64, i32,
+                               i32, vp, vp, vp, vp, i64, i32, vp],
     "vit_layer_norm_bwd_partial_floats": [i32, i32],
     "vit_layer_norm_bwd_blocks": [i32],
     "vit_layer_norm_bwd_variant": [i32],
     "vit_sdpa_fwd": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, i32, vp],
     "vit_sdpa_fwd_fp8": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, i32, vp],
+    "vit_sdpa_fwd_cls": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, vp],
+    "vit_sdpa_cls_count": [i32],
     "vit_sdpa_bwd_variant": [i32],
     "vit_sdpa_long_config": [i32],
     "vit_sdpa_long_count": [i32],

@@ -86,6 +86,10 @@ _FUSED_RESID_F32 = [os.environ.get("VIT_FUSED_RESID_F32", "0") == "1"]
 # blocks that no backward can follow (no-grad passes, all-frozen blocks) take the forward-only chain
 # (block_forward_only); VIT_FWD_ONLY=0 / set_forward_only(False) keeps them on the training chain
 _FWD_ONLY = [os.environ.get("VIT_FWD_ONLY", "1") != "0"]
+# forward() pools the class token: its last block computes proj / norm2 / fc1 / fc2 for the B class rows only
+# and their gradients on tail_pad(N) rows per image (the class-token tail); VIT_CLS_TAIL=0 /
+# set_cls_tail(False) keeps the block dense
+_CLS_TAIL = [os.environ.get("VIT_CLS_TAIL", "1") != "0"]
 
 
 def set_wgrad_overlap(enable: bool):
@@ -270,7 +274,13 @@ def _block_chain(x, params, cfg, fwd_only):
     forward-only path (block_forward_only).  Returns (xo [B, N, D], the tensors a backward would need,
     the GEMM weight operands).  ``fwd_only``: fc1 runs the act-only epilogue and no act'(pre) tensor
     exists; every other launch, the half-batch schedule and the fused-residual ``pending`` state are
-    the training chain's."""
+    the training chain's.
+
+    cfg "cls_tail" (the last block under forward(), whose output only the class-token head reads): norm1,
+    qkv and attention run for all rows; proj, norm2, fc1, fc2 and the residual adds run for the B class rows
+    alone, read by stride N*D from the dense tensors, on compact [B, .] tensors.  xo is then [B, 1, D]: bit
+    for bit the dense block's class rows (GEMM and LayerNorm rows are independent).  The half-batch
+    schedule is the same: each chain carries its images' class rows."""
     n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
     B, N, D = x.shape
     H, T, eps = cfg["heads"], cfg["dtype"], cfg["eps"]
@@ -283,17 +293,20 @@ def _block_chain(x, params, cfg, fwd_only):
     x2 = x.reshape(M, D)
     F = fc1w.shape[0]
     f32 = torch.float32
-    h1, h2 = torch.empty(M, D, dtype=T, device=dev), torch.empty(M, D, dtype=T, device=dev)
-    m1, r1, m2, r2 = (torch.empty(M, dtype=f32, device=dev) for _ in range(4))
+    ct = bool(cfg.get("cls_tail"))
+    Mt = B if ct else M  # rows of everything downstream of attention
+    h1, h2 = torch.empty(M, D, dtype=T, device=dev), torch.empty(Mt, D, dtype=T, device=dev)
+    m1, r1 = (torch.empty(M, dtype=f32, device=dev) for _ in range(2))
+    m2, r2 = (torch.empty(Mt, dtype=f32, device=dev) for _ in range(2))
     qkv = torch.empty(M, 3 * D, dtype=T, device=dev)
     o = torch.empty(M, D, dtype=T, device=dev)
     lse = torch.empty(B * H * N, dtype=f32, device=dev)
-    xm, xo = torch.empty(M, D, dtype=f32, device=dev), torch.empty(M, D, dtype=f32, device=dev)
+    xm, xo = torch.empty(Mt, D, dtype=f32, device=dev), torch.empty(Mt, D, dtype=f32, device=dev)
     # fc1's epilogue writes act = GELU(pre) for fc2 and dact = GELU'(pre) for the backward
     # (the erf is evaluated once; the fc2 dgrad epilogue is then a multiply); a forward-only pass has
     # no backward to feed: no dact, and the act-only epilogue stores act alone (the same bits)
-    act = torch.empty(M, F, dtype=T, device=dev)
-    dact = None if fwd_only else torch.empty(M, F, dtype=T, device=dev)
+    act = torch.empty(Mt, F, dtype=T, device=dev)
+    dact = None if fwd_only else torch.empty(Mt, F, dtype=T, device=dev)
     Wqkv, Wproj, W1, W2 = _wt(qkvw, T), _wt(projw, T), _wt(fc1w, T), _wt(fc2w, T)
     causal = bool(cfg.get("causal", False))
     attn_fp8 = bool(cfg.get("attn_fp8", False))  # forward-only blocks (frozen prefix, no-grad passes)
@@ -308,7 +321,13 @@ def _block_chain(x, params, cfg, fwd_only):
     pend = rs.get("pending") if rs is not None else None
     pb = yb = None
     if rs is not None:
-        pb, yb = torch.empty(M, D, dtype=T, device=dev), torch.empty(M, D, dtype=T, device=dev)
+        pb, yb = torch.empty(Mt, D, dtype=T, device=dev), torch.empty(Mt, D, dtype=T, device=dev)
+    # class-token tail: the class rows of the residual stream and of the attention output, by stride
+    x_cls = o_cls = xc = None
+    if ct:
+        x_cls, o_cls = x2.view(B, N * D)[:, :D], o.view(B, N * D)[:, :D]
+        if rs is None:  # the EPI_RESID epilogue reads its residual at the output's row stride: compact copy
+            xc = torch.empty(B, D, dtype=f32, device=dev)
 
     def fc1(sl):
         if fwd_only:
@@ -339,8 +358,40 @@ def _block_chain(x, params, cfg, fwd_only):
             steps.append(lambda: ops.add_layer_norm_fwd(xm[sl], yb[sl], xo[sl]))
         return steps
 
+    def chain_tail(b0, b1):
+        """The class-token tail over images [b0, b1): the dense chain's first three launches, then its
+        remaining ones over the class rows b0 .. b1 of the compact tensors."""
+        sl, cs = slice(b0 * N, b1 * N), slice(b0, b1)
+        steps = [
+            ln1(sl),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
+            # (only query 0 of each head is read: the query-limited forward; the tail is never causal or fp8)
+            lambda: ops.sdpa_fwd_cls(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N]),
+        ]
+        if rs is not None:
+            steps += [
+                lambda: ops.linear_fwd(o_cls[cs], Wproj, projb.detach(), out=pb[cs]),
+                lambda: ops.add_layer_norm_fwd(x_cls[cs], pb[cs], xm[cs], n2w.detach(), n2b.detach(), eps,
+                                               out=h2[cs], mean=m2[cs], rstd=r2[cs]),
+                fc1(cs),
+                lambda: ops.linear_fwd(act[cs], W2, fc2b.detach(), out=yb[cs]),
+                lambda: ops.add_layer_norm_fwd(xm[cs], yb[cs], xo[cs]),
+            ]
+        else:
+            steps += [
+                lambda: ops.pad_cols(x_cls[cs], D, out=xc[cs]),
+                lambda: ops.linear_fwd(o_cls[cs], Wproj, projb.detach(), epi=L.EPI_RESID, resid=xc[cs], out=xm[cs]),
+                lambda: ops.layer_norm_fwd(xm[cs], n2w.detach(), n2b.detach(), eps, T, out=h2[cs], mean=m2[cs],
+                                           rstd=r2[cs]),
+                fc1(cs),
+                lambda: ops.linear_fwd(act[cs], W2, fc2b.detach(), epi=L.EPI_RESID, resid=xm[cs], out=xo[cs]),
+            ]
+        return steps
+
     def chain(b0, b1):
         """The block over images [b0, b1) (rows b0*N .. b1*N of every tensor) as its 7 launches."""
+        if ct:
+            return chain_tail(b0, b1)
         if rs is not None:
             return chain_fused(b0, b1)
         r0, r1_ = b0 * N, b1 * N
@@ -371,7 +422,7 @@ def _block_chain(x, params, cfg, fwd_only):
         mine, other = chain(0, hb), chain(hb, B)
         side.run(lambda: run(other))
         side.guard(x2, h1, m1, r1, qkv, o, lse, xm, h2, m2, r2, dact, act, xo,
-                   *(t for t in (pb, yb, *(pend or ())) if t is not None))
+                   *(t for t in (pb, yb, xc, *(pend or ())) if t is not None))
         run(mine)
         # each half only feeds the same half of the next block: a stack of blocks joins
         # once after its last block (cfg "defer_join", ViT._tokens) instead of per block
@@ -380,8 +431,8 @@ def _block_chain(x, params, cfg, fwd_only):
     else:
         run(chain(0, B))
     if rs is not None:
-        rs["pending"] = None if cfg.get("resid_last") else (xm, yb)
-    return xo.reshape(B, N, D), (x2, h1, m1, r1, qkv, o, lse, xm, h2, m2, r2, dact, act), (Wqkv, Wproj, W1, W2)
+        rs["pending"] = None if (ct or cfg.get("resid_last")) else (xm, yb)
+    return xo.reshape(B, Mt // B, D), (x2, h1, m1, r1, qkv, o, lse, xm, h2, m2, r2, dact, act), (Wqkv, Wproj, W1, W2)
 
 
 def block_forward_only(x, params, cfg):
@@ -405,6 +456,42 @@ def set_forward_only(enable: bool) -> bool:
     prev = _FWD_ONLY[0]
     _FWD_ONLY[0] = bool(enable)
     return prev
+
+
+# Rows per image of the tail's backward tensors (the class row, then zeros).  64 rests on three kernel
+# constants: the input-gradient epilogues sum columns per 64-row group (ops.DGRAD_SUM_ROWS), the weight-gradient
+# kernels accumulate one 32-row k-tile per MFMA (ops.WGRAD_KTILE_ROWS), and the LayerNorm backward writes one
+# partial block per ops.ln_bwd_rows_per() rows (32; VIT_LN_BWD_ROWS).  With 64 a multiple of each, every such
+# unit holds at most one class row, as in the dense launch (N > 64), and the sums keep the dense order.
+TAIL_PAD = 64
+
+
+def tail_pad(N: int, ln_rows_per: int = 32) -> int:
+    """Rows per image of the class-token tail's backward: TAIL_PAD where the padded launches' reduction
+    units line up with it, else N (the dense layout: zero rows instead of no rows, nothing to line up)."""
+    ok = (N > TAIL_PAD and ln_rows_per >= 1 and TAIL_PAD % ln_rows_per == 0
+          and TAIL_PAD % ops.DGRAD_SUM_ROWS == 0 and TAIL_PAD % ops.WGRAD_KTILE_ROWS == 0)
+    return TAIL_PAD if ok else N
+
+
+def cls_tail_enabled() -> bool:
+    return _CLS_TAIL[0]
+
+
+def set_cls_tail(enable: bool) -> bool:
+    """Let ``VisionTransformer.forward()`` run its last block as the class-token tail (default; environment
+    ``VIT_CLS_TAIL=0`` starts with it off) or dense (A/B runs, the equality tests).  Returns the previous
+    setting."""
+    prev = _CLS_TAIL[0]
+    _CLS_TAIL[0] = bool(enable)
+    return prev
+
+
+def wants_cls_tail(enabled: bool, cls_only: bool, global_pool: str, attn_fp8: bool = False) -> bool:
+    """The routing rule of the class-token tail, as a pure function: the last block of a pass whose caller
+    reads the class rows alone (forward(), never forward_features()) under class-token pooling.  The fp8
+    attention passes keep the dense block."""
+    return bool(enabled) and bool(cls_only) and global_pool == "token" and not attn_fp8
 
 
 def wants_forward_only(enabled: bool, grad_enabled: bool, input_requires_grad: bool,
@@ -447,6 +534,7 @@ class _BlockFn(torch.autograd.Function):
         ctx.meta = (B, N, D, H, T, cfg.get("compact_np", 0), cfg["quick_gelu"], causal)
         ctx.defer_bwd = bool(cfg.get("defer_bwd_join"))
         ctx.attn_fp8 = attn_fp8
+        ctx.cls_tail = bool(cfg.get("cls_tail"))
         ctx.grad_hook = cfg.get("grad_hook")
         ctx.flat_span = cfg.get("flat_span")
         return xo
@@ -459,9 +547,39 @@ class _BlockFn(torch.autograd.Function):
         B, N, D, H, T, compact_np, qg, causal = ctx.meta
         ng = ctx.needs_input_grad
         M = B * N
+        # class-token tail (_block_chain): dxo is the class rows' gradient [B, 1, D] and the forward saved
+        # compact [B, .] tensors.  The MLP, norm2 and proj gradients run on row-padded copies: P rows per
+        # image, the class row first, zeros after it (tail_pad).  A zero row adds exact zeros to every sum,
+        # and with one class row per 64-row group, per LayerNorm partial block and per 32-row k-tile every
+        # reduction adds the same terms in the same order as the dense block's: the partial rows are laid
+        # out as the dense launch's (spread_partials) and the weight gradients split as the dense pair.
+        ct = ctx.cls_tail
+        P = tail_pad(N, ops.ln_bwd_rows_per()) if ct else N
+        Mt = B * P
+        spread_sums = ct and P != N
         dev = dxo.device
-        dxo = dxo.contiguous().reshape(M, D)
+        dxo = dxo.contiguous().reshape(B if ct else M, D)
         dxo_c, dxo_sum = _take_copy(dxo, T, want_dsum=True)
+        pads = []
+
+        def rows_padded(t):  # [B, w] (any row stride) -> [B * P, w]
+            w = t.shape[1]
+            pads.append(ops.pad_cols(t, P * w).view(B * P, w))
+            return pads[-1]
+
+        dg_rows = ln_rows = sp_mlp = sp_attn = None
+        if ct:
+            dxo_c = rows_padded(dxo_c)
+            dxo = dxo_c if T == torch.float32 else rows_padded(dxo)
+            xm, h2, dact, act = rows_padded(xm), rows_padded(h2), rows_padded(dact), rows_padded(act)
+            m2, r2 = rows_padded(m2.view(B, 1)).view(-1), rows_padded(r2.view(B, 1)).view(-1)
+        if spread_sums:
+            F = act.shape[1]
+            rp = ops.ln_bwd_rows_per()  # (tail_pad: rp divides P, as do the other two units)
+            dg_rows = ops.dense_part_rows(B, N, ops.DGRAD_SUM_ROWS, P // ops.DGRAD_SUM_ROWS, dev)
+            ln_rows = ops.dense_part_rows(B, N, rp, P // rp, dev)
+            sp_mlp = ops.pair_split(M, D, F, F, D)
+            sp_attn = ops.pair_split(M, D, D, 3 * D, D, bool(compact_np))
         gelu_bwd = L.EPI_QGELU_BWD if qg else L.EPI_GELU_BWD
         side = _Side(dev)
         need_mlp_in = any(ng[0:11])     # anything upstream of fc2 (its input gradient path)
@@ -496,32 +614,36 @@ class _BlockFn(torch.autograd.Function):
             side.run(lambda: ops.linear_wgrad(dxo_c, act, out=g[11], reduce_on=rbw))
         dx = None
         if need_mlp_in:
-            dpre = ops.linear_dgrad(dxo_c, W2, out_dtype=T, epi=gelu_bwd, pre=dact, dbias=g[10], reduce_on=rb)
+            dpre = ops.linear_dgrad(dxo_c, W2, out_dtype=T, epi=gelu_bwd, pre=dact, dbias=g[10], reduce_on=rb,
+                                    part_rows=dg_rows)
             if pair_mlp:
-                side.run(lambda: ops.linear_wgrad_pair((dxo_c, act, g[11]), (dpre, h2, g[9]), rbw))
+                side.run(lambda: ops.linear_wgrad_pair((dxo_c, act, g[11]), (dpre, h2, g[9]), rbw, split=sp_mlp))
             elif ng[9]:
                 side.run(lambda: ops.linear_wgrad(dpre, h2, out=g[9], reduce_on=rbw))
         if any(ng[0:9]):
             dh2 = ops.linear_dgrad(dpre, W1, out_dtype=T)
-            dxm = torch.empty(M, D, dtype=torch.float32, device=dev)
-            dxm_c = dxm if T == torch.float32 else torch.empty(M, D, dtype=T, device=dev)
-            ops.layer_norm_bwd(xm, D, dh2, n2w.detach(), m2, r2, dxm, D, M, dres=dxo, ldres=D,
+            dxm = torch.empty(Mt, D, dtype=torch.float32, device=dev)
+            dxm_c = dxm if T == torch.float32 else torch.empty(Mt, D, dtype=T, device=dev)
+            ops.layer_norm_bwd(xm, D, dh2, n2w.detach(), m2, r2, dxm, D, Mt, dres=dxo, ldres=D,
                                dx_copy=None if T == torch.float32 else dxm_c, ld_copy=D, dgamma=g[7], dbeta=g[8],
-                               dsum=g[6], reduce_on=rb)
+                               dsum=g[6], reduce_on=rb, part_rows=ln_rows)
             # attention
             # block 0 (the patch rows' block, last in the backward): its last weight gradients are the tail
             tail = bool(compact_np)
-            pair_attn = rbw is not None and ng[5] and ng[3] and need_attn
+            # (padded tail: the proj gradient has B * P rows, the qkv one M: two launches with the pair's split)
+            pair_attn = rbw is not None and ng[5] and ng[3] and need_attn and not spread_sums
+            o_w = rows_padded(o.view(B, N * D)[:, :D]) if spread_sums else o
             if ng[5] and not pair_attn:
-                side.run(lambda: ops.linear_wgrad(dxm_c, o, out=g[5], tail=tail, reduce_on=rbw))
+                side.run(lambda: ops.linear_wgrad(dxm_c, o_w, out=g[5], split=sp_attn, tail=tail, reduce_on=rbw))
             if need_attn:
                 do = ops.linear_dgrad(dxm_c, Wproj, out_dtype=T)
-                dqkv = ops.sdpa_bwd(qkv, o, do, lse, B, H, N, dbias=g[4], causal=causal,
-                                    reduce_on=rb)
+                if spread_sums:  # the attention backward takes the dense dO: zero but for the class rows
+                    do = ops.pad_cols(do.view(B, P * D)[:, :D], N * D).view(M, D)
+                dqkv = ops.sdpa_bwd(qkv, o, do, lse, B, H, N, dbias=g[4], causal=causal, reduce_on=rb)
                 if pair_attn:
                     side.run(lambda: ops.linear_wgrad_pair((dxm_c, o, g[5]), (dqkv, h1, g[3]), rbw, tail=tail))
                 elif ng[3]:
-                    side.run(lambda: ops.linear_wgrad(dqkv, h1, out=g[3], tail=tail, reduce_on=rbw))
+                    side.run(lambda: ops.linear_wgrad(dqkv, h1, out=g[3], split=sp_attn, tail=tail, reduce_on=rbw))
             if need_h1:
                 dh1 = ops.linear_dgrad(dqkv, Wqkv, out_dtype=T)
                 dx = torch.empty(M, D, dtype=torch.float32, device=dev)
@@ -531,15 +653,17 @@ class _BlockFn(torch.autograd.Function):
                     dx_c = None if T == torch.float32 or not ng[0] else torch.empty(M, D, dtype=T, device=dev)
                 # column sums of dx = the upstream block's fc2.bias gradient (not needed below the first block)
                 dsum = None if (compact_np or not ng[0]) else torch.empty(D, dtype=torch.float32, device=dev)
-                ops.layer_norm_bwd(x2, D, dh1, n1w.detach(), m1, r1, dx, D, M, dres=dxm, ldres=D, dx_copy=dx_c,
-                                   ld_copy=D, compact_np=compact_np, dgamma=g[1], dbeta=g[2], dsum=dsum,
-                                   reduce_on=rb)
+                # (padded tail: the class rows of dxm, P rows apart, are added to every N-th row)
+                dres = dxm.view(B, P * D)[:, :D] if spread_sums else dxm
+                ops.layer_norm_bwd(x2, D, dh1, n1w.detach(), m1, r1, dx, D, M, dres=dres, ldres=dres.stride(0),
+                                   dx_copy=dx_c, ld_copy=D, compact_np=compact_np, dgamma=g[1], dbeta=g[2], dsum=dsum,
+                                   reduce_on=rb, res_every=N if spread_sums else 0)
                 if ng[0] and (dx_c is not None or dsum is not None):
                     _put_copy(dx, dx_c, dsum)
         side.run(rb.launch)
         side.guard(*rb.parts)
         side.guard(dxo, dxo_c, dxo_sum, x2, h1, m1, r1, qkv, o, lse, xm, h2, m2, r2, dact, act,
-                   *(v for v in (dpre, dxm, dxm_c, do, dqkv, dx) if v is not None))
+                   *(v for v in (dpre, dxm, dxm_c, do, dqkv, dx) if v is not None), *pads)
         if cfg_defer_bwd(ctx):
             _queue_backward_join(dev)
         # (not the gradients g: they alias the persistent flat buffer, and AccumulateGrad must be
@@ -574,10 +698,15 @@ class _HeadFn(torch.autograd.Function):
         dxc = ops.linear_dgrad(dlogits, hw.detach(), out_dtype=torch.float32)
         dhw = ops.linear_wgrad(dlogits, xc, out=_gout(hw))
         dhb = ops.colsum(dlogits, out=_gout(hb))
-        dx = ops.zero_(torch.empty(B, N, D, dtype=torch.float32, device=x.device))
+        # N == 1 (the last block ran as the class-token tail): the LayerNorm backward writes every row
+        dx = torch.empty(B, N, D, dtype=torch.float32, device=x.device)
+        if N > 1:
+            ops.zero_(dx)
         dx_c = None
         if T != torch.float32:
-            dx_c = ops.zero_(torch.empty(B * N, D, dtype=T, device=x.device))
+            dx_c = torch.empty(B * N, D, dtype=T, device=x.device)
+            if N > 1:
+                ops.zero_(dx_c)
         dnw, dnb = _gout(nw), _gout(nb)
         dsum = torch.empty(D, dtype=torch.float32, device=x.device)  # last block's fc2.bias gradient
         ops.layer_norm_bwd(x, N * D, dxc, nw.detach(), mc, rc, dx, N * D, B, dx_copy=dx_c, ld_copy=N * D,
@@ -763,7 +892,9 @@ class VisionTransformer(nn.Module):
         return list(self._shadows.pairs)
 
     # -- timm surface ----------------------------------------------------------------
-    def _tokens(self, x):
+    def _tokens(self, x, cls_only=False):
+        """The block stack's output [B, N, D]; ``cls_only`` (forward(): only the class rows are read) lets
+        the last block run as the class-token tail and return [B, 1, D]."""
         L.require_gpu(x)
         self._ensure_shadows()
         cfg = dict(self._cfg)
@@ -793,6 +924,8 @@ class VisionTransformer(nn.Module):
             bcfg = cfg if i != 0 else dict(cfg, compact_np=pe.num_patches)
             if "resid" in cfg and i == n - 1:
                 bcfg = dict(bcfg, resid_last=True)
+            if i == n - 1 and wants_cls_tail(_CLS_TAIL[0], cls_only, self.global_pool, cfg["attn_fp8"]):
+                bcfg = dict(bcfg, cls_tail=True)
             if hook is not None:
                 bcfg = dict(bcfg, grad_hook=hook, flat_span=blk._flat_span)
             x = run_block(x, blk.block_params(), bcfg)
@@ -815,7 +948,7 @@ class VisionTransformer(nn.Module):
                                                    self.head.bias.detach(), out_dtype=torch.float32)
 
     def forward(self, x):
-        x = self._tokens(x)
+        x = self._tokens(x, cls_only=True)
         return _HeadFn.apply(x, self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, dict(self._cfg))
 
 

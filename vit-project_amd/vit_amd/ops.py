@@ -106,12 +106,70 @@ def linear_fwd(x2d, w, bias=None, epi=L.EPI_STORE, out=None, out_dtype=None, res
     return (out, act_out) if epi in (L.EPI_BIAS_GELU, L.EPI_BIAS_QGELU) else out
 
 
-def linear_dgrad(dy2d, w, out_dtype=torch.float32, epi=L.EPI_STORE, pre=None, out=None, dbias=None, reduce_on=None):
+# rows per column-sum partial of the input-gradient epilogues (gemm.hip / gemm_g4.hip: one partial row per
+# 64-row group, vit_linear_dgrad_partial_floats) and rows per k-tile of the weight-gradient kernels (big::PP::BK)
+DGRAD_SUM_ROWS = 64
+WGRAD_KTILE_ROWS = 32
+_LN_ROWS = []
+_PART_ROWS = {}
+
+
+def ln_bwd_rows_per() -> int:
+    """Rows per partial block of the LayerNorm backward (VIT_LN_BWD_ROWS, read by the library), recovered from
+    vit_layer_norm_bwd_blocks: the largest row count that is still one block."""
+    if not _LN_ROWS:
+        blocks = L.lib().vit_layer_norm_bwd_blocks
+        r = 1
+        while r < (1 << 16) and blocks(r + 1) == 1:
+            r += 1
+        _LN_ROWS.append(r)
+    return _LN_ROWS[0]
+
+
+class PartRows:
+    """Where the partial rows of a row-padded launch go in the dense launch's [S][N] partial matrix: the
+    launch has n * every partial rows, of which row every * i (image i's, the others are zero rows' sums)
+    becomes row rows[i].  Checked on the host: rows distinct and inside the matrix."""
+
+    def __init__(self, rows, S, every, device):
+        rows = [int(r) for r in rows]
+        if not rows or min(rows) < 0 or max(rows) >= S or len(set(rows)) != len(rows) or every < 1:
+            raise ValueError(f"partial rows {rows[:4]}.. do not fit a dense partial matrix of {S} rows one to one")
+        self.n, self.S, self.every = len(rows), int(S), int(every)
+        self.idx = torch.tensor(rows, dtype=torch.int64, device=device)
+
+
+def dense_part_rows(B, N, unit, every, device):
+    """PartRows of a launch over B images padded to ``every * unit`` rows each, against the dense launch over
+    B * N rows: image b's class row b * N lies in the dense launch's partial row b * N // unit.  Cached: it
+    depends on the shapes alone."""
+    key = (B, N, unit, every, torch.device(device))
+    if key not in _PART_ROWS:
+        _PART_ROWS[key] = PartRows([b * N // unit for b in range(B)], (B * N + unit - 1) // unit, every, device)
+    return _PART_ROWS[key]
+
+
+def spread_partials(part2d, pr):
+    """[S][N] f32, zero but for row pr.idx[i] = row pr.every * i of part2d ([n * every][N]): partial sums of a
+    row-padded launch laid out as the dense launch's partial rows, so that a ColBatch job reduces them in the
+    dense launch's order."""
+    rows, N = part2d.shape
+    assert part2d.is_contiguous() and part2d.dtype == torch.float32
+    assert rows == pr.n * pr.every and pr.idx.numel() == pr.n and pr.idx.device == part2d.device, (rows, pr.n, pr.every)
+    out = zero_(torch.empty(pr.S * N, dtype=torch.float32, device=part2d.device))
+    scatter_rows(part2d.view(pr.n, pr.every * N)[:, :N], pr.idx, out.view(pr.S, N))
+    return out
+
+
+def linear_dgrad(dy2d, w, out_dtype=torch.float32, epi=L.EPI_STORE, pre=None, out=None, dbias=None, reduce_on=None,
+                 part_rows=None):
     """dx = dy @ w  (dy [M,N], w [N,K]); with EPI_GELU_BWD / EPI_QGELU_BWD times ``pre`` [M,K] =
     the act'(pre) the forward's BIAS_GELU epilogue saved;
     dbias [K] (optional) receives the column sums of dx (fused into the GEMM epilogue).
     ``reduce_on`` (an object with ``.run(fn)``, e.g. the model's side stream): the final
-    reduction of those column sums is issued through it instead of inline."""
+    reduction of those column sums is issued through it instead of inline.
+    ``part_rows`` (a PartRows, with a ColBatch): the partial rows are laid out as a dense launch's before
+    they are reduced (:func:`spread_partials`)."""
     M, N = dy2d.shape
     K = w.shape[1]
     assert w.shape[0] == N and w.dtype == dy2d.dtype and dy2d.stride(1) == 1
@@ -132,8 +190,10 @@ def linear_dgrad(dy2d, w, out_dtype=torch.float32, epi=L.EPI_STORE, pre=None, ou
     call("vit_linear_dgrad", L.dt(dy2d), L.dt(out), epi, M, N, K, ptr(dy2d), dy2d.stride(0), ptr(w), ptr(out),
          out.stride(0), ptr(pre), ptr(dbias), ptr(part), nfl, int(defer), _s(dy2d))
     if defer:
-        rows = (M + 63) // 64
+        rows = (M + DGRAD_SUM_ROWS - 1) // DGRAD_SUM_ROWS
         if isinstance(reduce_on, ColBatch):
+            if part_rows is not None:
+                part, rows = spread_partials(part[:rows * K].view(rows, K), part_rows), part_rows.S
             reduce_on.add(part, rows, K, dbias)
             return out
 
@@ -253,7 +313,15 @@ def linear_wgrad(dy2d, x2d, out=None, split=None, tail=False, reduce_on=None):
     return out
 
 
-def linear_wgrad_pair(a, b, reduce_on, tail=False):
+def pair_split(M, Na, Ka, Nb, Kb, tail=False):
+    """The split-K factor :func:`linear_wgrad_pair` chooses for a pair over M rows."""
+    tiles = ((Na + 255) // 256) * ((Ka + 255) // 256) + ((Nb + 255) // 256) * ((Kb + 255) // 256)
+    wgs = _WGRAD_TAIL_WGS[0] if tail else _WGRAD_WGS[0]
+    return max(1, min(max(1, round(wgs / tiles)), M // 1024))
+
+
+def linear_wgrad_pair(a, b, reduce_on, tail=False, split=None):
+    asked = split  # (the fallback launches choose their own split unless the caller fixed one)
     """Two weight gradients of a block over the same token rows, a = (dy, x, out), b likewise, as
     ONE grouped launch of split-K partials whose slab sums become two jobs of ``reduce_on`` (a
     ColBatch).  The split is chosen for the pair's tiles together (half the slabs of two separate
@@ -265,9 +333,8 @@ def linear_wgrad_pair(a, b, reduce_on, tail=False):
     ok = (isinstance(reduce_on, ColBatch) and dya.dtype == torch.bfloat16 and dyb.dtype == torch.bfloat16
           and xa.dtype == dya.dtype and xb.dtype == dyb.dtype and dyb.shape[0] == M and M % 32 == 0)
     if ok:
-        tiles = ((Na + 255) // 256) * ((Ka + 255) // 256) + ((Nb + 255) // 256) * ((Kb + 255) // 256)
-        wgs = _WGRAD_TAIL_WGS[0] if tail else _WGRAD_WGS[0]
-        split = max(1, min(max(1, round(wgs / tiles)), M // 1024))
+        if split is None:
+            split = pair_split(M, Na, Ka, Nb, Kb, tail)
         nz = L.lib().vit_linear_wgrad_nslabs(L.BF16, M, Na, Ka, split)
         sa = torch.empty(nz * Na * Ka, dtype=torch.float32, device=dya.device)
         sb = torch.empty(nz * Nb * Kb, dtype=torch.float32, device=dya.device)
@@ -288,8 +355,8 @@ def linear_wgrad_pair(a, b, reduce_on, tail=False):
             reduce_on.add(sa.view(nz, Na * Ka), nz, Na * Ka, outa)
             reduce_on.add(sb.view(nz, Nb * Kb), nz, Nb * Kb, outb)
             return outa, outb
-    linear_wgrad(dya, xa, out=outa, tail=tail, reduce_on=reduce_on)
-    linear_wgrad(dyb, xb, out=outb, tail=tail, reduce_on=reduce_on)
+    linear_wgrad(dya, xa, out=outa, split=asked, tail=tail, reduce_on=reduce_on)
+    linear_wgrad(dyb, xb, out=outb, split=asked, tail=tail, reduce_on=reduce_on)
     return outa, outb
 
 
@@ -350,8 +417,11 @@ def add_layer_norm_fwd(x2d, r2d, xs, w=None, b=None, eps=1e-6, out=None, mean=No
 
 
 def layer_norm_bwd(x, ldx, dy, w, mean, rstd, dx, lddx, rows, dres=None, ldres=0, dx_copy=None, ld_copy=0,
-                   compact_np=0, dgamma=None, dbeta=None, dsum=None, ws="ln_partial", reduce_on=None):
+                   compact_np=0, dgamma=None, dbeta=None, dsum=None, ws="ln_partial", reduce_on=None, res_every=0,
+                   part_rows=None):
     """dsum [D] (optional) receives the column sums of dx (a Linear bias gradient).
+    ``res_every`` > 0: ``dres`` is compact, one row per ``res_every`` rows of dx, added to rows 0, res_every,
+    ... alone (the class-token rows' gradient; vit_layer_norm_bwd_cls).
     ``reduce_on`` (an object with ``.run(fn)``): the dgamma / dbeta / dsum reductions of the
     per-64-row partials are issued through it (e.g. on the side stream) instead of inline."""
     D = w.numel()
@@ -363,16 +433,26 @@ def layer_norm_bwd(x, ldx, dy, w, mean, rstd, dx, lddx, rows, dres=None, ldres=0
         nfl = L.lib().vit_layer_norm_bwd_partial_floats(rows, D)
         part = (torch.empty(nfl, dtype=torch.float32, device=x.device) if defer
                 else workspace(ws, nfl * 4, x.device))
-    call("vit_layer_norm_bwd", L.dt(x), L.dt(dy), rows, D, ptr(x), ldx, ptr(dy), dy.stride(0), ptr(w), ptr(mean),
-         ptr(rstd), ptr(dres), ldres, ptr(dx), lddx, ptr(dx_copy), ld_copy,
-         L.dt(dx_copy) if dx_copy is not None else L.BF16, compact_np, ptr(dgamma), ptr(dbeta), ptr(dsum), ptr(part),
-         nfl, int(defer), _s(x))
+    tail = (ptr(dx), lddx, ptr(dx_copy), ld_copy, L.dt(dx_copy) if dx_copy is not None else L.BF16, compact_np,
+            ptr(dgamma), ptr(dbeta), ptr(dsum), ptr(part), nfl, int(defer), _s(x))
+    head = (L.dt(x), L.dt(dy), rows, D, ptr(x), ldx, ptr(dy), dy.stride(0), ptr(w), ptr(mean), ptr(rstd), ptr(dres),
+            ldres)
+    if res_every:
+        assert dres is not None and dres.dtype == torch.float32 and dres.shape[0] * res_every >= rows
+        call("vit_layer_norm_bwd_cls", *head, int(res_every), *tail)
+    else:
+        call("vit_layer_norm_bwd", *head, *tail)
     if defer:
         nb = L.lib().vit_layer_norm_bwd_blocks(rows)
         if isinstance(reduce_on, ColBatch):
             for q, o in enumerate((dgamma, dbeta, dsum)):
-                if o is not None:
-                    reduce_on.add(part[q * nb * D:(q + 1) * nb * D], nb, D, o)
+                if o is None:
+                    continue
+                pq = part[q * nb * D:(q + 1) * nb * D]
+                if part_rows is not None:  # a PartRows: laid out as the dense launch's partial blocks
+                    reduce_on.add(spread_partials(pq.view(nb, D), part_rows), part_rows.S, D, o)
+                else:
+                    reduce_on.add(pq, nb, D, o)
             return
         sc = part[3 * nb * D:]
 
@@ -420,6 +500,21 @@ def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=Fal
     return o, lse
 
 
+def sdpa_fwd_cls(qkv2d, B, H, N, o=None, scale=None, lse=None):
+    """:func:`sdpa_fwd` for a caller that reads query 0 of every (b, h) alone (the class-token tail): bf16 up to
+    288 tokens runs query tile 0 of the resident kernel -- rows 0..15 of each image bit for bit sdpa_fwd's, the
+    other rows o = 0 and lse = +inf; anything else runs sdpa_fwd (all rows)."""
+    D = H * 64
+    if o is None:
+        o = torch.empty(B * N, D, dtype=qkv2d.dtype, device=qkv2d.device)
+    if lse is None:
+        lse = torch.empty(B * H * N, dtype=torch.float32, device=qkv2d.device)
+    scale = 64 ** -0.5 if scale is None else scale
+    call("vit_sdpa_fwd_cls", L.dt(qkv2d), B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(o), o.stride(0), ptr(lse),
+         float(scale), _s(qkv2d))
+    return o, lse
+
+
 def sdpa_bwd(qkv2d, o, do, lse, B, H, N, dqkv=None, scale=None, dbias=None, causal=False, ws="", reduce_on=None):
     """dbias [3*H*64] (optional) receives the column sums of dqkv (the qkv bias gradient).
     ``ws``: workspace-name suffix (calls running concurrently on different streams need their own).
@@ -460,11 +555,14 @@ def patch_unfold(img, ps, dtype, ld=None):
     return U
 
 
-def pad_cols(w2d, ld):
-    """[rows, cols] -> [rows, ld] with columns [cols, ld) zero (vit_copy_rows_padded)."""
+def pad_cols(w2d, ld, out=None):
+    """[rows, cols] -> [rows, ld] with columns [cols, ld) zero (vit_copy_rows_padded); rows of any stride
+    (ld == cols gathers strided rows, e.g. each image's class-token row, into a compact tensor)."""
     rows, cols = w2d.shape
     assert w2d.stride(1) == 1 and ld >= cols
-    out = torch.empty(rows, ld, dtype=w2d.dtype, device=w2d.device)
+    if out is None:
+        out = torch.empty(rows, ld, dtype=w2d.dtype, device=w2d.device)
+    assert out.shape == (rows, ld) and out.is_contiguous() and out.dtype == w2d.dtype
     call("vit_copy_rows_padded", L.dt(w2d), rows, cols, ptr(w2d), w2d.stride(0), ptr(out), ld, _s(w2d))
     return out
 

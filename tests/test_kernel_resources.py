@@ -2,8 +2,8 @@
 
 - the inline-asm wide-wave GEMM kernels (csrc/gemm_w4.inc): no scratch, and no instruction touches an asm
   LDS read's destination before the next lgkmcnt(0) wait (tools/w4_audit.py);
-- every instantiation of the fused attention backward (its phase-1 query loop is fully
-  unrolled): no VGPR spill, no scratch.
+- every attention kernel (the fused backward's phase-1 query loop is fully unrolled; the
+  resident and streamed kernels share their tile steps as inlined functions): no VGPR spill, no scratch.
 
 Skipped when the objects are not built (``make -C vit-project_amd/csrc``).
 """
@@ -32,9 +32,9 @@ def test_w4_kernels_pass_the_asm_audit():
     assert w4_audit.audit(text, r"w4") == 0
 
 
-def test_attention_backward_has_no_spills():
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kres.sh"), _need("attention.o"), "attn_bwd"],
+def test_attention_backward_has_no_spills():  # every attn_ kernel since round 12; the name is kept
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kres.sh"), _need("attention.o"), "attn_"],
                          capture_output=True, text=True, check=True).stdout.splitlines()
-    assert out, "no attn_bwd kernels found"
+    assert out, "no attn_ kernels found"
     bad = [l for l in out if " spill 0 " not in l or " priv 0 " not in l]
     assert not bad, bad[:5]

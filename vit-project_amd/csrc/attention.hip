@@ -521,6 +521,119 @@ __device__ __forceinline__ void bias_flush_c(const float (&own)[NOUT], char* sme
 }
 
 // ---------------------------------------------------------------------------
+// Pieces of the bf16 backward shared by the resident kernels (attn_bwd_dq, attn_bwd_dkv: whole-head
+// images) and the streamed ones (attn_bwd_dq_stream, attn_bwd_dkv_stream: 64-row chunk images).  A tile
+// is named twice: row0, its first row inside the LDS image, and key0 / q0, its absolute index (the same
+// for a resident image, j0 + row0 for a chunk).
+// ---------------------------------------------------------------------------
+// Query row q of one head (clamped to N - 1): the q and dO fragments, delta = rowsum(dO * O) (written for
+// the dkv kernel) and lse * log2(e).  base / dob / ob: the head's q, dO, O columns of row 0.
+__device__ __forceinline__ void at_qrow(const bf16* base, int64_t ld_qkv, const bf16* dob, int64_t ld_do,
+                                        const bf16* ob, int64_t ld_o, const float* lse_bh, float* delta_bh, int q,
+                                        int N, int g, bf16x8 (&qf)[2], bf16x8 (&of)[2], float& dl, float& l2) {
+  const int qc = min(q, N - 1);
+  dl = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    qf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)qc * ld_qkv + kk * 32 + g * 8);
+    of[kk] = *reinterpret_cast<const bf16x8*>(dob + (int64_t)qc * ld_do + kk * 32 + g * 8);
+    const bf16x8 ov = *reinterpret_cast<const bf16x8*>(ob + (int64_t)qc * ld_o + kk * 32 + g * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dl = fmaf((float)of[kk][e], (float)ov[e], dl);
+  }
+  dl += __shfl_xor(dl, 16, 64);
+  dl += __shfl_xor(dl, 32, 64);
+  l2 = lse_bh[qc] * LOG2E;
+  if (g == 0 && q < N) delta_bh[q] = dl;
+}
+// Key row kc of one head: the k and v fragments.
+__device__ __forceinline__ void at_krow(const bf16* base, int64_t ld_qkv, int D, int kc, int g, bf16x8 (&kf)[2],
+                                        bf16x8 (&vf)[2]) {
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    kf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)kc * ld_qkv + D + kk * 32 + g * 8);
+    vf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)kc * ld_qkv + 2 * D + kk * 32 + g * 8);
+  }
+}
+// A 16-row fragment set x[dt][t] (this lane: columns dt*16 + 4g + t of its row) as bf16 to the row at p.
+__device__ __forceinline__ void at_store_row(bf16* p, const f32x4 (&x)[4], int g) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+    *reinterpret_cast<bf16x4*>(p + dt * 16 + 4 * g) =
+        bf16x4{(bf16)x[dt][0], (bf16)x[dt][1], (bf16)x[dt][2], (bf16)x[dt][3]};
+}
+// dk (already scaled) and dv of one key row; row = the key's dq column of this head.
+__device__ __forceinline__ void at_store_dkv(bf16* row, int D, const f32x4 (&dk)[4], const f32x4 (&dv)[4], int g) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    bf16x4 kv = {(bf16)dk[dt][0], (bf16)dk[dt][1], (bf16)dk[dt][2], (bf16)dk[dt][3]};
+    bf16x4 vv = {(bf16)dv[dt][0], (bf16)dv[dt][1], (bf16)dv[dt][2], (bf16)dv[dt][3]};
+    *reinterpret_cast<bf16x4*>(row + D + dt * 16 + 4 * g) = kv;
+    *reinterpret_cast<bf16x4*>(row + 2 * D + dt * 16 + 4 * g) = vv;
+  }
+}
+// dq half, one pair of key tiles (32 keys): S^T and dP^T of the lane's query against the K / V images,
+// p = exp2(c2 S - l2) (0 on keys >= N and, causal, on keys > q), dS = p (dP - dl), dQ += dS K.
+// edge: the caller's wave-uniform "this pair (chunk) may hold keys >= N".
+__device__ __forceinline__ void at_dq_step(const char* Kimg, const char* Vimg, int row0, int key0, int N, bool edge,
+                                           const AtOffsets& off, int g, const bf16x8 (&qf)[2], const bf16x8 (&of)[2],
+                                           float c2, float l2, float dl, int q, int causal, f32x4 (&dq)[4]) {
+  f32x4 ds[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      sacc = mfma16(rowf(Kimg, row0 + u * 16, off.row[kk]), qf[kk], sacc);
+      dpacc = mfma16(rowf(Vimg, row0 + u * 16, off.row[kk]), of[kk], dpacc);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = key0 + u * 16 + 4 * g + r;
+      float pv = fexp2(fmaf(sacc[r], c2, -l2));
+      if (edge && key >= N) pv = 0.f;
+      if (causal && key > q) pv = 0.f;
+      ds[u][r] = pv * (dpacc[r] - dl);
+    }
+  }
+  const bf16x8 dsf = pack8(ds[0], ds[1]);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma16(trf(Kimg, row0, off.tr[dt]), dsf, dq[dt]);
+}
+// dkv half, one pair of query tiles (32 queries): S and dP of the lane's key against the Q / dO images,
+// row constants from the lse * log2(e) / delta strips (indexed like the image), dV += P^T dO, dK += dS^T Q.
+__device__ __forceinline__ void at_dkv_step(const char* Qimg, const char* Oimg, const float* lse2, const float* delta,
+                                            int row0, int q0, const AtOffsets& off, int g, const bf16x8 (&kf)[2],
+                                            const bf16x8 (&vf)[2], float c2, bool kvalid, int key, int causal,
+                                            f32x4 (&dk)[4], f32x4 (&dv)[4]) {
+  f32x4 p[2], ds[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      sacc = mfma16(rowf(Qimg, row0 + u * 16, off.row[kk]), kf[kk], sacc);
+      dpacc = mfma16(rowf(Oimg, row0 + u * 16, off.row[kk]), vf[kk], dpacc);
+    }
+    const f32x4 l2 = *reinterpret_cast<const f32x4*>(lse2 + row0 + u * 16 + 4 * g);
+    const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + row0 + u * 16 + 4 * g);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float pv = kvalid ? fexp2(fmaf(sacc[r], c2, -l2[r])) : 0.f;
+      if (causal && key > q0 + u * 16 + 4 * g + r) pv = 0.f;
+      p[u][r] = pv;
+      ds[u][r] = pv * (dpacc[r] - dl[r]);
+    }
+  }
+  const bf16x8 pf = pack8(p[0], p[1]), dsf = pack8(ds[0], ds[1]);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    dv[dt] = mfma16(trf(Oimg, row0, off.tr[dt]), pf, dv[dt]);
+    dk[dt] = mfma16(trf(Qimg, row0, off.tr[dt]), dsf, dk[dt]);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // bf16 backward, two kernels per (b, h) so each holds only half the head in LDS
 // (57 KiB -> two workgroups per CU); N > 224 (CLIP ViT-L/14's 257 tokens), else attn_bwd_fused:
 //   attn_bwd_dq  : LDS K, V; each wave owns query tiles (Q, dO, O from global),
@@ -557,58 +670,23 @@ __global__ __launch_bounds__(AT_THREADS, 4) void attn_bwd_dq(const bf16* __restr
   for (int dt = 0; dt < 4; ++dt) cs[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int qt = wave; qt < NT; qt += AT_WAVES) {
     const int q = qt * 16 + (lane & 15);
-    const int qc = min(q, N - 1);
     bf16x8 qf[2], of[2];
-    float dl = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      qf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)qc * ld_qkv + kk * 32 + g * 8);
-      of[kk] = *reinterpret_cast<const bf16x8*>(dout + ((int64_t)b * N + qc) * ld_do + h * 64 + kk * 32 + g * 8);
-      const bf16x8 ov = *reinterpret_cast<const bf16x8*>(o + ((int64_t)b * N + qc) * ld_o + h * 64 + kk * 32 + g * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) dl = fmaf((float)of[kk][e], (float)ov[e], dl);
-    }
-    dl += __shfl_xor(dl, 16, 64);
-    dl += __shfl_xor(dl, 32, 64);
-    const float l2 = lse[(int64_t)bh * N + qc] * LOG2E;
-    if (g == 0 && q < N) delta_out[(int64_t)bh * N + q] = dl;
+    float dl, l2;
+    at_qrow(base, ld_qkv, dout + (int64_t)b * N * ld_do + h * 64, ld_do, o + (int64_t)b * N * ld_o + h * 64, ld_o,
+            lse + (int64_t)bh * N, delta_out + (int64_t)bh * N, q, N, g, qf, of, dl, l2);
     f32x4 dq[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
-    for (int kp = 0; kp < NT2; ++kp) {
-      f32x4 ds[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int kt = 2 * kp + u;
-        f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          sacc = mfma16(rowf(Kimg, kt * 16, off.row[kk]), qf[kk], sacc);
-          dpacc = mfma16(rowf(Vimg, kt * 16, off.row[kk]), of[kk], dpacc);
-        }
-        const bool edge = (kt + 1) * 16 > N;  // wave-uniform: only the last tiles hold padded keys
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float pv = fexp2(fmaf(sacc[r], c2, -l2));
-          if (edge && kt * 16 + 4 * g + r >= N) pv = 0.f;
-          if (causal && kt * 16 + 4 * g + r > q) pv = 0.f;
-          ds[u][r] = pv * (dpacc[r] - dl);
-        }
-      }
-      const bf16x8 dsf = pack8(ds[0], ds[1]);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma16(trf(Kimg, kp * 32, off.tr[dt]), dsf, dq[dt]);
-    }
+    for (int kp = 0; kp < NT2; ++kp)  // edge, wave-uniform: only the last pair holds padded keys
+      at_dq_step(Kimg, Vimg, kp * 32, kp * 32, N, (kp + 1) * 32 > N, off, g, qf, of, c2, l2, dl, q, causal, dq);
     if (q < N) {
-      bf16* row = dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        bf16x4 qv = {(bf16)(dq[dt][0] * scale), (bf16)(dq[dt][1] * scale), (bf16)(dq[dt][2] * scale),
-                     (bf16)(dq[dt][3] * scale)};
-        *reinterpret_cast<bf16x4*>(row + dt * 16 + 4 * g) = qv;
-        cs[dt] += dq[dt] * scale;
+        dq[dt] *= scale;
+        cs[dt] += dq[dt];
       }
+      at_store_row(dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64, dq, g);
     }
   }
   if (bias_part) bias_flush<1>(cs, nullptr, smem, bias_part + (int64_t)b * 3 * D + h * 64, D);
@@ -648,60 +726,20 @@ __global__ __launch_bounds__(AT_THREADS, 4) void attn_bwd_dkv(const bf16* __rest
   for (int kt = wave; kt < NT; kt += AT_WAVES) {
     const int key = kt * 16 + (lane & 15);
     const bool kvalid = key < N;
-    const int kc = min(key, N - 1);
     bf16x8 kf[2], vf[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      kf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)kc * ld_qkv + D + kk * 32 + g * 8);
-      vf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)kc * ld_qkv + 2 * D + kk * 32 + g * 8);
-    }
+    at_krow(base, ld_qkv, D, min(key, N - 1), g, kf, vf);
     f32x4 dv[4], dk[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) { dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[dt] = dv[dt]; }
 #pragma unroll 1  // unroll 2 spills ~300 VGPRs at the 128-register budget
-    for (int qp = 0; qp < NT2; ++qp) {
-      f32x4 p[2], ds[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int qt = 2 * qp + u;
-        f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          sacc = mfma16(rowf(Qimg, qt * 16, off.row[kk]), kf[kk], sacc);
-          dpacc = mfma16(rowf(Oimg, qt * 16, off.row[kk]), vf[kk], dpacc);
-        }
-        const f32x4 l2 = *reinterpret_cast<const f32x4*>(lse2 + qt * 16 + 4 * g);
-        const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + qt * 16 + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float pv = kvalid ? fexp2(fmaf(sacc[r], c2, -l2[r])) : 0.f;
-          if (causal && key > qt * 16 + 4 * g + r) pv = 0.f;
-          p[u][r] = pv;
-          ds[u][r] = pv * (dpacc[r] - dl[r]);
-        }
-      }
-      const bf16x8 pf = pack8(p[0], p[1]), dsf = pack8(ds[0], ds[1]);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        dv[dt] = mfma16(trf(Oimg, qp * 32, off.tr[dt]), pf, dv[dt]);
-        dk[dt] = mfma16(trf(Qimg, qp * 32, off.tr[dt]), dsf, dk[dt]);
-      }
-    }
+    for (int qp = 0; qp < NT2; ++qp)
+      at_dkv_step(Qimg, Oimg, lse2, delta, qp * 32, qp * 32, off, g, kf, vf, c2, kvalid, key, causal, dk, dv);
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       dk[dt] = kvalid ? dk[dt] * scale : f32x4{0.f, 0.f, 0.f, 0.f};
       if (!kvalid) dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    if (kvalid) {
-      bf16* row = dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        bf16x4 kv = {(bf16)dk[dt][0], (bf16)dk[dt][1], (bf16)dk[dt][2], (bf16)dk[dt][3]};
-        bf16x4 vv = {(bf16)dv[dt][0], (bf16)dv[dt][1], (bf16)dv[dt][2], (bf16)dv[dt][3]};
-        *reinterpret_cast<bf16x4*>(row + D + dt * 16 + 4 * g) = kv;
-        *reinterpret_cast<bf16x4*>(row + 2 * D + dt * 16 + 4 * g) = vv;
-      }
-    }
+    if (kvalid) at_store_dkv(dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64, D, dk, dv, g);
     if (bias_part) {  // wave-uniform
       cs[0] += colsum16(dk, lane);
       cs[1] += colsum16(dv, lane);
@@ -957,6 +995,59 @@ __device__ __forceinline__ int kswz(int r) {
   return x ^ ((((x >> 2) ^ (x >> 3)) & 1) << 2);
 }
 
+// Rows [0, rows) of a head slice into a swizzled image (rows >= N zero).
+__device__ __forceinline__ void f32_img_load(float* img, const float* src, int64_t ld, int N, int rows, int tid,
+                                             int nthr) {
+  for (int i = tid; i < rows * 16; i += nthr) {
+    const int r = i >> 4, c = i & 15;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (r < N) v = *reinterpret_cast<const f32x4*>(src + (int64_t)r * ld + c * 4);
+    *reinterpret_cast<f32x4*>(img + r * 64 + ((c ^ kswz(r)) << 2)) = v;
+  }
+}
+// row r of a swizzled image: the 16 floats [16g, 16g + 16) (4 chunks)
+__device__ __forceinline__ void f32_row16(const float* img, int r, int g, float (&x)[16]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(img + r * 64 + (((4 * g + j) ^ kswz(r)) << 2));
+    x[4 * j] = v[0]; x[4 * j + 1] = v[1]; x[4 * j + 2] = v[2]; x[4 * j + 3] = v[3];
+  }
+}
+// chunk c of row r; SWZ = false: a plain row-major image (the resident forward's V)
+template <bool SWZ = true>
+__device__ __forceinline__ f32x4 f32_chunk(const float* img, int r, int c) {
+  return *reinterpret_cast<const f32x4*>(img + r * 64 + ((SWZ ? c ^ kswz(r) : c) << 2));
+}
+__device__ __forceinline__ void f32_glob16(const float* p, float (&x)[16]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p + 4 * j);
+    x[4 * j] = v[0]; x[4 * j + 1] = v[1]; x[4 * j + 2] = v[2]; x[4 * j + 3] = v[3];
+  }
+}
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+// x[dt][rr] * mul = element 4 rr + dt of the lane's 16 floats at p (the O^T / dQ^T / dK^T / dV^T accumulators:
+// row m of d-tile dt is head dim 4m + dt); mul = 1.f folds away.
+__device__ __forceinline__ void f32_store_row(float* p, const f32x4 (&x)[4], float mul) {
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr)
+    *reinterpret_cast<f32x4*>(p + 4 * rr) = f32x4{x[0][rr] * mul, x[1][rr] * mul, x[2][rr] * mul, x[3][rr] * mul};
+}
+// dk * scale and dv of one key row; row = the lane's 16 floats of the key's dq column.
+__device__ __forceinline__ void f32_store_dkv(float* row, int D, const f32x4 (&dk)[4], const f32x4 (&dv)[4],
+                                              float scale) {
+  f32_store_row(row + D, dk, scale);
+  f32_store_row(row + 2 * D, dv, 1.f);
+}
+// o = oacc / l and lse[at] = (mc + log2 l) ln 2 of one query (mc = max * c2, l = the row sum); lse may be null.
+__device__ __forceinline__ void f32_store_o(float* orow, float* lse, int64_t at, const f32x4 (&oacc)[4], float l,
+                                            float mc, int g) {
+  f32_store_row(orow, oacc, 1.0f / l);
+  if (g == 0 && lse) lse[at] = (mc + __log2f(l)) * LN2;
+}
+
 template <int NT>
 __global__ __launch_bounds__(512) void attn_fwd_f32mfma(const float* __restrict__ qkv, int64_t ld_qkv, int D, int H,
                                                         int N, float scale, float* __restrict__ o, int64_t ld_o,
@@ -968,7 +1059,8 @@ __global__ __launch_bounds__(512) void attn_fwd_f32mfma(const float* __restrict_
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
   const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
-  // K, V -> LDS (rows >= N zero)
+  // K, V -> LDS (rows >= N zero) in one loop, both loads of a piece in flight together: two f32_img_load
+  // passes measured 4 % slower at 257 tokens (profiles/r12/README.md)
   for (int i = tid; i < ROWS * 16; i += 512) {
     const int r = i >> 4, c = i & 15;
     f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = kv;
@@ -984,14 +1076,7 @@ __global__ __launch_bounds__(512) void attn_fwd_f32mfma(const float* __restrict_
   for (int qt = wave; qt < NT; qt += 8) {
     const int q = qt * 16 + l15;
     float qf[16];
-    {
-      const float* qr = base + (int64_t)min(q, N - 1) * ld_qkv + 16 * g;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(qr + 4 * j);
-        qf[4 * j] = v[0]; qf[4 * j + 1] = v[1]; qf[4 * j + 2] = v[2]; qf[4 * j + 3] = v[3];
-      }
-    }
+    f32_glob16(base + (int64_t)min(q, N - 1) * ld_qkv + 16 * g, qf);
     f32x4 s[NT];
 #pragma unroll
     for (int k0 = 0; k0 < NT; k0 += KG) {
@@ -999,12 +1084,7 @@ __global__ __launch_bounds__(512) void attn_fwd_f32mfma(const float* __restrict_
 #pragma unroll
       for (int u = 0; u < KG; ++u) {
         if (k0 + u < NT) {
-          const int r = (k0 + u) * 16 + l15;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(Kimg + r * 64 + (((4 * g + j) ^ kswz(r)) << 2));
-            kf[u][4 * j] = v[0]; kf[u][4 * j + 1] = v[1]; kf[u][4 * j + 2] = v[2]; kf[u][4 * j + 3] = v[3];
-          }
+          f32_row16(Kimg, (k0 + u) * 16 + l15, g, kf[u]);
           s[k0 + u] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
       }
@@ -1012,7 +1092,7 @@ __global__ __launch_bounds__(512) void attn_fwd_f32mfma(const float* __restrict_
       for (int ks = 0; ks < 16; ++ks)
 #pragma unroll
         for (int u = 0; u < KG; ++u)
-          if (k0 + u < NT) s[k0 + u] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[u][ks], qf[ks], s[k0 + u], 0, 0, 0);
+          if (k0 + u < NT) s[k0 + u] = mfma4(kf[u][ks], qf[ks], s[k0 + u]);
     }
     // keys >= N exist only in the last tile
 #pragma unroll
@@ -1049,21 +1129,13 @@ __global__ __launch_bounds__(512) void attn_fwd_f32mfma(const float* __restrict_
     for (int kt = 0; kt < NT; ++kt) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(Vimg + (kt * 16 + 4 * g + r) * 64 + 4 * l15);
+        const f32x4 v = f32_chunk<false>(Vimg, kt * 16 + 4 * g + r, l15);
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[dt], s[kt][r], oacc[dt], 0, 0, 0);
+        for (int dt = 0; dt < 4; ++dt) oacc[dt] = mfma4(v[dt], s[kt][r], oacc[dt]);
       }
       if (kt % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // bound V-read hoisting (VGPRs)
     }
-    if (q < N) {
-      const float inv = 1.0f / l;
-      float* orow = o + ((int64_t)b * N + q) * ld_o + h * 64 + 16 * g;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-        *reinterpret_cast<f32x4*>(orow + 4 * rr) =
-            f32x4{oacc[0][rr] * inv, oacc[1][rr] * inv, oacc[2][rr] * inv, oacc[3][rr] * inv};
-      if (g == 0 && lse) lse[(int64_t)bh * N + q] = (mc + __log2f(l)) * LN2;
-    }
+    if (q < N) f32_store_o(o + ((int64_t)b * N + q) * ld_o + h * 64 + 16 * g, lse, (int64_t)bh * N + q, oacc, l, mc, g);
   }
 }
 
@@ -1076,36 +1148,97 @@ __global__ __launch_bounds__(512) void attn_fwd_f32mfma(const float* __restrict_
 //        holds keys 4g + r of query l15; dQ^T += K^T dS^T, B = dS^T from registers.  Writes delta.
 //   dkv: wave = key tile, Q and dO images; S and dP with the wave's key tile in registers (a lane
 //        holds queries 4g + r of key l15); dV^T += dO^T P, dK^T += Q^T dS, B from registers.
+// The row I/O and the two tile steps below are shared with the streamed f32 kernels (attn_bwd_dq_stream_f32,
+// attn_bwd_dkv_stream_f32), whose images are 64-row chunks.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void f32_img_load(float* img, const float* src, int64_t ld, int N, int rows, int tid,
-                                             int nthr) {
-  for (int i = tid; i < rows * 16; i += nthr) {
-    const int r = i >> 4, c = i & 15;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (r < N) v = *reinterpret_cast<const f32x4*>(src + (int64_t)r * ld + c * 4);
-    *reinterpret_cast<f32x4*>(img + r * 64 + ((c ^ kswz(r)) << 2)) = v;
-  }
-}
-// row r of a swizzled image: the 16 floats [16g, 16g + 16) (4 chunks)
-__device__ __forceinline__ void f32_row16(const float* img, int r, int g, float (&x)[16]) {
+// Query row q of one head (clamped to N - 1): q and dO in registers, delta = rowsum(dO * O) (written for the
+// dkv kernel) and lse * log2(e).  base / dob / ob: the head's q, dO, O columns of row 0.
+__device__ __forceinline__ void f32_qrow(const float* base, int64_t ld_qkv, const float* dob, int64_t ld_do,
+                                         const float* ob, int64_t ld_o, const float* lse_bh, float* delta_bh, int q,
+                                         int N, int g, float (&qf)[16], float (&df)[16], float& dl, float& l2) {
+  const int qc = min(q, N - 1);
+  float of[16];
+  f32_glob16(base + (int64_t)qc * ld_qkv + 16 * g, qf);
+  f32_glob16(dob + (int64_t)qc * ld_do + 16 * g, df);
+  f32_glob16(ob + (int64_t)qc * ld_o + 16 * g, of);
+  dl = 0.f;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(img + r * 64 + (((4 * g + j) ^ kswz(r)) << 2));
-    x[4 * j] = v[0]; x[4 * j + 1] = v[1]; x[4 * j + 2] = v[2]; x[4 * j + 3] = v[3];
-  }
+  for (int j = 0; j < 16; ++j) dl = fmaf(df[j], of[j], dl);
+  dl += __shfl_xor(dl, 16, 64);
+  dl += __shfl_xor(dl, 32, 64);
+  if (q < N && g == 0) delta_bh[q] = dl;
+  l2 = lse_bh[qc] * LOG2E;
 }
-__device__ __forceinline__ f32x4 f32_chunk(const float* img, int r, int c) {
-  return *reinterpret_cast<const f32x4*>(img + r * 64 + ((c ^ kswz(r)) << 2));
+// Key row kc of one head: k and v in registers.
+__device__ __forceinline__ void f32_krow(const float* base, int64_t ld_qkv, int D, int kc, int g, float (&kf)[16],
+                                         float (&vf)[16]) {
+  f32_glob16(base + (int64_t)kc * ld_qkv + D + 16 * g, kf);
+  f32_glob16(base + (int64_t)kc * ld_qkv + 2 * D + 16 * g, vf);
 }
-__device__ __forceinline__ void f32_glob16(const float* p, float (&x)[16]) {
+// dq half, one key tile: S^T and dP^T of the lane's query (a lane holds keys 4g + r), p = exp2(c2 S - l2)
+// (0 on keys >= N and, causal, on keys > q), dS = p (dP - dl), dQ^T += K^T dS^T.  row0: the tile's first row in
+// the image; key0: its first key (the same for a resident image, j0 + row0 for a streamed chunk).
+__device__ __forceinline__ void f32_dq_step(const float* Kimg, const float* Vimg, int row0, int key0, int N, int l15,
+                                            int g, const float (&qf)[16], const float (&df)[16], float c2, float l2,
+                                            float dl, int q, int causal, f32x4 (&dq)[4]) {
+  float kf[16], vf[16];
+  f32_row16(Kimg, row0 + l15, g, kf);
+  f32_row16(Vimg, row0 + l15, g, vf);
+  f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = st;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(p + 4 * j);
-    x[4 * j] = v[0]; x[4 * j + 1] = v[1]; x[4 * j + 2] = v[2]; x[4 * j + 3] = v[3];
+  for (int ks = 0; ks < 16; ++ks) {
+    st = mfma4(kf[ks], qf[ks], st);   // S^T[key 4g + r][query l15]
+    dpt = mfma4(vf[ks], df[ks], dpt);
+  }
+  f32x4 ds;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int key = key0 + 4 * g + r;
+    float p = key < N ? fexp2(fmaf(st[r], c2, -l2)) : 0.f;
+    if (causal && key > q) p = 0.f;
+    ds[r] = p * (dpt[r] - dl);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const f32x4 a = f32_chunk(Kimg, row0 + 4 * g + r, l15);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma4(a[dt], ds[r], dq[dt]);
   }
 }
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+// dkv half, one query tile: S and dP of the lane's key (a lane holds queries 4g + r), row constants from the
+// lse * log2(e) / delta strips (indexed like the image), dV^T += dO^T P, dK^T += Q^T dS.  q0: the tile's first query.
+__device__ __forceinline__ void f32_dkv_step(const float* Qimg, const float* Oimg, const float* l2s, const float* dls,
+                                             int row0, int q0, int l15, int g, const float (&kf)[16],
+                                             const float (&vf)[16], float c2, bool kvalid, int key, int causal,
+                                             f32x4 (&dk)[4], f32x4 (&dv)[4]) {
+  float qf[16], df[16];
+  f32_row16(Qimg, row0 + l15, g, qf);
+  f32_row16(Oimg, row0 + l15, g, df);
+  f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dpc = sc;
+#pragma unroll
+  for (int ks = 0; ks < 16; ++ks) {
+    sc = mfma4(qf[ks], kf[ks], sc);   // S[query 4g + r][key l15]
+    dpc = mfma4(df[ks], vf[ks], dpc);
+  }
+  const f32x4 l2 = *reinterpret_cast<const f32x4*>(l2s + row0 + 4 * g);
+  const f32x4 dl = *reinterpret_cast<const f32x4*>(dls + row0 + 4 * g);
+  f32x4 p, ds;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float pv = kvalid ? fexp2(fmaf(sc[r], c2, -l2[r])) : 0.f;
+    if (causal && key > q0 + 4 * g + r) pv = 0.f;
+    p[r] = pv;
+    ds[r] = pv * (dpc[r] - dl[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const f32x4 ao = f32_chunk(Oimg, row0 + 4 * g + r, l15), aq = f32_chunk(Qimg, row0 + 4 * g + r, l15);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      dv[dt] = mfma4(ao[dt], p[r], dv[dt]);
+      dk[dt] = mfma4(aq[dt], ds[r], dk[dt]);
+    }
+  }
 }
 
 template <int NT>
@@ -1126,54 +1259,17 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_f32mfma(const float* __restri
   __syncthreads();
   const float c2 = scale * LOG2E;
   for (int qt = wave; qt < NT; qt += 8) {
-    const int q = qt * 16 + l15, qc = min(q, N - 1);
-    float qf[16], df[16], of[16];
-    f32_glob16(base + (int64_t)qc * ld_qkv + 16 * g, qf);
-    f32_glob16(dout + ((int64_t)b * N + qc) * ld_do + h * 64 + 16 * g, df);
-    f32_glob16(o + ((int64_t)b * N + qc) * ld_o + h * 64 + 16 * g, of);
-    float dl = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) dl = fmaf(df[j], of[j], dl);
-    dl += __shfl_xor(dl, 16, 64);
-    dl += __shfl_xor(dl, 32, 64);
-    if (q < N && g == 0) delta_out[(int64_t)bh * N + q] = dl;
-    const float l2 = q < N ? lse[(int64_t)bh * N + q] * LOG2E : INFINITY;
+    const int q = qt * 16 + l15;
+    float qf[16], df[16], dl, l2;
+    f32_qrow(base, ld_qkv, dout + (int64_t)b * N * ld_do + h * 64, ld_do, o + (int64_t)b * N * ld_o + h * 64, ld_o,
+             lse + (int64_t)bh * N, delta_out + (int64_t)bh * N, q, N, g, qf, df, dl, l2);
     f32x4 dq[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
-    for (int kt = 0; kt < NT; ++kt) {
-      float kf[16], vf[16];
-      f32_row16(Kimg, kt * 16 + l15, g, kf);
-      f32_row16(Vimg, kt * 16 + l15, g, vf);
-      f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = st;
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        st = mfma4(kf[ks], qf[ks], st);   // S^T[key 4g + r][query l15]
-        dpt = mfma4(vf[ks], df[ks], dpt);
-      }
-      f32x4 ds;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = kt * 16 + 4 * g + r;
-        float p = key < N ? fexp2(fmaf(st[r], c2, -l2)) : 0.f;
-        if (causal && key > q) p = 0.f;
-        ds[r] = p * (dpt[r] - dl);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const f32x4 a = f32_chunk(Kimg, kt * 16 + 4 * g + r, l15);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma4(a[dt], ds[r], dq[dt]);
-      }
-    }
-    if (q < N) {
-      float* row = dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64 + 16 * g;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-        *reinterpret_cast<f32x4*>(row + 4 * rr) =
-            f32x4{dq[0][rr] * scale, dq[1][rr] * scale, dq[2][rr] * scale, dq[3][rr] * scale};
-    }
+    for (int kt = 0; kt < NT; ++kt)
+      f32_dq_step(Kimg, Vimg, kt * 16, kt * 16, N, l15, g, qf, df, c2, l2, dl, q, causal, dq);
+    if (q < N) f32_store_row(dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64 + 16 * g, dq, scale);
   }
 }
 
@@ -1201,54 +1297,17 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_f32mfma(const float* __restr
   __syncthreads();
   const float c2 = scale * LOG2E;
   for (int kt = wave; kt < NT; kt += 8) {
-    const int key = kt * 16 + l15, kc = min(key, N - 1);
+    const int key = kt * 16 + l15;
     const bool kvalid = key < N;
     float kf[16], vf[16];
-    f32_glob16(base + (int64_t)kc * ld_qkv + D + 16 * g, kf);
-    f32_glob16(base + (int64_t)kc * ld_qkv + 2 * D + 16 * g, vf);
+    f32_krow(base, ld_qkv, D, min(key, N - 1), g, kf, vf);
     f32x4 dk[4], dv[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = dk[dt]; }
 #pragma unroll 1
-    for (int qt = 0; qt < NT; ++qt) {
-      float qf[16], df[16];
-      f32_row16(Qimg, qt * 16 + l15, g, qf);
-      f32_row16(Oimg, qt * 16 + l15, g, df);
-      f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dpc = sc;
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        sc = mfma4(qf[ks], kf[ks], sc);   // S[query 4g + r][key l15]
-        dpc = mfma4(df[ks], vf[ks], dpc);
-      }
-      const f32x4 l2 = *reinterpret_cast<const f32x4*>(l2s + qt * 16 + 4 * g);
-      const f32x4 dl = *reinterpret_cast<const f32x4*>(dls + qt * 16 + 4 * g);
-      f32x4 p, ds;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float pv = kvalid ? fexp2(fmaf(sc[r], c2, -l2[r])) : 0.f;
-        if (causal && key > qt * 16 + 4 * g + r) pv = 0.f;
-        p[r] = pv;
-        ds[r] = pv * (dpc[r] - dl[r]);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const f32x4 ao = f32_chunk(Oimg, qt * 16 + 4 * g + r, l15), aq = f32_chunk(Qimg, qt * 16 + 4 * g + r, l15);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          dv[dt] = mfma4(ao[dt], p[r], dv[dt]);
-          dk[dt] = mfma4(aq[dt], ds[r], dk[dt]);
-        }
-      }
-    }
-    if (kvalid) {
-      float* row = dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64 + 16 * g;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        *reinterpret_cast<f32x4*>(row + D + 4 * rr) =
-            f32x4{dk[0][rr] * scale, dk[1][rr] * scale, dk[2][rr] * scale, dk[3][rr] * scale};
-        *reinterpret_cast<f32x4*>(row + 2 * D + 4 * rr) = f32x4{dv[0][rr], dv[1][rr], dv[2][rr], dv[3][rr]};
-      }
-    }
+    for (int qt = 0; qt < NT; ++qt)
+      f32_dkv_step(Qimg, Oimg, l2s, dls, qt * 16, qt * 16, l15, g, kf, vf, c2, kvalid, key, causal, dk, dv);
+    if (kvalid) f32_store_dkv(dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64 + 16 * g, D, dk, dv, scale);
   }
 }
 
@@ -1475,6 +1534,50 @@ __device__ __forceinline__ void st_commit(char* buf, StPiece p, int j0, int N) {
   *reinterpret_cast<bf16x8*>(buf + at_off(r, c)) = p.a;
   *reinterpret_cast<bf16x8*>(buf + ST_IMG + at_off(r, c)) = p.b;
 }
+// Online-softmax update for one chunk's raw scores s (this lane: keys j0 + kt*16 + 4g + r of its query, in both
+// dtypes): -inf on keys >= N, the running max m (raw scores, all 4 lanes of a query agree), this lane's part l of
+// the sum and oacc rescaled by alpha; s becomes p = exp2((s - m) c2).
+__device__ __forceinline__ void st_softmax_chunk(f32x4 (&s)[4], int j0, int N, int g, float c2, float& m, float& l,
+                                                 f32x4 (&oacc)[4]) {
+  if (j0 + ST_CH > N) {  // wave-uniform: only the last chunk holds keys >= N
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (j0 + kt * 16 + 4 * g + r >= N) s[kt][r] = -INFINITY;
+  }
+  float mt = -INFINITY;
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kt][r]);
+  mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
+  mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+  const float mn = fmaxf(m, mt);             // finite from the first chunk on: key 0 is never masked
+  const float alpha = fexp2((m - mn) * c2);  // first chunk: m = -inf -> 0
+  m = mn;
+  const float mc = m * c2;
+  float lt = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const float p = fexp2(fmaf(s[kt][r], c2, -mc)); s[kt][r] = p; lt += p; }
+  l = fmaf(l, alpha, lt);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oacc[dt] *= alpha;
+}
+// Row constants of a chunk for the dkv kernels, a strip of 2 x 64 floats behind the chunk's two images: threads
+// 0..63 carry lse * log2(e) (+inf past N: p = 0), 64..127 delta (0 past N).
+__device__ __forceinline__ float st_stat_fetch(const float* lse_bh, const float* delta_bh, int j0, int N) {
+  const int tid = threadIdx.x;
+  if (tid >= 2 * ST_CH) return 0.f;
+  const int i = j0 + (tid & (ST_CH - 1));
+  if (tid < ST_CH) return i < N ? lse_bh[i] * LOG2E : INFINITY;
+  return i < N ? delta_bh[i] : 0.f;
+}
+__device__ __forceinline__ void st_stat_commit(void* strip, float v) {
+  if (threadIdx.x < 2 * ST_CH) static_cast<float*>(strip)[threadIdx.x] = v;
+}
 
 __global__ __launch_bounds__(AT_THREADS, 2) void attn_fwd_stream(const bf16* __restrict__ qkv, int64_t ld_qkv, int D, int H,
                                                                 int N, float scale, bf16* __restrict__ o, int64_t ld_o,
@@ -1514,32 +1617,7 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_fwd_stream(const bf16* __r
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) s[kt] = mfma16(rowf(Kc, kt * 16, off.row[kk]), qf[kk], s[kt]);
     }
-    if (j0 + ST_CH > N) {  // wave-uniform: only the last chunk holds keys >= N
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (j0 + kt * 16 + 4 * g + r >= N) s[kt][r] = -INFINITY;
-    }
-    float mt = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kt][r]);
-    mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
-    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-    const float mn = fmaxf(m, mt);                // finite from the first chunk on: key 0 is never masked
-    const float alpha = fexp2((m - mn) * c2);     // first chunk: m = -inf -> 0
-    m = mn;
-    const float mc = m * c2;
-    float lt = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { const float p = fexp2(fmaf(s[kt][r], c2, -mc)); s[kt][r] = p; lt += p; }
-    l = fmaf(l, alpha, lt);
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) oacc[dt] *= alpha;
+    st_softmax_chunk(s, j0, N, g, c2, m, l, oacc);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const bf16x8 pf = pack8(s[2 * ks], s[2 * ks + 1]);
@@ -1564,7 +1642,8 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_fwd_stream(const bf16* __r
   }
 }
 
-// query-parallel half of the streamed backward: delta = rowsum(dO * O) and dQ (attn_bwd_dq's loop per chunk)
+// query-parallel half of the streamed backward: delta = rowsum(dO * O) and dQ (attn_bwd_dq's at_qrow and, per
+// chunk, at_dq_step)
 __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dq_stream(const bf16* __restrict__ qkv, int64_t ld_qkv, int D, int H,
                                                                    int N, float scale, const bf16* __restrict__ o,
                                                                    int64_t ld_o, const bf16* __restrict__ dout,
@@ -1576,21 +1655,10 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dq_stream(const bf16* 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
   const bf16* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
   const int q = blockIdx.y * ST_QB + wave * 16 + (lane & 15);
-  const int qc = min(q, N - 1);
   bf16x8 qf[2], of[2];
-  float dl = 0.f;
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    qf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)qc * ld_qkv + kk * 32 + g * 8);
-    of[kk] = *reinterpret_cast<const bf16x8*>(dout + ((int64_t)b * N + qc) * ld_do + h * 64 + kk * 32 + g * 8);
-    const bf16x8 ov = *reinterpret_cast<const bf16x8*>(o + ((int64_t)b * N + qc) * ld_o + h * 64 + kk * 32 + g * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) dl = fmaf((float)of[kk][e], (float)ov[e], dl);
-  }
-  dl += __shfl_xor(dl, 16, 64);
-  dl += __shfl_xor(dl, 32, 64);
-  const float l2 = lse[(int64_t)bh * N + qc] * LOG2E;
-  if (g == 0 && q < N) delta_out[(int64_t)bh * N + q] = dl;
+  float dl, l2;
+  at_qrow(base, ld_qkv, dout + (int64_t)b * N * ld_do + h * 64, ld_do, o + (int64_t)b * N * ld_o + h * 64, ld_o,
+          lse + (int64_t)bh * N, delta_out + (int64_t)bh * N, q, N, g, qf, of, dl, l2);
   const AtOffsets off(lane);
   const int nc = (N + ST_CH - 1) / ST_CH;
   StPiece pc = st_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, 0, N);
@@ -1609,39 +1677,15 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dq_stream(const bf16* 
     if (more) pc = st_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0 + ST_CH, N);
     const bool edge = j0 + ST_CH > N;  // wave-uniform: only the last chunk holds keys >= N
 #pragma unroll
-    for (int kp = 0; kp < 2; ++kp) {
-      f32x4 ds[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int kt = 2 * kp + u;
-        f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          sacc = mfma16(rowf(Kc, kt * 16, off.row[kk]), qf[kk], sacc);
-          dpacc = mfma16(rowf(Vc, kt * 16, off.row[kk]), of[kk], dpacc);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float pv = fexp2(fmaf(sacc[r], c2, -l2));
-          if (edge && j0 + kt * 16 + 4 * g + r >= N) pv = 0.f;
-          ds[u][r] = pv * (dpacc[r] - dl);
-        }
-      }
-      const bf16x8 dsf = pack8(ds[0], ds[1]);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma16(trf(Kc, kp * 32, off.tr[dt]), dsf, dq[dt]);
-    }
+    for (int kp = 0; kp < 2; ++kp)
+      at_dq_step(Kc, Vc, kp * 32, j0 + kp * 32, N, edge, off, g, qf, of, c2, l2, dl, q, 0, dq);
     if (more) st_commit(smem[(c + 1) & 1], pc, j0 + ST_CH, N);
     __syncthreads();
   }
   if (q < N) {
-    bf16* row = dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      bf16x4 qv = {(bf16)(dq[dt][0] * scale), (bf16)(dq[dt][1] * scale), (bf16)(dq[dt][2] * scale),
-                   (bf16)(dq[dt][3] * scale)};
-      *reinterpret_cast<bf16x4*>(row + dt * 16 + 4 * g) = qv;
-    }
+    for (int dt = 0; dt < 4; ++dt) dq[dt] *= scale;
+    at_store_row(dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64, dq, g);
   }
 }
 
@@ -1660,29 +1704,16 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dkv_stream(const bf16*
   const bf16* dob = dout + (int64_t)b * N * ld_do + h * 64;
   const int key = blockIdx.y * ST_QB + wave * 16 + (lane & 15);
   const bool kvalid = key < N;
-  const int kc = min(key, N - 1);
   bf16x8 kf[2], vf[2];
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    kf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)kc * ld_qkv + D + kk * 32 + g * 8);
-    vf[kk] = *reinterpret_cast<const bf16x8*>(base + (int64_t)kc * ld_qkv + 2 * D + kk * 32 + g * 8);
-  }
-  // row constants of a chunk: threads 0..63 carry lse * log2(e) (+inf past N: p = 0), 64..127 delta (0 past N)
-  auto stat_fetch = [&](int j0) -> float {
-    if (tid >= 2 * ST_CH) return 0.f;
-    const int i = j0 + (tid & (ST_CH - 1));
-    if (tid < ST_CH) return i < N ? lse[(int64_t)bh * N + i] * LOG2E : INFINITY;
-    return i < N ? delta_in[(int64_t)bh * N + i] : 0.f;
-  };
-  auto stat_commit = [&](char* buf, float v) {
-    if (tid < 2 * ST_CH) reinterpret_cast<float*>(buf + 2 * ST_IMG)[tid] = v;
-  };
+  at_krow(base, ld_qkv, D, min(key, N - 1), g, kf, vf);
+  const float* lse_bh = lse + (int64_t)bh * N;
+  const float* delta_bh = delta_in + (int64_t)bh * N;
   const AtOffsets off(lane);
   const int nc = (N + ST_CH - 1) / ST_CH;
   StPiece pc = st_fetch(base, ld_qkv, dob, ld_do, 0, N);
-  float sv = stat_fetch(0);
+  float sv = st_stat_fetch(lse_bh, delta_bh, 0, N);
   st_commit(smem[0], pc, 0, N);
-  stat_commit(smem[0], sv);
+  st_stat_commit(smem[0] + 2 * ST_IMG, sv);
   __syncthreads();
   const float c2 = scale * LOG2E;
   f32x4 dv[4], dk[4];
@@ -1698,52 +1729,21 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dkv_stream(const bf16*
     const bool more = c + 1 < nc;
     if (more) {
       pc = st_fetch(base, ld_qkv, dob, ld_do, j0 + ST_CH, N);
-      sv = stat_fetch(j0 + ST_CH);
+      sv = st_stat_fetch(lse_bh, delta_bh, j0 + ST_CH, N);
     }
 #pragma unroll 1
-    for (int qp = 0; qp < 2; ++qp) {
-      f32x4 p[2], ds[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int qt = 2 * qp + u;
-        f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          sacc = mfma16(rowf(Qc, qt * 16, off.row[kk]), kf[kk], sacc);
-          dpacc = mfma16(rowf(Oc, qt * 16, off.row[kk]), vf[kk], dpacc);
-        }
-        const f32x4 l2 = *reinterpret_cast<const f32x4*>(lse2 + qt * 16 + 4 * g);
-        const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + qt * 16 + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = kvalid ? fexp2(fmaf(sacc[r], c2, -l2[r])) : 0.f;
-          p[u][r] = pv;
-          ds[u][r] = pv * (dpacc[r] - dl[r]);
-        }
-      }
-      const bf16x8 pf = pack8(p[0], p[1]), dsf = pack8(ds[0], ds[1]);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        dv[dt] = mfma16(trf(Oc, qp * 32, off.tr[dt]), pf, dv[dt]);
-        dk[dt] = mfma16(trf(Qc, qp * 32, off.tr[dt]), dsf, dk[dt]);
-      }
-    }
+    for (int qp = 0; qp < 2; ++qp)
+      at_dkv_step(Qc, Oc, lse2, delta, qp * 32, j0 + qp * 32, off, g, kf, vf, c2, kvalid, key, 0, dk, dv);
     if (more) {
       st_commit(smem[(c + 1) & 1], pc, j0 + ST_CH, N);
-      stat_commit(smem[(c + 1) & 1], sv);
+      st_stat_commit(smem[(c + 1) & 1] + 2 * ST_IMG, sv);
     }
     __syncthreads();
   }
   if (kvalid) {
-    bf16* row = dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      bf16x4 kv = {(bf16)(dk[dt][0] * scale), (bf16)(dk[dt][1] * scale), (bf16)(dk[dt][2] * scale),
-                   (bf16)(dk[dt][3] * scale)};
-      bf16x4 vv = {(bf16)dv[dt][0], (bf16)dv[dt][1], (bf16)dv[dt][2], (bf16)dv[dt][3]};
-      *reinterpret_cast<bf16x4*>(row + D + dt * 16 + 4 * g) = kv;
-      *reinterpret_cast<bf16x4*>(row + 2 * D + dt * 16 + 4 * g) = vv;
-    }
+    for (int dt = 0; dt < 4; ++dt) dk[dt] *= scale;
+    at_store_dkv(dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64, D, dk, dv, g);
   }
 }
 
@@ -1826,32 +1826,7 @@ __global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_stream_f32(const float
       for (int ks = 0; ks < 16; ++ks) s[kt] = mfma4(kf[ks], qf[ks], s[kt]);  // S^T[key 4g + r][query l15]
       if (kt % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // bound K-row hoisting (VGPRs)
     }
-    if (j0 + ST_CH > N) {  // wave-uniform: only the last chunk holds keys >= N
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (j0 + kt * 16 + 4 * g + r >= N) s[kt][r] = -INFINITY;
-    }
-    float mt = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kt][r]);
-    mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
-    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-    const float mn = fmaxf(m, mt);             // finite from the first chunk on: key 0 is never masked
-    const float alpha = fexp2((m - mn) * c2);  // first chunk: m = -inf -> 0
-    m = mn;
-    const float mc = m * c2;
-    float lt = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { const float p = fexp2(fmaf(s[kt][r], c2, -mc)); s[kt][r] = p; lt += p; }
-    l = fmaf(l, alpha, lt);
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) oacc[dt] *= alpha;
+    st_softmax_chunk(s, j0, N, g, c2, m, l, oacc);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -1865,18 +1840,11 @@ __global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_stream_f32(const float
   }
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
-  if (q < N) {
-    const float inv = 1.0f / l;
-    float* orow = o + ((int64_t)b * N + q) * ld_o + h * 64 + 16 * g;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr)
-      *reinterpret_cast<f32x4*>(orow + 4 * rr) =
-          f32x4{oacc[0][rr] * inv, oacc[1][rr] * inv, oacc[2][rr] * inv, oacc[3][rr] * inv};
-    if (g == 0 && lse) lse[(int64_t)bh * N + q] = (m * c2 + __log2f(l)) * LN2;
-  }
+  if (q < N)
+    f32_store_o(o + ((int64_t)b * N + q) * ld_o + h * 64 + 16 * g, lse, (int64_t)bh * N + q, oacc, l, m * c2, g);
 }
 
-// query-parallel half of the streamed f32 backward: delta = rowsum(dO * O) and dQ (attn_bwd_dq_f32mfma's loop per chunk)
+// query-parallel half of the streamed f32 backward: delta = rowsum(dO * O) and dQ (f32_qrow, f32_dq_step per chunk)
 __global__ __launch_bounds__(AT_THREADS, 4) void attn_bwd_dq_stream_f32(
     const float* __restrict__ qkv, int64_t ld_qkv, int D, int H, int N, float scale, const float* __restrict__ o,
     int64_t ld_o, const float* __restrict__ dout, int64_t ld_do, const float* __restrict__ lse,
@@ -1886,21 +1854,10 @@ __global__ __launch_bounds__(AT_THREADS, 4) void attn_bwd_dq_stream_f32(
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, l15 = lane & 15;
   const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
-  const int q = blockIdx.y * ST_QB + wave * 16 + l15, qc = min(q, N - 1);
-  float qf[16], df[16];
-  float dl = 0.f;
-  {
-    float of[16];
-    f32_glob16(base + (int64_t)qc * ld_qkv + 16 * g, qf);
-    f32_glob16(dout + ((int64_t)b * N + qc) * ld_do + h * 64 + 16 * g, df);
-    f32_glob16(o + ((int64_t)b * N + qc) * ld_o + h * 64 + 16 * g, of);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) dl = fmaf(df[j], of[j], dl);
-  }
-  dl += __shfl_xor(dl, 16, 64);
-  dl += __shfl_xor(dl, 32, 64);
-  if (q < N && g == 0) delta_out[(int64_t)bh * N + q] = dl;
-  const float l2 = lse[(int64_t)bh * N + qc] * LOG2E;
+  const int q = blockIdx.y * ST_QB + wave * 16 + l15;
+  float qf[16], df[16], dl, l2;
+  f32_qrow(base, ld_qkv, dout + (int64_t)b * N * ld_do + h * 64, ld_do, o + (int64_t)b * N * ld_o + h * 64, ld_o,
+           lse + (int64_t)bh * N, delta_out + (int64_t)bh * N, q, N, g, qf, df, dl, l2);
   const int nc = (N + ST_CH - 1) / ST_CH;
   SfPiece pc = sf_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, 0, N);
   sf_commit(ring, pc, 0, N);
@@ -1917,39 +1874,12 @@ __global__ __launch_bounds__(AT_THREADS, 4) void attn_bwd_dq_stream_f32(
     const bool more = c + 1 < nc;
     if (more) pc = sf_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0 + ST_CH, N);
 #pragma unroll 1
-    for (int kt = 0; kt < 4; ++kt) {
-      float kf[16], vf[16];
-      f32_row16(Kc, kt * 16 + l15, g, kf);
-      f32_row16(Vc, kt * 16 + l15, g, vf);
-      f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = st;
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        st = mfma4(kf[ks], qf[ks], st);  // S^T[key 4g + r][query l15]
-        dpt = mfma4(vf[ks], df[ks], dpt);
-      }
-      f32x4 ds;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = j0 + kt * 16 + 4 * g + r < N ? fexp2(fmaf(st[r], c2, -l2)) : 0.f;
-        ds[r] = p * (dpt[r] - dl);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const f32x4 a = f32_chunk(Kc, kt * 16 + 4 * g + r, l15);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma4(a[dt], ds[r], dq[dt]);
-      }
-    }
+    for (int kt = 0; kt < 4; ++kt)
+      f32_dq_step(Kc, Vc, kt * 16, j0 + kt * 16, N, l15, g, qf, df, c2, l2, dl, q, 0, dq);
     if (more) sf_commit(ring + ((c + 1) & 1) * 2 * SF_IMG, pc, j0 + ST_CH, N);
     __syncthreads();
   }
-  if (q < N) {
-    float* row = dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64 + 16 * g;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr)
-      *reinterpret_cast<f32x4*>(row + 4 * rr) =
-          f32x4{dq[0][rr] * scale, dq[1][rr] * scale, dq[2][rr] * scale, dq[3][rr] * scale};
-  }
+  if (q < N) f32_store_row(dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64 + 16 * g, dq, scale);
 }
 
 // key-parallel half: dK, dV of the workgroup's 128 keys (K, V rows in registers) over streamed Q / dO chunks.
@@ -1965,26 +1895,17 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dkv_stream_f32(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
   const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
   const float* dob = dout + (int64_t)b * N * ld_do + h * 64;
-  const int key = blockIdx.y * ST_QB + wave * 16 + l15, kc = min(key, N - 1);
+  const int key = blockIdx.y * ST_QB + wave * 16 + l15;
   const bool kvalid = key < N;
   float kf[16], vf[16];
-  f32_glob16(base + (int64_t)kc * ld_qkv + D + 16 * g, kf);
-  f32_glob16(base + (int64_t)kc * ld_qkv + 2 * D + 16 * g, vf);
-  // row constants of a chunk: threads 0..63 carry lse * log2(e) (+inf past N: p = 0), 64..127 delta (0 past N)
-  auto stat_fetch = [&](int j0) -> float {
-    if (tid >= 2 * ST_CH) return 0.f;
-    const int i = j0 + (tid & (ST_CH - 1));
-    if (tid < ST_CH) return i < N ? lse[(int64_t)bh * N + i] * LOG2E : INFINITY;
-    return i < N ? delta_in[(int64_t)bh * N + i] : 0.f;
-  };
-  auto stat_commit = [&](float* buf, float v) {
-    if (tid < 2 * ST_CH) buf[2 * SF_IMG + tid] = v;
-  };
+  f32_krow(base, ld_qkv, D, min(key, N - 1), g, kf, vf);
+  const float* lse_bh = lse + (int64_t)bh * N;
+  const float* delta_bh = delta_in + (int64_t)bh * N;
   const int nc = (N + ST_CH - 1) / ST_CH;
   SfPiece pc = sf_fetch(base, ld_qkv, dob, ld_do, 0, N);
-  float sv = stat_fetch(0);
+  float sv = st_stat_fetch(lse_bh, delta_bh, 0, N);
   sf_commit(ring, pc, 0, N);
-  stat_commit(ring, sv);
+  st_stat_commit(ring + 2 * SF_IMG, sv);
   __syncthreads();
   const float c2 = scale * LOG2E;
   f32x4 dk[4], dv[4];
@@ -2000,54 +1921,19 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dkv_stream_f32(
     const bool more = c + 1 < nc;
     if (more) {
       pc = sf_fetch(base, ld_qkv, dob, ld_do, j0 + ST_CH, N);
-      sv = stat_fetch(j0 + ST_CH);
+      sv = st_stat_fetch(lse_bh, delta_bh, j0 + ST_CH, N);
     }
 #pragma unroll 1
-    for (int qt = 0; qt < 4; ++qt) {
-      float qf[16], df[16];
-      f32_row16(Qc, qt * 16 + l15, g, qf);
-      f32_row16(Oc, qt * 16 + l15, g, df);
-      f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dpc = sc;
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        sc = mfma4(qf[ks], kf[ks], sc);  // S[query 4g + r][key l15]
-        dpc = mfma4(df[ks], vf[ks], dpc);
-      }
-      const f32x4 l2 = *reinterpret_cast<const f32x4*>(l2s + qt * 16 + 4 * g);
-      const f32x4 dl = *reinterpret_cast<const f32x4*>(dls + qt * 16 + 4 * g);
-      f32x4 p, ds;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float pv = kvalid ? fexp2(fmaf(sc[r], c2, -l2[r])) : 0.f;
-        p[r] = pv;
-        ds[r] = pv * (dpc[r] - dl[r]);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const f32x4 ao = f32_chunk(Oc, qt * 16 + 4 * g + r, l15), aq = f32_chunk(Qc, qt * 16 + 4 * g + r, l15);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          dv[dt] = mfma4(ao[dt], p[r], dv[dt]);
-          dk[dt] = mfma4(aq[dt], ds[r], dk[dt]);
-        }
-      }
-    }
+    for (int qt = 0; qt < 4; ++qt)
+      f32_dkv_step(Qc, Oc, l2s, dls, qt * 16, j0 + qt * 16, l15, g, kf, vf, c2, kvalid, key, 0, dk, dv);
     if (more) {
       float* nb = ring + ((c + 1) & 1) * SF_BUF_DKV;
       sf_commit(nb, pc, j0 + ST_CH, N);
-      stat_commit(nb, sv);
+      st_stat_commit(nb + 2 * SF_IMG, sv);
     }
     __syncthreads();
   }
-  if (kvalid) {
-    float* row = dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64 + 16 * g;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      *reinterpret_cast<f32x4*>(row + D + 4 * rr) =
-          f32x4{dk[0][rr] * scale, dk[1][rr] * scale, dk[2][rr] * scale, dk[3][rr] * scale};
-      *reinterpret_cast<f32x4*>(row + 2 * D + 4 * rr) = f32x4{dv[0][rr], dv[1][rr], dv[2][rr], dv[3][rr]};
-    }
-  }
+  if (kvalid) f32_store_dkv(dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64 + 16 * g, D, dk, dv, scale);
 }
 
 // qkv-bias gradient partials past 288 tokens: part[b][c] = sum over the image's N rows of dqkv[.][c], one
@@ -2078,16 +1964,52 @@ static bool attn_long_stream() {
   return v != 0;
 }
 constexpr int AT_RESIDENT_MAX = 288;  // the resident kernels' token limit (NT_CASES)
+// VIT_ATTN_F32_GENERIC=1: the scalar-FMA f32 kernels instead of the f32 MFMA ones (A/B runs); f32 only
+static bool attn_f32_generic() {
+  static const int v = [] { const char* e = getenv("VIT_ATTN_F32_GENERIC"); return e && *e == '1' ? 1 : 0; }();
+  return v != 0;
+}
 
-// the streamed f32 kernels' rings are past the 64 KiB static limit: dynamic LDS, raised once
+// Which kernel family a vit_sdpa_fwd / vit_sdpa_bwd call takes (attention dispatch table).
+// aligned: every row stride of the call meets the family's vector width -- bf16 forward ld_qkv % 8, ld_o % 4,
+// backward also ld_do % 8, ld_dqkv % 4; f32 every stride % 4.
+enum AttnPath { AP_RESIDENT_BF16, AP_RESIDENT_F32, AP_STREAM_BF16, AP_STREAM_F32, AP_GENERIC };
+static AttnPath attn_path(int dtype, int N, int causal, bool aligned) {
+  const bool resident = N <= AT_RESIDENT_MAX;
+  if (aligned && (dtype == VIT_BF16 || (dtype == VIT_F32 && !attn_f32_generic()))) {
+    if (resident) return dtype == VIT_BF16 ? AP_RESIDENT_BF16 : AP_RESIDENT_F32;
+    // a causal streamed form is out of scope: it takes the generic kernels
+    if (!causal && attn_long_stream()) return dtype == VIT_BF16 ? AP_STREAM_BF16 : AP_STREAM_F32;
+  }
+  return AP_GENERIC;
+}
+
+// Kernels whose LDS is past the 64 KiB static limit take it as dynamic LDS; each family raises the
+// attribute once, behind a static flag.
+template <typename K>
+static void raise_lds(K* kernel, int bytes) {
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
 static void stream_f32_attrs() {
   static bool attr = false;
   if (attr) return;
-  (void)hipFuncSetAttribute((const void*)attn_fwd_stream_f32, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS);
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_stream_f32, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS);
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_stream_f32, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS_DKV);
+  raise_lds(attn_fwd_stream_f32, SF_LDS);
+  raise_lds(attn_bwd_dq_stream_f32, SF_LDS);
+  raise_lds(attn_bwd_dkv_stream_f32, SF_LDS_DKV);
   attr = true;
 }
+template <int NT>
+struct F32Res {  // resident f32 kernels: two head images of NT * 16 rows (+ lse / delta strips in dkv)
+  static constexpr int IMG = NT * 16 * 64 * 4, LDS = 2 * IMG, LDS_DKV = 2 * IMG + 2 * NT * 16 * 4;
+  static void attrs() {
+    static bool attr = false;
+    if (attr) return;
+    raise_lds(attn_fwd_f32mfma<NT>, LDS);
+    raise_lds(attn_bwd_dq_f32mfma<NT>, LDS);
+    raise_lds(attn_bwd_dkv_f32mfma<NT>, LDS_DKV);
+    attr = true;
+  }
+};
 
 // ---------------------------------------------------------------------------
 template <int NT>
@@ -2107,22 +2029,12 @@ static int fwd_mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N,
   VIT_CHECK_LAUNCH();
   return 0;
 }
-// VIT_ATTN_F32_GENERIC=1: the scalar-FMA f32 forward instead of the f32 MFMA kernel (A/B runs)
-static bool attn_f32_generic() {
-  static const int v = [] { const char* e = getenv("VIT_ATTN_F32_GENERIC"); return e && *e == '1' ? 1 : 0; }();
-  return v != 0;
-}
 template <int NT>
 static int fwd_f32mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal, void* o,
                        int64_t ld_o, float* lse, hipStream_t s) {
-  constexpr int lds = 2 * NT * 16 * 64 * 4;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_f32mfma<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
-  hipLaunchKernelGGL((attn_fwd_f32mfma<NT>), dim3(B * H), dim3(512), lds, s, (const float*)qkv, ld_qkv, D, H, N, scale,
-                     (float*)o, ld_o, lse, causal);
+  F32Res<NT>::attrs();
+  hipLaunchKernelGGL((attn_fwd_f32mfma<NT>), dim3(B * H), dim3(512), F32Res<NT>::LDS, s, (const float*)qkv, ld_qkv, D,
+                     H, N, scale, (float*)o, ld_o, lse, causal);
   VIT_CHECK_LAUNCH();
   return 0;
 }
@@ -2130,25 +2042,35 @@ template <int NT>
 static int bwd_f32mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal,
                        const void* o, int64_t ld_o, const void* dout, int64_t ld_do, const float* lse, float* delta,
                        void* dqkv, int64_t ld_dqkv, hipStream_t s) {
-  constexpr int img = NT * 16 * 64 * 4, lds_dq = 2 * img, lds_dkv = 2 * img + 2 * NT * 16 * 4;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_f32mfma<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dq);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_f32mfma<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dkv);
-    attr = true;
-  }
-  hipLaunchKernelGGL((attn_bwd_dq_f32mfma<NT>), dim3(B * H), dim3(512), lds_dq, s, (const float*)qkv, ld_qkv, D, H, N,
-                     scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta, (float*)dqkv, ld_dqkv, causal);
+  F32Res<NT>::attrs();
+  hipLaunchKernelGGL((attn_bwd_dq_f32mfma<NT>), dim3(B * H), dim3(512), F32Res<NT>::LDS, s, (const float*)qkv, ld_qkv,
+                     D, H, N, scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta, (float*)dqkv, ld_dqkv,
+                     causal);
   VIT_CHECK_LAUNCH();
-  hipLaunchKernelGGL((attn_bwd_dkv_f32mfma<NT>), dim3(B * H), dim3(512), lds_dkv, s, (const float*)qkv, ld_qkv, D, H,
-                     N, scale, (const float*)dout, ld_do, lse, (const float*)delta, (float*)dqkv, ld_dqkv, causal);
+  hipLaunchKernelGGL((attn_bwd_dkv_f32mfma<NT>), dim3(B * H), dim3(512), F32Res<NT>::LDS_DKV, s, (const float*)qkv,
+                     ld_qkv, D, H, N, scale, (const float*)dout, ld_do, lse, (const float*)delta, (float*)dqkv, ld_dqkv,
+                     causal);
   VIT_CHECK_LAUNCH();
   return 0;
 }
-// VIT_ATTN_BWD_SPLIT=1 keeps the two-kernel backward for every N (A/B runs)
+// The generic backward: any token count and alignment, causal or not.
+template <typename T>
+static int bwd_generic(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal,
+                       const void* o, int64_t ld_o, const void* dout, int64_t ld_do, const float* lse, float* delta,
+                       void* dqkv, int64_t ld_dqkv, hipStream_t s) {
+  if ((int64_t)B * H > 65535) return (int)hipErrorInvalidValue;  // the generic kernels put b*h on grid.y
+  const dim3 grid((N + 63) / 64, B * H);
+  hipLaunchKernelGGL(attn_bwd_dq_generic<T>, grid, dim3(256), 0, s, (const T*)qkv, ld_qkv, D, H, N, scale, (const T*)o,
+                     ld_o, (const T*)dout, ld_do, lse, delta, (T*)dqkv, ld_dqkv, causal);
+  VIT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(attn_bwd_dkv_generic<T>, grid, dim3(256), 0, s, (const T*)qkv, ld_qkv, D, H, N, scale,
+                     (const T*)dout, ld_do, lse, delta, (T*)dqkv, ld_dqkv, causal);
+  VIT_CHECK_LAUNCH();
+  return 0;
+}
 // bf16 backward form for N <= 224 (vit_sdpa_bwd_variant / VIT_ATTN_BWD_SPLIT=1, A/B): 1 = whole-head fused
-// (the default), 2 = the two kernels.  (Round 4's banded-query form measured 0.276 vs 0.248 ms standalone
-// and -0.8 % in the step, profiles/r04/ab_attn_bwd_band.txt, and was removed in round 5.)
+// (the default), 2 = the two kernels for every N.  (Round 4's banded-query form measured 0.276 vs 0.248 ms
+// standalone and -0.8 % in the step, profiles/r04/ab_attn_bwd_band.txt, and was removed in round 5.)
 static int g_bwd_variant = -1;
 static bool attn_bwd_split() {
   if (g_bwd_variant == 2) return true;
@@ -2164,12 +2086,9 @@ static int bwd_mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N,
     if (!attn_bwd_split()) {
       static bool attr = false;
       if (!attr) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd_fused<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  BwdF<NT>::LDS);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_fused<NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  BwdF<NT>::LDS);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_fused<NT, false, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, BwdF<NT>::LDS);
+        raise_lds(attn_bwd_fused<NT>, BwdF<NT>::LDS);
+        raise_lds(attn_bwd_fused<NT, true>, BwdF<NT>::LDS);
+        raise_lds(attn_bwd_fused<NT, false, true>, BwdF<NT>::LDS);
         attr = true;
       }
 #define BWD_FUSED(C, S, ST)                                                                                    \
@@ -2256,38 +2175,38 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
   hipStream_t s = (hipStream_t)stream;
   if (head_dim != 64 || N <= 0) return (int)hipErrorInvalidValue;
   const int D = H * 64;
-  const bool resident = N <= AT_RESIDENT_MAX;
-  if (!resident && dtype == VIT_BF16 && !causal && (ld_qkv % 8 == 0) && (ld_o % 4 == 0) && attn_long_stream()) {
-    hipLaunchKernelGGL(attn_fwd_stream, dim3(B * H, (N + ST_QB - 1) / ST_QB), dim3(AT_THREADS), 0, s,
-                       (const bf16*)qkv, ld_qkv, D, H, N, scale, (bf16*)o, ld_o, lse);
-    VIT_CHECK_LAUNCH();
-    ++g_long_count;
-    return 0;
-  }
-  if (!resident && dtype == VIT_F32 && !causal && (ld_qkv % 4 == 0) && (ld_o % 4 == 0) && attn_long_stream() &&
-      !attn_f32_generic()) {
-    stream_f32_attrs();
-    hipLaunchKernelGGL(attn_fwd_stream_f32, dim3(B * H, (N + ST_QB - 1) / ST_QB), dim3(AT_THREADS), SF_LDS, s,
-                       (const float*)qkv, ld_qkv, D, H, N, scale, (float*)o, ld_o, lse);
-    VIT_CHECK_LAUNCH();
-    ++g_long_f32_count;
-    return 0;
-  }
-  if (resident && dtype == VIT_BF16 && (ld_qkv % 8 == 0) && (ld_o % 4 == 0)) {
-    int nt = (N + 15) / 16;
-    switch (nt) {
+  const bool aligned = (ld_qkv % (dtype == VIT_BF16 ? 8 : 4) == 0) && (ld_o % 4 == 0);
+  const dim3 sgrid(B * H, (N + ST_QB - 1) / ST_QB);  // streamed kernels
+  switch (attn_path(dtype, N, causal, aligned)) {
+    case AP_STREAM_BF16:
+      hipLaunchKernelGGL(attn_fwd_stream, sgrid, dim3(AT_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
+                         (bf16*)o, ld_o, lse);
+      VIT_CHECK_LAUNCH();
+      ++g_long_count;
+      return 0;
+    case AP_STREAM_F32:
+      stream_f32_attrs();
+      hipLaunchKernelGGL(attn_fwd_stream_f32, sgrid, dim3(AT_THREADS), SF_LDS, s, (const float*)qkv, ld_qkv, D, H, N,
+                         scale, (float*)o, ld_o, lse);
+      VIT_CHECK_LAUNCH();
+      ++g_long_f32_count;
+      return 0;
+    case AP_RESIDENT_BF16:
+      switch ((N + 15) / 16) {
 #define CASE(n) case n: return fwd_mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
-      NT_CASES(CASE)
+        NT_CASES(CASE)
 #undef CASE
-    }
-  }
-  if (resident && dtype == VIT_F32 && (ld_qkv % 4 == 0) && (ld_o % 4 == 0) && !attn_f32_generic()) {
-    int nt = (N + 15) / 16;
-    switch (nt) {
+      }
+      break;
+    case AP_RESIDENT_F32:
+      switch ((N + 15) / 16) {
 #define CASE(n) case n: return fwd_f32mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
-      NT_CASES(CASE)
+        NT_CASES(CASE)
 #undef CASE
-    }
+      }
+      break;
+    case AP_GENERIC:
+      break;
   }
   if ((int64_t)B * H > 65535) return (int)hipErrorInvalidValue;  // the generic kernels put b*h on grid.y
   dim3 grid((N + 63) / 64, B * H);
@@ -2365,97 +2284,77 @@ int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
   hipStream_t s = (hipStream_t)stream;
   if (head_dim != 64 || N <= 0) return (int)hipErrorInvalidValue;
   const int D = H * 64;
-  const bool resident = N <= AT_RESIDENT_MAX;
   if (!delta_ws) return (int)hipErrorInvalidValue;
   // dbias == null with a partial buffer: leave the per-image [B][3D] partials for the caller (bf16 path)
   const bool part_only = !dbias && partial;
   if ((dbias || part_only) && (partial == nullptr || partial_floats < vit_sdpa_bwd_partial_floats(B, N, D)))
     return (int)hipErrorInvalidValue;
-  const bool mfma_ok = dtype == VIT_BF16 && (ld_qkv % 8 == 0) && (ld_do % 8 == 0) && (ld_dqkv % 4 == 0) && (ld_o % 4 == 0);
-  if (!resident && dtype == VIT_BF16) {
-    // streamed MFMA kernels, or the generic ones (causal, misaligned, vit_sdpa_long_config(0)); the bias
-    // partials come from a per-image column-sum pass over dqkv either way
-    if (mfma_ok && !causal && attn_long_stream()) {
-      const dim3 grid(B * H, (N + ST_QB - 1) / ST_QB);
-      hipLaunchKernelGGL(attn_bwd_dq_stream, grid, dim3(AT_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
+  const bool aligned = (ld_qkv % (dtype == VIT_BF16 ? 8 : 4) == 0) && (ld_do % (dtype == VIT_BF16 ? 8 : 4) == 0) &&
+                       (ld_dqkv % 4 == 0) && (ld_o % 4 == 0);
+  const AttnPath path = attn_path(dtype, N, causal, aligned);
+  // bf16 past 288 tokens, streamed or generic kernels alike: the bias partials come from a per-image
+  // column-sum pass over dqkv, so partial-only mode works there; elsewhere it needs the resident bf16 kernels
+  const bool long_bf16 = N > AT_RESIDENT_MAX && dtype == VIT_BF16;
+  if (part_only && !long_bf16 && path != AP_RESIDENT_BF16) return (int)hipErrorInvalidValue;
+  const dim3 sgrid(B * H, (N + ST_QB - 1) / ST_QB);  // streamed kernels
+  int rc = (int)hipErrorInvalidValue;
+  switch (path) {
+    case AP_RESIDENT_BF16:
+      switch ((N + 15) / 16) {
+#define CASE(n) case n: rc = bwd_mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv, (dbias || part_only) ? partial : nullptr, s); break;
+        NT_CASES(CASE)
+#undef CASE
+      }
+      if (rc || !dbias) return rc;
+      launch_colreduce(partial, B, 3 * D, dbias, 0, s, partial + (int64_t)B * 3 * D);
+      VIT_CHECK_LAUNCH();
+      return 0;
+    case AP_RESIDENT_F32:
+      switch ((N + 15) / 16) {
+#define CASE(n) case n: rc = bwd_f32mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv, s); break;
+        NT_CASES(CASE)
+#undef CASE
+      }
+      break;
+    case AP_STREAM_BF16:
+      hipLaunchKernelGGL(attn_bwd_dq_stream, sgrid, dim3(AT_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
                          (const bf16*)o, ld_o, (const bf16*)dout, ld_do, lse, delta_ws, (bf16*)dqkv, ld_dqkv);
       VIT_CHECK_LAUNCH();
-      hipLaunchKernelGGL(attn_bwd_dkv_stream, grid, dim3(AT_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
+      hipLaunchKernelGGL(attn_bwd_dkv_stream, sgrid, dim3(AT_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
                          (const bf16*)dout, ld_do, lse, (const float*)delta_ws, (bf16*)dqkv, ld_dqkv);
       VIT_CHECK_LAUNCH();
       ++g_long_count;
-    } else {
-      if ((int64_t)B * H > 65535) return (int)hipErrorInvalidValue;  // the generic kernels put b*h on grid.y
-      const dim3 grid((N + 63) / 64, B * H);
-      hipLaunchKernelGGL(attn_bwd_dq_generic<bf16>, grid, dim3(256), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
-                         (const bf16*)o, ld_o, (const bf16*)dout, ld_do, lse, delta_ws, (bf16*)dqkv, ld_dqkv, causal);
+      rc = 0;
+      break;
+    case AP_STREAM_F32:
+      stream_f32_attrs();
+      hipLaunchKernelGGL(attn_bwd_dq_stream_f32, sgrid, dim3(AT_THREADS), SF_LDS, s, (const float*)qkv, ld_qkv, D, H, N,
+                         scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta_ws, (float*)dqkv, ld_dqkv);
       VIT_CHECK_LAUNCH();
-      hipLaunchKernelGGL(attn_bwd_dkv_generic<bf16>, grid, dim3(256), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
-                         (const bf16*)dout, ld_do, lse, delta_ws, (bf16*)dqkv, ld_dqkv, causal);
+      hipLaunchKernelGGL(attn_bwd_dkv_stream_f32, sgrid, dim3(AT_THREADS), SF_LDS_DKV, s, (const float*)qkv, ld_qkv, D,
+                         H, N, scale, (const float*)dout, ld_do, lse, (const float*)delta_ws, (float*)dqkv, ld_dqkv);
       VIT_CHECK_LAUNCH();
-    }
-    if (!dbias && !part_only) return 0;
-    hipLaunchKernelGGL(attn_bias_image, dim3(B, (3 * D + 255) / 256), dim3(256), 0, s, (const bf16*)dqkv, ld_dqkv, N,
-                       3 * D, partial);
-    VIT_CHECK_LAUNCH();
-    if (dbias) {
-      launch_colreduce(partial, B, 3 * D, dbias, 0, s, partial + (int64_t)B * 3 * D);
-      VIT_CHECK_LAUNCH();
-    }
-    return 0;
+      ++g_long_f32_count;
+      rc = 0;
+      break;
+    case AP_GENERIC:
+      rc = dtype == VIT_BF16 ? bwd_generic<bf16>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse,
+                                                 delta_ws, dqkv, ld_dqkv, s)
+                             : bwd_generic<float>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse,
+                                                  delta_ws, dqkv, ld_dqkv, s);
+      break;
   }
-  if (part_only && !mfma_ok) return (int)hipErrorInvalidValue;
-  if (resident && mfma_ok) {
-    int nt = (N + 15) / 16;
-    int rc = (int)hipErrorInvalidValue;
-    switch (nt) {
-#define CASE(n) case n: rc = bwd_mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv, (dbias || part_only) ? partial : nullptr, s); break;
-      NT_CASES(CASE)
-#undef CASE
-    }
-    if (rc || !dbias) return rc;
+  if (rc) return rc;
+  if (!long_bf16)
+    return dbias ? vit_colsum(dtype, B * N, 3 * D, dqkv, ld_dqkv, dbias, partial, partial_floats, 0, stream) : 0;
+  if (!dbias && !part_only) return 0;
+  hipLaunchKernelGGL(attn_bias_image, dim3(B, (3 * D + 255) / 256), dim3(256), 0, s, (const bf16*)dqkv, ld_dqkv, N,
+                     3 * D, partial);
+  VIT_CHECK_LAUNCH();
+  if (dbias) {
     launch_colreduce(partial, B, 3 * D, dbias, 0, s, partial + (int64_t)B * 3 * D);
     VIT_CHECK_LAUNCH();
-    return 0;
   }
-  if (resident && dtype == VIT_F32 && (ld_qkv % 4 == 0) && (ld_do % 4 == 0) && (ld_dqkv % 4 == 0) && (ld_o % 4 == 0) &&
-      !attn_f32_generic()) {
-    int nt = (N + 15) / 16, rc = (int)hipErrorInvalidValue;
-    switch (nt) {
-#define CASE(n) case n: rc = bwd_f32mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv, s); break;
-      NT_CASES(CASE)
-#undef CASE
-    }
-    if (rc) return rc;
-    if (dbias) return vit_colsum(dtype, B * N, 3 * D, dqkv, ld_dqkv, dbias, partial, partial_floats, 0, stream);
-    return 0;
-  }
-  if (!resident && dtype == VIT_F32 && !causal && (ld_qkv % 4 == 0) && (ld_do % 4 == 0) && (ld_dqkv % 4 == 0) &&
-      (ld_o % 4 == 0) && attn_long_stream() && !attn_f32_generic()) {
-    stream_f32_attrs();
-    const dim3 grid(B * H, (N + ST_QB - 1) / ST_QB);
-    hipLaunchKernelGGL(attn_bwd_dq_stream_f32, grid, dim3(AT_THREADS), SF_LDS, s, (const float*)qkv, ld_qkv, D, H, N,
-                       scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta_ws, (float*)dqkv, ld_dqkv);
-    VIT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(attn_bwd_dkv_stream_f32, grid, dim3(AT_THREADS), SF_LDS_DKV, s, (const float*)qkv, ld_qkv, D, H,
-                       N, scale, (const float*)dout, ld_do, lse, (const float*)delta_ws, (float*)dqkv, ld_dqkv);
-    VIT_CHECK_LAUNCH();
-    ++g_long_f32_count;
-    if (dbias) return vit_colsum(dtype, B * N, 3 * D, dqkv, ld_dqkv, dbias, partial, partial_floats, 0, stream);
-    return 0;
-  }
-  if ((int64_t)B * H > 65535) return (int)hipErrorInvalidValue;  // the generic kernels put b*h on grid.y
-  dim3 grid((N + 63) / 64, B * H);
-#define GEN(T)                                                                                               \
-  hipLaunchKernelGGL(attn_bwd_dq_generic<T>, grid, dim3(256), 0, s, (const T*)qkv, ld_qkv, D, H, N, scale,    \
-                     (const T*)o, ld_o, (const T*)dout, ld_do, lse, delta_ws, (T*)dqkv, ld_dqkv, causal);    \
-  VIT_CHECK_LAUNCH();                                                                                        \
-  hipLaunchKernelGGL(attn_bwd_dkv_generic<T>, grid, dim3(256), 0, s, (const T*)qkv, ld_qkv, D, H, N, scale,   \
-                     (const T*)dout, ld_do, lse, delta_ws, (T*)dqkv, ld_dqkv, causal);
-  if (dtype == VIT_BF16) { GEN(bf16) } else { GEN(float) }
-#undef GEN
-  VIT_CHECK_LAUNCH();
-  if (dbias) return vit_colsum(dtype, B * N, 3 * D, dqkv, ld_dqkv, dbias, partial, partial_floats, 0, stream);
   return 0;
 }
 

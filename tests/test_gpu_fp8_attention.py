@@ -38,8 +38,10 @@ def _qkv(B, H, N, seed, dtype):
     return q, k, v, qkv
 
 
+# 129 and 192: three 64-key tiles, one key and all 64 in the last
 @pytest.mark.parametrize("B,H,N,causal", [(2, 2, 197, False), (2, 3, 77, True), (1, 2, 257, False),
-                                          (1, 1, 300, False), (3, 2, 16, False), (1, 2, 64, True)])
+                                          (1, 1, 300, False), (3, 2, 16, False), (1, 2, 64, True),
+                                          (2, 2, 129, False), (1, 2, 192, False), (2, 2, 129, True)])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_sdpa_fp8_matches_restatement_and_bound(B, H, N, causal, dtype):
     from vit_amd import ops
@@ -56,6 +58,53 @@ def test_sdpa_fp8_matches_restatement_and_bound(B, H, N, causal, dtype):
     ex = F8.exact_sdpa(q, k, v, causal=causal)
     err = (got - ex).abs().max().item() / ex.abs().max().item()
     cos = torch.nn.functional.cosine_similarity(got.flatten(), ex.flatten(), dim=0).item()
+    assert err <= 0.12 and cos >= 0.997, (err, cos)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_sdpa_fp8_three_tiles_far_draw_matches_restatement(dtype):
+    """B, H, N = 2, 2, 192 with the seed rule above (194) draws a row on which the CPU restatement alone is 0.16
+    of max|o| from exact attention (0.05 .. 0.08 on the other draws): the format's error, found without a GPU, and
+    past the 0.12 that the test above asks of kernel and format together.  The kernel must still be its
+    restatement there, under the same restatement bounds."""
+    from vit_amd import ops
+    B, H, N = 2, 2, 192
+    q, k, v, qkv = _qkv(B, H, N, seed=N + B, dtype=dtype)
+    o, lse = ops.sdpa_fwd(qkv.to(DEV), B, H, N, fp8=True)
+    torch.cuda.synchronize()
+    got = o.float().cpu().reshape(B, N, H, 64).permute(0, 2, 1, 3)
+    ref, ref_lse = F8.sdpa_fp8(q, k, v)
+    scale = ref.abs().max().item()
+    d = (got - ref.to(dtype).float()).abs()
+    print(f"max {d.max().item() / scale:.3e} mean {d.mean().item() / scale:.3e} of max|o_ref|")
+    assert d.max().item() <= 3e-2 * scale and d.mean().item() <= 1e-4 * scale, (d.max().item(), d.mean().item())
+    assert (lse.cpu().reshape(B, H, N) - ref_lse).abs().max().item() <= 1e-4 * ref_lse.abs().max().item() + 1e-5
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_sdpa_fp8_zero_rows_match_restatement(dtype):
+    """All-zero q and k rows (row scale e8m0_exp(0) = -127, uniform softmax rows) and zero v rows, from
+    oracle/attn_cases.py's ``zerorows``, under test_sdpa_fp8_matches_restatement_and_bound's bounds."""
+    from oracle import attn_cases as AC
+    from vit_amd import ops
+    B, H, N = 2, 2, 197
+    c = AC.make_case("zerorows", B, H, N, dtype)
+    q, k, v = (t.float() for t in AC.split_qkv(c.qkv, B, H, N))
+    assert (q[:, :, ::3] == 0).all() and (k[:, :, 1::5] == 0).all()
+    o, lse = ops.sdpa_fwd(c.qkv.to(DEV), B, H, N, fp8=True)
+    torch.cuda.synchronize()
+    got = o.float().cpu().reshape(B, N, H, 64).permute(0, 2, 1, 3)
+    ref, ref_lse = F8.sdpa_fp8(q, k, v)
+    assert torch.isfinite(got).all() and torch.isfinite(lse).all()
+    scale = ref.abs().max().item()
+    d = (got - ref.to(dtype).float()).abs()
+    print(f"max {d.max().item() / scale:.3e} mean {d.mean().item() / scale:.3e} of max|o_ref|")
+    assert d.max().item() <= 3e-2 * scale and d.mean().item() <= 1e-4 * scale, (d.max().item(), d.mean().item())
+    assert (lse.cpu().reshape(B, H, N) - ref_lse).abs().max().item() <= 1e-4 * ref_lse.abs().max().item() + 1e-5
+    ex = F8.exact_sdpa(q, k, v)
+    err = (got - ex).abs().max().item() / ex.abs().max().item()
+    cos = torch.nn.functional.cosine_similarity(got.flatten(), ex.flatten(), dim=0).item()
+    print(f"against exact attention: max err {err:.3e} cosine {cos:.5f}")
     assert err <= 0.12 and cos >= 0.997, (err, cos)
 
 

@@ -345,6 +345,11 @@ int vit_gather_rows(int n, int D, const float* src, int64_t ld_src, const int64_
                     void* stream);
 int vit_scatter_rows(int n, int D, const float* src, int64_t ld_src, const int64_t* idx, float* dst, int64_t ld_dst,
                      void* stream);
+/* gather_blocks  dst[i] = src[idx[i]] for whole token blocks (the cached frozen-prefix rows of a batch,
+ * VisualPrefixCache.take): rows of row_elems floats, contiguous in src and dst (row stride = row_elems),
+ * row_elems % 4 == 0, src and dst 16-byte aligned; idx is int64 in device memory and must have been checked
+ * against the rows of src by the caller (the kernel does not know their number).  Additive export, ABI 10. */
+int vit_gather_blocks(int n, int64_t row_elems, const float* src, const int64_t* idx, float* dst, void* stream);
 int vit_rownorm_fwd(int n, int D, const float* x, const float* log_scale, float* y, float* rnorm, void* stream);
 int vit_rownorm_bwd(int n, int D, const float* x, const float* dy, const float* rnorm, const float* log_scale,
                     float* dx, void* stream);

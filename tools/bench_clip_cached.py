@@ -1,0 +1,261 @@
+"""Config C3 with the frozen visual prefix cached against the same step uncached.
+
+CLIP-HBA ViT-L/14, DoRA r = 32 on the last two visual blocks and the last text block, MSE, AdamW, bs = 64
+(config C3), in fp32 and bf16.  Per dtype, in one process, cached and uncached alternate over --rounds
+rounds (>= 3); the record holds every round, the medians, the round-to-round spread and the ratio:
+
+  * the training step over shuffled batches of a --train image set (the cached step: ``cache.take(idx)`` +
+    ``forward(visual_prefix=...)``; the uncached one: ``images[idx]`` + ``forward(images)``),
+  * ``sweep.evaluate`` over 362 test images and ``sweep.behavioral_rsa`` over 48 inference images,
+  * the cache build itself.
+
+A third leg times the gather alone on one [n, 257, 1024] f32 tensor, 64 rows a call: ``take()`` (host index
+check and the index's copy included), and with the index already on the device ``vit_gather_blocks``,
+``vit_gather_rows`` and ``torch.index_select``.
+
+Without --leg this is a driver: every leg runs as a child process of its own under a time limit, the first
+failure stops the run, and the GPU clocks ``rocm-smi --showclocks`` reports are recorded before and after.
+Records go to --out (one JSON file per leg).
+
+    python tools/bench_clip_cached.py [--out profiles/r13] [--rounds 3] [--steps 8] [--leg f32|bf16|gather]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "vit-project_amd"))
+
+LEGS = ("f32", "bf16", "gather")
+LEG_TIMEOUT = {"f32": 420, "bf16": 300, "gather": 120}  # seconds, each child's own limit
+
+
+def _summary(vals):
+    med = statistics.median(vals)
+    return {"rounds": [round(v, 4) for v in vals], "median": round(med, 4),
+            "spread": round((max(vals) - min(vals)) / med, 4)}
+
+
+def _timed(fn, sync):
+    sync()
+    t0 = time.perf_counter()
+    out = fn()
+    sync()
+    return time.perf_counter() - t0, out
+
+
+def model_leg(a, dtype_name):
+    import numpy as np
+    import torch
+    import vit_amd
+    from vit_amd import sweep as S
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    dtype = {"f32": torch.float32, "bf16": torch.bfloat16}[dtype_name]
+    torch.manual_seed(0)
+    m = vit_amd.CLIPHBA([f"c{i}" for i in range(66)], "ViT-L/14", pos_embedding=True, compute_dtype=dtype)
+    vit_amd.apply_dora_to_ViT(m, n_vision_layers=2, n_transformer_layers=1, r=32)
+    vit_amd.switch_dora_layers(m, freeze_all=True, dora_state=True)
+    m = m.to(dev)
+    opt = vit_amd.FusedAdamW([p for p in m.parameters() if p.requires_grad], lr=3e-4)
+    crit = vit_amd.MSELoss()
+    g = torch.Generator().manual_seed(1)
+    mk = lambda n: (torch.randn(n, 3, 224, 224, generator=g).to(dev),
+                    (torch.randn(n, 66, generator=g) * 0.5 + 1.0).to(dev))
+    data = dict(train=mk(a.train), test=mk(362), inference=mk(48)[0])
+    r = np.random.default_rng(0).random((48, 48))
+    data["reference_rdm"] = (r + r.T) / 2
+    tr_x, tr_y = data["train"]
+    te_x, te_y = data["test"]
+
+    t_build, caches = _timed(lambda: S.prefix_caches_for(m, data, None, a.batch), sync)
+    rows = sum(c.x.shape[0] for c in caches.values())
+    order = torch.Generator().manual_seed(2)
+    # a shuffled batch's predictions, from the cache (built in order, in chunks) against the images themselves:
+    # other GEMM row counts in the frozen blocks, so equal to rounding, not bit for bit, in f32 (stream-K)
+    with torch.no_grad():
+        idx = torch.randperm(a.train, generator=torch.Generator().manual_seed(4))[:a.batch]
+        pu, pc = m(tr_x[idx]).double(), m(visual_prefix=caches["train"].take(idx)).double()
+        pred_diff = float((pc - pu).abs().max() / pu.abs().max())
+
+    fixed = caches["train"].take(torch.arange(a.batch))
+
+    def steps(cached, n):
+        m.train()
+        loss = None
+        for _ in range(n):
+            idx = torch.randperm(a.train, generator=order)[:a.batch]
+            x, y = tr_x[idx], tr_y[idx]  # as sweep._batches: the batch exists before the step is queued
+            opt.zero_grad(set_to_none=True)
+            if cached == "fixed":  # the cached step less its gather: one batch's rows, taken once
+                pred = m(visual_prefix=fixed)
+            else:
+                pred = m(visual_prefix=caches["train"].take(idx)) if cached else m(x)
+            loss = crit(pred, y)
+            loss.backward()
+            opt.step()
+        return loss
+
+    passes = {
+        "train_step_images_per_sec": None,
+        "evaluate_362_seconds": lambda c: S.evaluate(m, te_x, te_y, a.batch, crit,
+                                                     cache_visual_prefix=caches["test"] if c else False),
+        "rsa_48_seconds": lambda c: S.behavioral_rsa(m, data["inference"], data["reference_rdm"],
+                                                     cache_visual_prefix=caches["inference"] if c else False),
+    }
+    for c in (False, True):  # every shape of the timed windows, once
+        steps(c, a.warmup)
+        passes["evaluate_362_seconds"](c)
+        passes["rsa_48_seconds"](c)
+    res = {k: {"uncached": [], "cached": []} for k in passes}
+    host_ms = {"uncached": [], "cached": []}
+    no_gather = []
+    for _ in range(a.rounds):
+        for name, c in (("uncached", False), ("cached", True)):
+            dt, loss = _timed(lambda: steps(c, a.steps), sync)
+            assert torch.isfinite(loss)
+            res["train_step_images_per_sec"][name].append(a.batch * a.steps / dt)
+            for k in ("evaluate_362_seconds", "rsa_48_seconds"):
+                dt, _ = _timed(lambda: passes[k](c), sync)
+                res[k][name].append(dt)
+        dt, _ = _timed(lambda: steps("fixed", a.steps), sync)
+        no_gather.append(a.batch * a.steps / dt)
+    # the host's cost of queueing one step, the GPU idle when it starts (inside the windows above the index
+    # copy at the head of a step waits for the stream, so host time there is wall time): where this is
+    # close to the step's wall time the step is bound by the launches, not by the kernels
+    for name, c in (("uncached", False), ("cached", True)):
+        for _ in range(7):
+            sync()
+            t0 = time.perf_counter()
+            steps(c, 1)
+            host_ms[name].append((time.perf_counter() - t0) * 1e3)
+            sync()
+    # the clocks while the uncached step keeps the GPU busy (rocm-smi in a thread, steps until it returns)
+    import threading
+    load_clocks = []
+    th = threading.Thread(target=lambda: load_clocks.extend(_clocks()))
+    th.start()
+    while th.is_alive():
+        steps(False, 2)
+    th.join()
+    sync()
+    rec = {"metric": "CLIP-HBA ViT-L/14 + DoRA (config C3), frozen visual prefix cached vs uncached, one process",
+           "clocks_under_load": load_clocks,
+           "dtype": dtype_name, "batch": a.batch, "steps_per_round": a.steps, "rounds": a.rounds,
+           "train_images": a.train, "cache_rows": rows, "cache_gib": round(sum(c.nbytes for c in caches.values()) / 2 ** 30, 3),
+           "cache_build_seconds": round(t_build, 3), "shuffled_batch_prediction_rel_diff": pred_diff,
+           "cache_counters": {k: dict(hits=c.hits, bypassed=c.bypassed, builds=c.builds) for k, c in caches.items()},
+           "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2)}
+    rec["train_step_ms"] = {n: round(1e3 * a.batch / statistics.median(res["train_step_images_per_sec"][n]), 3)
+                            for n in host_ms}
+    rec["train_step_host_enqueue_ms"] = {n: _summary(v) for n, v in host_ms.items()}
+    for k, v in res.items():
+        u, c = _summary(v["uncached"]), _summary(v["cached"])
+        ratio = c["median"] / u["median"] if k.endswith("per_sec") else u["median"] / c["median"]
+        rec[k] = {"uncached": u, "cached": c, "cached_speedup": round(ratio, 3)}
+    rec["train_step_images_per_sec"]["cached_without_gather"] = _summary(no_gather)
+    return rec
+
+
+def gather_leg(a):
+    import torch
+    from vit_amd import _lib as L
+    from vit_amd import ops
+    from vit_amd.prefix_cache import VisualPrefixCache
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    n, N, W, b = a.gather_rows, 257, 1024, a.batch
+    cache = VisualPrefixCache()
+    cache.x = torch.randn(n, N, W, device=dev)
+    g = torch.Generator().manual_seed(3)
+    idxs = [torch.randperm(n, generator=g)[:b] for _ in range(a.gather_calls)]
+    didxs = [i.to(dev) for i in idxs]
+    out = torch.empty(b, N, W, device=dev)
+    src2, out2 = cache.x.view(n, N * W), out.view(b, N * W)
+    st = L.stream_ptr(dev)
+    variants = {
+        "take_cpu_index": lambda k: cache.take(idxs[k]),
+        "vit_gather_blocks": lambda k: L.call("vit_gather_blocks", b, N * W, L.ptr(cache.x), L.ptr(didxs[k]), L.ptr(out), st),
+        "vit_gather_rows": lambda k: ops.gather_rows(src2, didxs[k], out=out2),
+        "torch_index_select": lambda k: torch.index_select(cache.x, 0, didxs[k], out=out),
+    }
+    want = torch.index_select(cache.x, 0, didxs[0])
+    for name, fn in variants.items():
+        got = fn(0)
+        got = out if got is None else got
+        assert torch.equal(got.view(b, N, W), want), name
+    us = {k: [] for k in variants}
+    for _ in range(max(a.rounds, 5)):
+        for name, fn in variants.items():
+            dt, _ = _timed(lambda: [fn(k) for k in range(a.gather_calls)], sync)
+            us[name].append(dt / a.gather_calls * 1e6)
+    moved = 2 * b * N * W * 4
+    rec = {"metric": "gather of 64 cached [257, 1024] f32 rows, microseconds per call (calls queued back to back, one "
+                     "synchronise per round)", "source_rows": n, "rows_per_call": b, "calls_per_round": a.gather_calls,
+           "bytes_moved_per_call": moved}
+    for k, v in us.items():
+        s = _summary(v)
+        s["gb_per_sec_at_median"] = round(moved / s["median"] / 1e3, 1)
+        rec[k] = s
+    return rec
+
+
+def _clocks():
+    try:
+        p = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30)
+        return [ln.strip() for ln in p.stdout.splitlines() if "clk" in ln.lower()][:16] or ["not reported"]
+    except (OSError, subprocess.SubprocessError) as e:
+        return [f"not available: {type(e).__name__}"]
+
+
+def driver(a):
+    os.makedirs(a.out, exist_ok=True)
+    clocks = {"before": _clocks()}
+    for leg in a.legs.split(","):
+        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--out", a.out, "--rounds", str(a.rounds),
+               "--steps", str(a.steps), "--warmup", str(a.warmup), "--batch", str(a.batch), "--train", str(a.train),
+               "--gather-rows", str(a.gather_rows), "--gather-calls", str(a.gather_calls)]
+        print("leg", leg, flush=True)
+        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale).returncode  # TimeoutExpired ends the run
+        if rc != 0:
+            print(f"leg {leg} failed with exit code {rc}: stopping", flush=True)
+            return rc
+    clocks["after"] = _clocks()
+    with open(os.path.join(a.out, "clocks.json"), "w") as fh:
+        json.dump(clocks, fh, indent=1)
+    return 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", choices=LEGS)
+    ap.add_argument("--legs", default=",".join(LEGS), help="the driver's legs, in order")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13"))
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--train", type=int, default=256, help="training images (1444 in the sweep; the step sees 64 a time)")
+    ap.add_argument("--gather-rows", type=int, default=512)
+    ap.add_argument("--gather-calls", type=int, default=100)
+    ap.add_argument("--timeout-scale", type=float, default=1.0)
+    a = ap.parse_args()
+    if a.rounds < 3:
+        ap.error("--rounds must be at least 3: the spread is part of the record")
+    if a.leg is None:
+        sys.exit(driver(a))
+    rec = gather_leg(a) if a.leg == "gather" else model_leg(a, a.leg)
+    os.makedirs(a.out, exist_ok=True)
+    name = "gather_blocks.json" if a.leg == "gather" else f"bench_clip_cached_{a.leg}.json"
+    with open(os.path.join(a.out, name), "w") as fh:
+        json.dump(rec, fh, indent=1)
+    print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -11,6 +11,8 @@ from .optim import FusedSGD, FusedAdamW, CosineAnnealingLRWithWarmup
 from .dora import DoRALayer, dora_weight
 from . import rsa
 from . import clip
+from . import prefix_cache
+from .prefix_cache import VisualPrefixCache
 from . import sweep
 from . import data
 from . import evaluate
@@ -20,7 +22,8 @@ from .clip import CLIPHBA, MSELoss, mse_loss, apply_dora_to_ViT, switch_dora_lay
 __all__ = ["VisionTransformer", "create_model", "cross_entropy", "set_wgrad_overlap", "FusedSGD", "FusedAdamW",
            "CosineAnnealingLRWithWarmup", "DoRALayer", "dora_weight", "rsa", "clip", "data", "CLIPHBA", "MSELoss",
            "mse_loss", "apply_dora_to_ViT", "switch_dora_layers", "count_trainable_parameters", "set_forward_only",
-           "set_cls_tail", "block_forward_only", "evaluate", "EvalMeter", "validate", "resample_abs_pos_embed", "adapt_state_dict"]
+           "set_cls_tail", "block_forward_only", "evaluate", "EvalMeter", "validate", "resample_abs_pos_embed", "adapt_state_dict",
+           "prefix_cache", "VisualPrefixCache"]
 
 
 def load_library(path=None):

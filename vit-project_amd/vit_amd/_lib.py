@@ -92,6 +92,7 @@ SIGNATURES = {
     "vit_token_embed": [i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "vit_gather_rows": [i32, i32, vp, i64, vp, vp, i64, vp],
     "vit_scatter_rows": [i32, i32, vp, i64, vp, vp, i64, vp],
+    "vit_gather_blocks": [i32, i64, vp, vp, vp, vp],
     "vit_rownorm_fwd": [i32, i32, vp, vp, vp, vp, vp],
     "vit_rownorm_bwd": [i32, i32, vp, vp, vp, vp, vp, vp],
     "vit_mse_fwd": [i32, vp, vp, vp, vp],

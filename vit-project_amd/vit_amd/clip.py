@@ -31,7 +31,9 @@ blocks are autograd nodes with parameters that need gradients; their backward ru
 MLP/LN2 backward and one weight gradient (``_BlockFn`` honours ``needs_input_grad``).  The
 frozen text blocks in front of the first DoRA block see the same 66 prompts every step, so
 their output is cached (keyed by the prompt tensor and the parameters' versions) -- the result
-is bit-identical to recomputing it.
+is bit-identical to recomputing it.  The frozen visual blocks see the same images in every epoch of a
+sweep; keeping their output is opt-in (``visual_prefix`` / ``forward(prefix=...)`` here, the rows live in
+``prefix_cache.VisualPrefixCache``).
 """
 from __future__ import annotations
 
@@ -322,9 +324,9 @@ class CLIP(nn.Module):
         return dict(heads=heads, eps=1e-5, quick_gelu=True, dtype=self.compute_dtype, causal=causal, attn_fp8=fp8)
 
     # -- towers -----------------------------------------------------------------
-    def encode_image(self, image, pos_embedding=True):
-        L.require_gpu(image)
-        self._ensure_shadows()
+    def _visual_stem(self, image, pos_embedding):
+        """conv1 as an MFMA GEMM over unfolded patches, class + positional embedding, ln_pre: the f32
+        residual stream [B, N, W] in front of the first block."""
         v = self.visual
         stem = [v.conv1.weight, v.class_embedding, v.positional_embedding, v.ln_pre.weight, v.ln_pre.bias]
         if torch.is_grad_enabled() and any(p.requires_grad for p in stem):
@@ -349,20 +351,83 @@ class CLIP(nn.Module):
         x = ops.patch_embed_fwd(U, w2, None, pos.contiguous(), v.class_embedding.detach().contiguous(), B, npatch)
         x2, _, _ = ops.layer_norm_fwd(x.reshape(B * (npatch + 1), W), v.ln_pre.weight.detach(),
                                       v.ln_pre.bias.detach(), 1e-5, torch.float32, need_stats=False)
-        x = x2.reshape(B, npatch + 1, W)
+        return x2.reshape(B, npatch + 1, W)
+
+    def _visual_blocks(self, x, lo, hi):
+        """``visual.transformer.resblocks[lo:hi]`` over the residual stream ``x``.  The block at ``hi - 1``
+        writes its output out (``resid_last``) when it is the tower's last block or ``hi`` is a cut
+        (:meth:`visual_prefix`): nothing is then pending for a block that is not part of this call."""
+        W = self.visual.conv1.out_channels
+        T = self.compute_dtype
         heads = W // 64
-        blocks = list(v.transformer.resblocks)
+        blocks = list(self.visual.transformer.resblocks)
         first = _first_trainable(blocks)
         # the residual adds run inside the next LayerNorm (as the ViT blocks, model._tokens); in f32 the
         # same f32 add as the GEMM's residual epilogue, so the reference-precision result is unchanged
         rs = ({"pending": None} if ((T != torch.float32 or _FUSED_RESID_F32[0]) and ops.add_layer_norm_supported(W))
               else None)
-        for i, blk in enumerate(blocks):
+        for i in range(lo, hi):
             cfg = self._cfg(heads, False, frozen=i < first)
             if rs is not None:
-                cfg = dict(cfg, resid=rs, resid_last=i == len(blocks) - 1)
-            x = run_block(x, blk.block_params(), cfg)
-        idx = self._cls_rows(B, npatch + 1, x.device)
+                cfg = dict(cfg, resid=rs, resid_last=i == hi - 1)
+            x = run_block(x, blocks[i].block_params(), cfg)
+        return x
+
+    def visual_prefix(self, image, pos_embedding=True):
+        """The frozen front of the visual tower: ``(x, first)`` with ``x`` the f32 residual stream
+        [B, N, W] after the stem and ``resblocks[:first]``, ``first`` the first block with a trainable
+        parameter.  No augmentation reaches the CLIP-HBA sweep's images, so ``x`` is the same in every
+        step, epoch and condition: ``encode_image(prefix=x)`` continues from it.
+
+        The launches are those ``encode_image(image)`` runs for these blocks (forward-only chain, fp8
+        attention if enabled), but for the cut: block ``first - 1`` writes its output out, so with the
+        fused residual adds block ``first`` starts from a plain tensor and not from a pending pair."""
+        L.require_gpu(image)
+        first = _first_trainable(list(self.visual.transformer.resblocks))
+        if first == 0:
+            raise ValueError("visual_prefix: the first visual block is trainable, so there is no frozen prefix "
+                             "(apply_dora_to_ViT / switch_dora_layers leave the blocks in front of the DoRA ones frozen)")
+        self._ensure_shadows()
+        with torch.no_grad():
+            x = self._visual_blocks(self._visual_stem(image, pos_embedding), 0, first)
+        return x, first
+
+    def _check_prefix(self, prefix):
+        v = self.visual
+        N, W = (v.input_resolution // v.patch_size) ** 2 + 1, v.conv1.out_channels
+        if not torch.is_tensor(prefix) or prefix.dim() != 3 or tuple(prefix.shape[1:]) != (N, W):
+            got = tuple(prefix.shape) if torch.is_tensor(prefix) else type(prefix).__name__
+            raise ValueError(f"prefix must be the [B, {N}, {W}] tensor of visual_prefix(), got {got}")
+        if prefix.dtype != torch.float32:
+            raise ValueError(f"prefix must be float32 (the residual stream), got {prefix.dtype}")
+        if prefix.device != self.logit_scale.device:
+            raise ValueError(f"prefix is on {prefix.device}, the model on {self.logit_scale.device}")
+        if prefix.requires_grad:
+            raise ValueError("prefix must not require a gradient: the blocks that made it are frozen")
+
+    def encode_image(self, image=None, pos_embedding=True, prefix=None):
+        """Image features [B, embed_dim].  ``prefix`` (the ``x`` of :meth:`visual_prefix`, e.g. rows of a
+        :class:`~vit_amd.prefix_cache.VisualPrefixCache`) replaces ``image``: the stem and the frozen
+        blocks are skipped, the trainable blocks and the pooled head run as ever."""
+        if (image is None) == (prefix is None):
+            raise ValueError("encode_image takes an image batch or a prefix, one of the two")
+        blocks = list(self.visual.transformer.resblocks)
+        if prefix is not None:
+            self._check_prefix(prefix)
+            L.require_gpu(prefix)
+            lo = _first_trainable(blocks)
+            if lo == 0:
+                raise ValueError("encode_image(prefix=...): the first visual block is trainable, there is no "
+                                 "frozen prefix to continue from")
+            self._ensure_shadows()
+            x = prefix.contiguous()
+        else:
+            L.require_gpu(image)
+            self._ensure_shadows()
+            x, lo = self._visual_stem(image, pos_embedding), 0
+        x = self._visual_blocks(x, lo, len(blocks))
+        v = self.visual
+        idx = self._cls_rows(x.shape[0], x.shape[1], x.device)
         return _PoolHeadFn.apply(x, idx, v.ln_post.weight, v.ln_post.bias, v.proj, 1e-5)
 
     def _cls_rows(self, B, N, dev):
@@ -412,8 +477,10 @@ class CLIP(nn.Module):
             self._idx_cache = c
         return _PoolHeadFn.apply(x, c[key], self.ln_final.weight, self.ln_final.bias, self.text_projection, 1e-5)
 
-    def forward(self, image, text, pos_embedding=True):
-        img = self.encode_image(image, pos_embedding)
+    def forward(self, image=None, text=None, pos_embedding=True, prefix=None):
+        if text is None:
+            raise ValueError("CLIP.forward needs the tokenized prompts")
+        img = self.encode_image(image, pos_embedding, prefix=prefix)
         txt = self.encode_text(text)
         return _ClipLogitsFn.apply(img, txt, self.logit_scale)
 
@@ -491,14 +558,18 @@ class CLIPHBA(nn.Module):
         self._cached_tokenized_prompts = None
         self._cached_device = None
 
-    def forward(self, image):
+    def forward(self, image=None, *, visual_prefix=None):
+        """``forward(image)`` as the reference calls it; ``forward(visual_prefix=x)`` continues from the
+        frozen visual blocks' output (``clip_model.visual_prefix``, a ``VisualPrefixCache`` row batch)."""
+        if (image is None) == (visual_prefix is None):
+            raise ValueError("CLIPHBA.forward takes an image batch or visual_prefix, one of the two")
         if self.clip_model.training:
             self.clip_model.eval()
-        device = image.device
+        device = image.device if image is not None else visual_prefix.device
         if self._cached_tokenized_prompts is None or self._cached_device != device:
             self._cached_tokenized_prompts = self.tokenized_prompts.to(device)
             self._cached_device = device
-        pred_score = self.clip_model(image, self._cached_tokenized_prompts, self.pos_embedding)
+        pred_score = self.clip_model(image, self._cached_tokenized_prompts, self.pos_embedding, prefix=visual_prefix)
         return pred_score.float()
 
 

@@ -660,6 +660,45 @@ def scatter_rows(src2d, idx, dst2d):
     return dst2d
 
 
+def check_block_indices(idx, rows: int):
+    """The host-side guard of :func:`gather_blocks`: int64, one-dimensional, every entry in [0, rows)."""
+    if idx.dtype != torch.int64 or idx.dim() != 1:
+        raise TypeError(f"gather_blocks: idx must be a 1-D int64 tensor, got {idx.dtype} {tuple(idx.shape)}")
+    if idx.numel():
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= rows:
+            raise IndexError(f"gather_blocks: index {lo if lo < 0 else hi} is out of range for {rows} rows")
+
+
+def gather_blocks(src3d, idx, out=None):
+    """out[i] = src3d[idx[i]] for whole [N, W] token blocks (f32, contiguous, N * W a multiple of 4):
+    ``torch.index_select(src3d, 0, idx)`` with the grid spread over each block, not one wave per row.
+
+    ``idx`` is checked on the host before anything is queued (``IndexError``, nothing launched).  Pass
+    the batch order as the CPU tensor it already is: the check then costs no synchronisation; a device
+    ``idx`` is read back for it."""
+    L.require_gpu(src3d)
+    if src3d.dim() != 3 or src3d.dtype != torch.float32 or not src3d.is_contiguous():
+        raise ValueError(f"gather_blocks: src must be a contiguous f32 [n, N, W] tensor, got {src3d.dtype} "
+                         f"{tuple(src3d.shape)} strides {src3d.stride()}")
+    rows, N, W = src3d.shape
+    if (N * W) % 4 or src3d.data_ptr() % 16:
+        raise ValueError(f"gather_blocks: blocks of {N * W} floats at {src3d.data_ptr():#x} are not 16-byte vectors")
+    check_block_indices(idx, rows)
+    n = idx.numel()
+    if out is None:
+        out = torch.empty(n, N, W, dtype=torch.float32, device=src3d.device)
+    elif (out.shape != (n, N, W) or out.dtype != torch.float32 or out.device != src3d.device
+          or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError(f"gather_blocks: out must be a contiguous, 16-byte aligned f32 {(n, N, W)} tensor on "
+                         f"{src3d.device}")
+    if n == 0:
+        return out
+    didx = idx.to(src3d.device).contiguous()
+    call("vit_gather_blocks", n, N * W, ptr(src3d), ptr(didx), ptr(out), _s(src3d))
+    return out
+
+
 def rownorm_fwd(x2d, log_scale=None):
     n, D = x2d.shape
     y = torch.empty_like(x2d)

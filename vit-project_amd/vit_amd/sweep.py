@@ -48,6 +48,11 @@ DORA_MODULES = ("clip_model.visual.transformer.resblocks.22.attn.out_proj",
                 "clip_model.transformer.resblocks.11.attn.out_proj")
 
 
+# perturbations that replace the batch's images (perturb.perturb_batch): such batches cannot come from a
+# visual prefix cache
+IMAGE_PERTURBATIONS = ("image_noise", "uniform_images")
+
+
 def _module(model, path):
     m = model
     for attr in path.split("."):
@@ -138,35 +143,88 @@ def load_random_states(random_state_path, epoch, optimizer=None, dataloader_gene
     return True
 
 
-def _batches(images, targets, batch_size, generator, shuffle=True):
-    """torch DataLoader(shuffle=True, generator=g) order over in-memory tensors."""
+def _batches(images, targets, batch_size, generator, shuffle=True, with_index=False):
+    """torch DataLoader(shuffle=True, generator=g) order over in-memory tensors.  ``with_index``: yield
+    ``(images[idx], targets[idx], idx)``, ``idx`` the batch's rows as a CPU int64 tensor (what a visual
+    prefix cache is asked for); the draw, the order and the batches are the same."""
     n = images.shape[0]
     order = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
     for i in range(0, n, batch_size):
         idx = order[i:i + batch_size]
-        yield images[idx], targets[idx]
+        if with_index:
+            yield images[idx], targets[idx], idx
+        else:
+            yield images[idx], targets[idx]
 
 
-def evaluate(model, images, targets, batch_size, criterion):
-    """NEWP:584-602: mean criterion over the test set (no grad)."""
+PREFIX_SETS = ("train", "test", "inference")
+
+
+def _set_images(data, name):
+    return data[name] if name == "inference" else data[name][0]
+
+
+def prefix_caches_for(model, data, caches=None, batch_size=64, max_bytes=None):
+    """The visual prefix caches of ``data``'s train, test and inference images for ``model``, as a dict
+    by set name.  ``caches`` (a dict from an earlier call) is updated in place: a cache whose key still
+    matches is kept -- ``load_dora_parameters`` touches only DoRA modules, so a worker's caches carry over
+    its conditions -- and a stale one is rebuilt.  ``ValueError`` when ``model`` cannot use a cache (no
+    CLIPHBA, or no frozen visual block)."""
+    from .prefix_cache import VisualPrefixCache, frozen_visual_blocks
+    frozen_visual_blocks(model)
+    caches = {} if caches is None else caches
+    for name in PREFIX_SETS:
+        c = caches.get(name)
+        if c is None:
+            c = caches[name] = VisualPrefixCache()
+        c.ensure(model, _set_images(data, name), batch_size, max_bytes)
+    return caches
+
+
+def _checked_cache(cache, model, images, batch_size):
+    """``cache_visual_prefix`` of one pass as a cache that matches: True builds one for this pass, a
+    ``VisualPrefixCache`` is checked (the caller owns it, so a stale one is an error here, not a rebuild)."""
+    if cache is True:
+        from .prefix_cache import VisualPrefixCache
+        return VisualPrefixCache.build(model, images, batch_size)
+    if not cache.valid_for(model, images):
+        raise RuntimeError("the visual prefix cache is stale for this model and these images (a frozen parameter, "
+                           "a model switch or the image tensor changed since it was built): rebuild it with "
+                           "ensure() / prefix_caches_for()")
+    return cache
+
+
+def evaluate(model, images, targets, batch_size, criterion, cache_visual_prefix=False):
+    """NEWP:584-602: mean criterion over the test set (no grad).  ``cache_visual_prefix``: False, the
+    ``VisualPrefixCache`` of ``images`` (checked against the model here, once per pass), or True to build
+    one for this pass."""
+    cache = _checked_cache(cache_visual_prefix, model, images, batch_size) if cache_visual_prefix else None
     model.eval()
     tot, n = 0.0, 0
     with torch.no_grad():
-        for x, y in _batches(images, targets, batch_size, None, shuffle=False):
-            pred = model(x)
+        for x, y, *idx in _batches(images, targets, batch_size, None, shuffle=False, with_index=cache is not None):
+            pred = model(x) if cache is None else model(visual_prefix=cache.take(idx[0]))
             tot += float(criterion(pred, y)) * x.shape[0]
             n += x.shape[0]
     model.train()
     return tot / max(n, 1)
 
 
-def behavioral_rsa(model, inference_images, reference_rdm, batch_size=16):
+def behavioral_rsa(model, inference_images, reference_rdm, batch_size=16, cache_visual_prefix=False):
     """NEWP:605-654: 66-D predictions of the 48 inference images -> RDM -> Spearman vs the
-    reference RDM (vit_amd.rsa restates the reference's float64 corrcoef / upper triangle)."""
+    reference RDM (vit_amd.rsa restates the reference's float64 corrcoef / upper triangle).
+    ``cache_visual_prefix``: as :func:`evaluate`, for ``inference_images``."""
+    cache = (_checked_cache(cache_visual_prefix, model, inference_images, batch_size) if cache_visual_prefix
+             else None)
     model.eval()
+    n = inference_images.shape[0]
     with torch.no_grad():
-        preds = torch.cat([model(inference_images[i:i + batch_size]).float().cpu()
-                           for i in range(0, inference_images.shape[0], batch_size)])
+        if cache is None:
+            preds = torch.cat([model(inference_images[i:i + batch_size]).float().cpu()
+                               for i in range(0, n, batch_size)])
+        else:
+            preds = torch.cat([model(visual_prefix=cache.take(torch.arange(i, min(i + batch_size, n)))).float().cpu()
+                               for i in range(0, n, batch_size)])
     model.train()
     rho, p, _ = RSA.rsa(preds.numpy().astype(np.float64), reference_rdm)
     return rho, p
@@ -175,7 +233,8 @@ def behavioral_rsa(model, inference_images, reference_rdm, batch_size=16):
 def train_condition(model, optimizer, criterion, data, *, epochs, training_run, perturb_length, perturb_type,
                     perturb_seed=42, perturb_distribution="target", batch_size=64, early_stopping_patience=5,
                     training_res_path, dora_parameters_path, random_state_path, dataloader_generator,
-                    resume_from_epoch=0, previous_training_res_path=None, modules=DORA_MODULES):
+                    resume_from_epoch=0, previous_training_res_path=None, modules=DORA_MODULES,
+                    cache_visual_prefix=False, prefix_caches=None):
     """The epoch loop of NEWP:train_model for one (training_run, perturb_length) condition.
 
     ``data`` = dict(train=(images, targets), test=(images, targets), inference=images,
@@ -184,9 +243,23 @@ def train_condition(model, optimizer, criterion, data, *, epochs, training_run, 
 
     CSV start (NEWP:797-834): resuming in place (``previous_training_res_path`` is this CSV)
     appends; otherwise the file is rewritten with the header and, when resuming from another
-    run (a shorter sibling, LEN:246-253), that run's rows for epochs <= ``resume_from_epoch``."""
+    run (a shorter sibling, LEN:246-253), that run's rows for epochs <= ``resume_from_epoch``.
+
+    ``cache_visual_prefix`` (off by default): the frozen visual blocks' output of the train,
+    test and inference images is computed once (``prefix_caches_for``) and every step, test pass and RSA
+    pass continues from it.  ``prefix_caches``: a dict that keeps the caches between calls -- a cache that
+    no longer matches the model or the images is rebuilt here, never used.  Batches whose *images* are
+    perturbed (``image_noise``, ``uniform_images`` inside the window) run uncached and are counted in the
+    train cache's ``bypassed``; target perturbations keep the cache.  ``ValueError`` at once when the model
+    has no frozen visual block or is no ``CLIPHBA``.  The generator draws and the batch order are the
+    same either way."""
     tr_x, tr_y = data["train"]
     te_x, te_y = data["test"]
+    caches = None
+    if cache_visual_prefix:
+        caches = prefix_caches_for(model, data, prefix_caches, batch_size)
+    elif prefix_caches is not None:
+        raise ValueError("prefix_caches is given but cache_visual_prefix is off")
     mean, std = float(tr_y.mean()), float(tr_y.std())
     in_place = (previous_training_res_path == training_res_path and os.path.exists(training_res_path)
                 and resume_from_epoch > 0)
@@ -210,21 +283,32 @@ def train_condition(model, optimizer, criterion, data, *, epochs, training_run, 
     for epoch in range(resume_from_epoch, epochs):
         used = dict(random_target=False, label_shuffle=False, uniform_images=False, image_noise=False)
         total = 0.0
-        for batch_idx, (x, y) in enumerate(_batches(tr_x, tr_y, batch_size, dataloader_generator)):
-            if P.in_window(epoch, training_run, perturb_length) and perturb_type is not None:
+        for batch_idx, (x, y, *idx) in enumerate(_batches(tr_x, tr_y, batch_size, dataloader_generator,
+                                                          with_index=caches is not None)):
+            perturbed = P.in_window(epoch, training_run, perturb_length) and perturb_type is not None
+            if perturbed:
                 x, y = P.perturb_batch(perturb_type, x.clone(), y, epoch=epoch, batch_idx=batch_idx,
                                        training_run=training_run, perturb_length=perturb_length,
                                        perturb_seed=perturb_seed, mean=mean, std=std,
                                        distribution=perturb_distribution)
                 used[perturb_type] = True
             optimizer.zero_grad()
-            loss = criterion(model(x), y)
+            if caches is None:
+                pred = model(x)
+            elif perturbed and perturb_type in IMAGE_PERTURBATIONS:
+                caches["train"].bypass()  # the images were replaced: nothing cached describes them
+                pred = model(x)
+            else:
+                pred = model(visual_prefix=caches["train"].take(idx[0]))
+            loss = criterion(pred, y)
             loss.backward()
             optimizer.step()
             total += float(loss.detach()) * x.shape[0]
         train_loss = total / tr_x.shape[0]
-        test_loss = evaluate(model, te_x, te_y, batch_size, criterion)
-        rho, p = behavioral_rsa(model, data["inference"], data["reference_rdm"])
+        test_loss = evaluate(model, te_x, te_y, batch_size, criterion,
+                             cache_visual_prefix=caches["test"] if caches else False)
+        rho, p = behavioral_rsa(model, data["inference"], data["reference_rdm"],
+                                cache_visual_prefix=caches["inference"] if caches else False)
         row = [epoch + 1, train_loss, test_loss, rho, p, used["random_target"], used["label_shuffle"],
                used["uniform_images"], used["image_noise"]]
         with open(training_res_path, "a", newline="") as fh:
@@ -334,15 +418,22 @@ def resume_plan(out_dir, perturb_type, start, length, baseline_dora_path, baseli
 
 def run_sweep(make_model_and_optimizer, criterion, data, conditions: Sequence[Tuple[int, int]], *, rank=0,
               world=1, perturb_type, out_dir, baseline_dora_path, baseline_random_state_path, epochs,
-              **train_kw) -> List[Tuple[Tuple[int, int], str]]:
+              cache_visual_prefix=False, **train_kw) -> List[Tuple[Tuple[int, int], str]]:
     """Run this rank's share of ``conditions`` ((training_run, perturb_length) pairs, LEN:42-83).
 
     ``parallel.shard_conditions`` keeps each start epoch's chain on one rank, and a chain runs in
     increasing length, so each condition finds its shorter sibling finished (``resume_plan``).
     Each condition writes LEN's layout: ``out_dir/{perturb_type}_e{E}_l{L}/training_res.csv``,
     ``dora_params_{E}/``, ``random_states_{E}/``.  No collective: conditions are independent
-    (SURVEY §8e).  Returns [((start, length), csv path, resume source)]."""
+    (SURVEY §8e).  Returns [((start, length), csv path, resume source)].
+
+    ``cache_visual_prefix``: this call owns one set of visual prefix caches and hands it to every
+    condition (``train_condition``).  They carry over from one condition to the next as long as
+    ``make_model_and_optimizer`` returns models that share their frozen parameter tensors (the backbone
+    loaded once, fresh DoRA layers and optimizer per condition); a model with new frozen tensors has
+    another key and its caches are rebuilt."""
     done = []
+    caches = {} if cache_visual_prefix else None
     for start, length in shard_conditions(conditions, world, rank):
         plan = resume_plan(out_dir, perturb_type, start, length, baseline_dora_path, baseline_random_state_path)
         d = condition_dir(out_dir, perturb_type, start, length)
@@ -361,7 +452,8 @@ def run_sweep(make_model_and_optimizer, criterion, data, conditions: Sequence[Tu
                         perturb_type=perturb_type, training_res_path=res,
                         dora_parameters_path=os.path.join(d, f"dora_params_{start}"),
                         random_state_path=os.path.join(d, f"random_states_{start}"), dataloader_generator=gen,
-                        resume_from_epoch=resume, previous_training_res_path=plan["previous_csv"], **train_kw)
+                        resume_from_epoch=resume, previous_training_res_path=plan["previous_csv"],
+                        cache_visual_prefix=cache_visual_prefix, prefix_caches=caches, **train_kw)
         done.append(((start, length), res, plan["source"]))
     return done
 
@@ -379,12 +471,16 @@ def _sweep_worker(rank, world, make_model_and_optimizer, criterion, data, condit
     results.put((rank, out))
 
 
-def launch_sweep(nprocs, make_model_and_optimizer, criterion, data, conditions, *, gpus=None, **kw):
+def launch_sweep(nprocs, make_model_and_optimizer, criterion, data, conditions, *, gpus=None,
+                 cache_visual_prefix=False, **kw):
     """One process per GPU (or per CPU worker when ``gpus`` is None), each running its
     ``shard_conditions`` share of ``conditions`` through :func:`run_sweep` -- the 8-way sharded
     C5 sweep with no collective.  ``make_model_and_optimizer`` and ``criterion``
-    must be picklable (module-level).  Returns {rank: [((start, length), csv, source)]}."""
+    must be picklable (module-level).  Returns {rank: [((start, length), csv, source)]}.
+    ``cache_visual_prefix``: each worker builds and owns its visual prefix caches (``run_sweep``)."""
     import torch.multiprocessing as mp
+    if cache_visual_prefix:
+        kw = dict(kw, cache_visual_prefix=True)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     devices = list(gpus) if gpus else []

@@ -245,6 +245,15 @@ int vit_sdpa_cls_count(int reset);
  * (VIT_BF16 or VIT_F32); head_dim 64, N <= 320; lse may be null.  Forward only. */
 int vit_sdpa_fwd_fp8(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o,
                      int64_t ld_o, float* lse, float scale, int causal, void* stream);
+/* The streamed form of vit_sdpa_fwd_fp8 (additive to ABI 10): the same quantisation, MFMAs and f32
+ * online softmax, with K and V passing through a two-buffer LDS ring of 64-key chunks instead of
+ * living there whole, so any N >= 1 runs; grid (B*H, ceil(N / 256)).  Up to 320 tokens o and lse are
+ * bit for bit vit_sdpa_fwd_fp8's.  Same arguments and refusals otherwise (head_dim != 64,
+ * ld_qkv % 8, ld_o % 4: hipErrorInvalidValue).  Forward only. */
+int vit_sdpa_fwd_fp8_stream(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv,
+                            void* o, int64_t ld_o, float* lse, float scale, int causal, void* stream);
+/* Host-side count of vit_sdpa_fwd_fp8_stream calls that launched (reset != 0 zeroes it after reading). */
+int vit_sdpa_fp8_stream_count(int reset);
 /* SDPA backward into dqkv (qkv layout). delta_ws >= B*H*N floats.  dbias (optional, [3*H*64]) =
  * column sums of dqkv (the qkv Linear's bias gradient), fused into the kernels;
  * partial >= vit_sdpa_bwd_partial_floats(B, N, H*64).  dbias == NULL with partial != NULL (bf16

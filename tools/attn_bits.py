@@ -7,7 +7,8 @@ One JSON line per seeded case (inputs as tests/test_gpu_attention_long.py::_case
 dqkv, delta_ws and dbias; for bf16 also of the [B][3D] bias partials that partial-only mode (dbias == NULL) leaves.
 The backward runs from the library's own o and lse.  Cases: the bf16 resident two-kernel backward (N > 224, and
 vit_sdpa_bwd_variant(2) below that), the f32 resident kernels, the streamed kernels of both dtypes, and the fused
-bf16 backward as a control.
+bf16 backward as a control.  First come the resident fp8 forward's o and lse (N = 77 causal, 197, 257, 320, both
+dtypes; ``--fp8-only`` stops after them).
 """
 import hashlib
 import json
@@ -32,6 +33,8 @@ CASES = ([("bf16 resident two-kernel", BF16, n, False, -1) for n in (240, 257, 2
          [("f32 resident", F32, n, c, -1) for n, c in ((50, False), (77, True), (197, False), (257, False), (288, False))] +
          [("streamed", dt, n, False, -1) for dt in (BF16, F32) for n in (289, 320, 577)] +
          [("bf16 fused (control)", BF16, 197, False, -1)])
+# the resident fp8 forward (o and lse only), both dtypes; --fp8-only runs these alone
+FP8_CASES = ((77, True), (197, False), (257, False), (320, False))
 
 
 def sha(t):
@@ -65,9 +68,30 @@ def run(dtype, N, causal):
     return out
 
 
+def run_fp8(dtype, N, causal):
+    """o and lse of the resident fp8 forward (vit_sdpa_fwd_fp8; N <= 320)."""
+    D = H * 64
+    g = torch.Generator().manual_seed(34)
+    qkv = (torch.randn(B * N, 3 * D, generator=g) * 1.5).to(dtype).cuda()
+    o, lse = ops.sdpa_fwd(qkv, B, H, N, causal=causal, fp8=True)
+    torch.cuda.synchronize()
+    return {"o": sha(o), "lse": sha(lse)}
+
+
 def main():
+    # an older build of the library (the parent's, for comparison) lacks the exports added since: bind what it has
+    import ctypes
+    probe = ctypes.CDLL(L.LIB_PATH)
+    for name in [n for n in L.SIGNATURES if not hasattr(probe, n)]:
+        del L.SIGNATURES[name]
     L.load()
     lib = L.lib()
+    for dtype in (BF16, F32):
+        for N, causal in FP8_CASES:
+            print(json.dumps({"kernels": "fp8 resident", "dtype": "bf16" if dtype == BF16 else "f32", "N": N,
+                              "causal": causal, **run_fp8(dtype, N, causal)}), flush=True)
+    if "--fp8-only" in sys.argv[1:]:
+        return
     for kernels, dtype, N, causal, variant in CASES:
         lib.vit_sdpa_bwd_variant(variant)
         try:

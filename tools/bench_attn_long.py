@@ -5,7 +5,10 @@ for the cost of streaming per score.  The variants alternate over --rounds round
 variant's round-to-round spread are reported.
 
     python tools/bench_attn_long.py [--dtype bf16|f32] [--batch 64] [--heads 12] [--n 577] [--n-resident 257]
-                                    [--reps 20]
+                                    [--reps 20] [--fp8]
+
+--fp8 (forward only): the streamed fp8 kernel against the streamed forward of --dtype at --n, and the resident fp8
+kernel against the streamed one at --n-resident (<= 320).
 
 Prints one JSON line per (variant, round) and a final summary line.  --no-generic / --no-streamed skip a
 variant (a tree without the streamed kernels can still time its resident kernels with --n 0).
@@ -48,8 +51,50 @@ def time_case(c, reps):
             "fwd_us_per_head": round(tf * 1e6 / (B * H), 4), "bwd_us_per_head": round(tb * 1e6 / (B * H), 4)}
 
 
+def main_fp8(a, dtype):
+    """--fp8, forward only: at --n the streamed fp8 kernel (ops.sdpa_fwd(fp8=True, fp8_long=True)) against the
+    streamed forward of --dtype; at --n-resident the resident fp8 kernel against the streamed one
+    (ops.sdpa_fwd_fp8_stream).  The variants alternate over --rounds rounds in this one process."""
+    L.lib().vit_sdpa_long_config(1)
+    variants = []
+    if a.n:
+        c = case(a.batch, a.heads, a.n, dtype)
+        fwd = lambda c=c, **kw: ops.sdpa_fwd(c["qkv"], c["B"], c["H"], c["N"], o=c["o"], lse=c["lse"], **kw)
+        variants += [(f"streamed {a.dtype}", c, fwd), ("streamed fp8", c, lambda: fwd(fp8=True, fp8_long=True))]
+    if a.n_resident:
+        r = case(a.batch, a.heads, a.n_resident, dtype)
+        variants += [("resident fp8 @ n_resident",  r, lambda: ops.sdpa_fwd(r["qkv"], r["B"], r["H"], r["N"], o=r["o"],
+                                                                              lse=r["lse"], fp8=True)),
+                     ("streamed fp8 @ n_resident", r, lambda: ops.sdpa_fwd_fp8_stream(r["qkv"], r["B"], r["H"], r["N"],
+                                                                                       o=r["o"], lse=r["lse"]))]
+    res = {name: [] for name, *_ in variants}
+    try:
+        for rnd in range(a.rounds):
+            for name, vc, f in variants:
+                t = timeit(f, a.reps)
+                fl = 4.0 * vc["B"] * vc["H"] * vc["N"] * vc["N"] * 64
+                row = {"fwd_ms": round(t * 1e3, 4), "fwd_tflops": round(fl / t / 1e12, 1)}
+                res[name].append(row)
+                print(json.dumps({"variant": name, "dtype": a.dtype, "round": rnd, "N": vc["N"], "batch": a.batch,
+                                  "heads": a.heads, **row}), flush=True)
+    finally:
+        L.lib().vit_sdpa_long_config(-1)
+    med = {name: statistics.median(r["fwd_ms"] for r in rs) for name, rs in res.items()}
+    spread = {name: round((max(r["fwd_ms"] for r in rs) - min(r["fwd_ms"] for r in rs)) / med[name], 4)
+              for name, rs in res.items()}
+    out = {"summary": True, "fp8": True, "dtype": a.dtype, "batch": a.batch, "heads": a.heads, "n": a.n,
+           "n_resident": a.n_resident, "median_fwd_ms": med, "spread": spread}
+    if a.n:
+        out[f"streamed_{a.dtype}_over_streamed_fp8"] = round(med[f"streamed {a.dtype}"] / med["streamed fp8"], 3)
+    if a.n_resident:
+        out["streamed_fp8_over_resident_fp8"] = round(med["streamed fp8 @ n_resident"] / med["resident fp8 @ n_resident"], 3)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fp8", action="store_true", help="forward only: the streamed fp8 kernel against the streamed "
+                    "forward of --dtype at --n, and against the resident fp8 kernel at --n-resident")
     ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--heads", type=int, default=12)
@@ -63,6 +108,8 @@ def main():
     a = ap.parse_args()
     lib = L.lib()
     dtype = torch.float32 if a.dtype == "f32" else torch.bfloat16
+    if a.fp8:
+        return main_fp8(a, dtype)
     variants = []
     if a.n:
         long_case = case(a.batch, a.heads, a.n, dtype)

@@ -6,6 +6,8 @@
         bf16 forward chains' half-batch row counts (27580 / 22852 x 3072 x 768) and at C3's fc1
         (16448 x 4096 x 1024, bf16 with QuickGELU and fp32); bytes written are computed from shapes.
   vit   ViT-B/16 no-grad forward, images/s, set_forward_only(True) against (False).
+  vit384fp8  vit_base_patch16_384 no-grad forward (577 tokens), bf16 attention against the streamed fp8 kernel
+        (not in the default --what; use --batch 64).
 
 Each pair is warmed up, then timed ``repeats`` times in the order A B A B ..., ``iters`` launches (or
 forwards) per timing; the record holds every repeat, the medians, the A/B difference and the repeat
@@ -110,9 +112,40 @@ def bench_vit(repeats, iters, batch):
     return [r]
 
 
+def bench_vit384_fp8(repeats, iters, batch):
+    """vit_base_patch16_384 (577 tokens, bf16) no-grad forward: bf16 attention against the streamed fp8 kernel
+    (set_attention_fp8(True, long_sequences=True))."""
+    import vit_amd
+    from vit_amd import _lib as L
+    torch.manual_seed(0)
+    m = vit_amd.create_model("vit_base_patch16_384", num_classes=1000, compute_dtype=torch.bfloat16).cuda().eval()
+    x = torch.randn(batch, 3, 384, 384, device="cuda")
+
+    def run(on):
+        def f():
+            m.set_attention_fp8(on, long_sequences=on)
+            with torch.no_grad():
+                return m(x)
+        return f
+
+    c0 = L.lib().vit_sdpa_fp8_stream_count(0)
+    y_off, y_on = run(False)().float(), run(True)().float()
+    streamed = L.lib().vit_sdpa_fp8_stream_count(0) - c0
+    ta, tb = alternate(run(False), run(True), repeats, iters, warmup=3)
+    m.set_attention_fp8(False)
+    r = {"case": "vit_b16_384_nograd_forward", "a": "bf16 attention", "b": "streamed fp8 attention", "batch": batch,
+         "iters": iters, "fp8_stream_calls_per_forward": streamed,
+         "logits_max_abs_diff": round((y_on - y_off).abs().max().item(), 5),
+         "logits_max_abs": round(y_off.abs().max().item(), 5)}
+    r.update(summary(ta, tb))
+    r["a_images_per_s"] = round(batch / r["a_median_ms"] * 1e3, 1)
+    r["b_images_per_s"] = round(batch / r["b_median_ms"] * 1e3, 1)
+    return [r]
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", default="fc1,vit")
+    ap.add_argument("--what", default="fc1,vit", help="fc1, vit, vit384fp8 (comma-separated)")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=256)
@@ -126,6 +159,8 @@ def main():
             rows += bench_fc1(a.repeats, a.iters)
         elif what == "vit":
             rows += bench_vit(a.repeats, a.iters, a.batch)
+        elif what == "vit384fp8":
+            rows += bench_vit384_fp8(a.repeats, a.iters, a.batch)
         else:
             raise SystemExit(f"unknown --what {what}")
     text = "\n".join(json.dumps(r) for r in rows)

@@ -281,6 +281,108 @@ template <> __device__ __forceinline__ void load8f<float>(const float* p, float*
   for (int u = 0; u < 4; ++u) { x[u] = a[u]; x[4 + u] = b[u]; }
 }
 
+// One 64-key tile of the fp8 online softmax, stated once for attn_fwd_fp8 (the tile inside the head's resident
+// images) and attn_fwd_fp8_stream (the chunk in the ring buffer): the two S^T MFMAs, the mask, the max / alpha /
+// exp2 update, the P pack and the two PV MFMAs.  Kt: the tile's 64 K rows (f8_koff layout), ksc: its 128 row-scale
+// bytes; Vt: the V^T image at the tile's key 0, rows vrow bytes apart; vsc[d * vsc_ld]: the tile's V scale bytes.
+// key0: the tile's first key, counted from key 0 of the head (mask only).  This lane: query q, lane half h.
+__device__ __forceinline__ void f8_tile_step(const unsigned char* Kt, const unsigned char* ksc, const unsigned char* Vt,
+                                             int vrow, const unsigned char* vsc, int vsc_ld, int key0, int N, int q,
+                                             int causal, const i32x8& qf, int qsc, float c2, int h, int l31, float& m,
+                                             float& l, f32x16 (&oacc)[2]) {
+  f32x16 s[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int key = u * 32 + l31;
+    typedef int i32x4_ __attribute__((ext_vector_type(4)));
+    const i32x4_ lo = *reinterpret_cast<const i32x4_*>(Kt + f8_koff(key, 2 * h));
+    const i32x4_ hi = *reinterpret_cast<const i32x4_*>(Kt + f8_koff(key, 2 * h + 1));
+    const i32x8 kf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    f32x16 z = {};
+    s[u] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf, qf, z, 0, 0, 0, ksc[key * 2 + h], 0, qsc);
+  }
+  // rows of s[u]: key key0 + u*32 + 4h + (r&3) + 8(r>>2); column: query q.  The mask (key >= N, causal: key > q)
+  // compares each row's constant part with two per-tile limits, so no per-row key lives in a register
+  const int lim_n = N - key0 - 4 * h, lim_q = causal ? q - key0 - 4 * h : 64;
+  float mt = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int kr = u * 32 + (r & 3) + 8 * (r >> 2);
+      if (kr >= lim_n || kr > lim_q) s[u][r] = -INFINITY;
+      mt = fmaxf(mt, s[u][r]);
+    }
+  mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+  const float mn = fmaxf(m, mt);  // finite from the first tile on: key 0 is never masked
+  const float alpha = fexp2((m - mn) * c2);  // first tile: m = -inf -> 0
+  m = mn;
+  const float mc = m * c2;
+  l *= alpha;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt) oacc[dt] *= alpha;
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float p = fexp2(fmaf(s[u][r], c2, -mc));
+      s[u][r] = p;
+      l += p;
+    }
+  i32x8 pf;  // P^T fragment: byte j = tile (j/16), register j%16, times 2^8
+#pragma unroll
+  for (int w = 0; w < 8; ++w) {
+    const f32x16& t = s[w >> 2];
+    const int r = 4 * (w & 3);
+    pf[w] = pack_fp8x4(t[r] * 256.f, t[r + 1] * 256.f, t[r + 2] * 256.f, t[r + 3] * 256.f);
+  }
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt) {
+    const int d = dt * 32 + l31;
+    const unsigned char* row = Vt + d * vrow + 4 * h;
+    i32x8 vf;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) vf[w] = *reinterpret_cast<const int*>(row + (w >> 2) * 32 + 8 * (w & 3));
+    oacc[dt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(vf, pf, oacc[dt], 0, 0, 0, vsc[d * vsc_ld], 0, 127 - 8);
+  }
+}
+
+// The Q^T fragment of query row qrow (its 64 head dims at src0): this lane's 32 d values (block h), one E8M0
+// scale for the row across both lane halves.
+template <typename T>
+__device__ __forceinline__ void f8_q_frag(const T* src0, int h, i32x8& qf, int& qsc) {
+  const T* src = src0 + h * 32;
+  float x[32];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) load8f<T>(src + c * 8, x + c * 8);
+  float amax = 0.f;
+#pragma unroll
+  for (int u = 0; u < 32; ++u) amax = fmaxf(amax, fabsf(x[u]));
+  amax = fmaxf(amax, __shfl_xor(amax, 32, 64));  // the query's other lane half: one scale per row
+  const int e = e8m0_exp(amax);
+  const float inv = inv_exp2i(e);
+#pragma unroll
+  for (int u = 0; u < 8; ++u) qf[u] = pack_fp8x4(x[4 * u] * inv, x[4 * u + 1] * inv, x[4 * u + 2] * inv, x[4 * u + 3] * inv);
+  qsc = e + 127;
+}
+
+// Writing o and lse of one 32-query tile, for both fp8 kernels: oacc holds O^T (rows d, column query q).
+template <typename T>
+__device__ __forceinline__ void f8_store(T* orow, float* lse_q, const f32x16 (&oacc)[2], float l, float mc, int h) {
+  const float inv = 1.0f / l;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int mq = 0; mq < 4; ++mq) {
+      const int d = dt * 32 + 4 * h + 8 * mq;
+      const f32x4 ov = {oacc[dt][4 * mq] * inv, oacc[dt][4 * mq + 1] * inv, oacc[dt][4 * mq + 2] * inv,
+                        oacc[dt][4 * mq + 3] * inv};
+      if constexpr (sizeof(T) == 2) *reinterpret_cast<bf16x4*>(orow + d) = bf16x4{(bf16)ov[0], (bf16)ov[1], (bf16)ov[2], (bf16)ov[3]};
+      else *reinterpret_cast<f32x4*>(orow + d) = ov;
+    }
+  if (h == 0 && lse_q) *lse_q = (mc + __log2f(l)) * LN2;
+}
+
 template <int NKT, typename T>  // 64-key tiles: keys padded to NKT * 64; T = the qkv / o dtype
 __global__ __launch_bounds__(F8_THREADS, 2) void attn_fwd_fp8(const T* __restrict__ qkv, int64_t ld_qkv, int D,
                                                              int H, int N, float scale, T* __restrict__ o,
@@ -350,99 +452,192 @@ __global__ __launch_bounds__(F8_THREADS, 2) void attn_fwd_fp8(const T* __restric
     // Q^T fragment: this lane's 32 d values (block h) of query q
     i32x8 qf;
     int qsc;
-    {
-      const T* src = base + (int64_t)min(q, N - 1) * ld_qkv + h * 32;
-      float x[32];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) load8f<T>(src + c * 8, x + c * 8);
-      float amax = 0.f;
-#pragma unroll
-      for (int u = 0; u < 32; ++u) amax = fmaxf(amax, fabsf(x[u]));
-      amax = fmaxf(amax, __shfl_xor(amax, 32, 64));  // the query's other lane half: one scale per row
-      const int e = e8m0_exp(amax);
-      const float inv = inv_exp2i(e);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) qf[u] = pack_fp8x4(x[4 * u] * inv, x[4 * u + 1] * inv, x[4 * u + 2] * inv, x[4 * u + 3] * inv);
-      qsc = e + 127;
-    }
+    f8_q_frag<T>(base + (int64_t)min(q, N - 1) * ld_qkv, h, qf, qsc);
     // online softmax over 64-key tiles (two S^T MFMAs each): only one tile's scores are live
     float m = -INFINITY, l = 0.f;
     f32x16 oacc[2] = {};
 #pragma unroll 1
-    for (int kt = 0; kt < NKT; ++kt) {
-      f32x16 s[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int key = (2 * kt + u) * 32 + l31;
-        typedef int i32x4_ __attribute__((ext_vector_type(4)));
-        const i32x4_ lo = *reinterpret_cast<const i32x4_*>(Kimg + f8_koff(key, 2 * h));
-        const i32x4_ hi = *reinterpret_cast<const i32x4_*>(Kimg + f8_koff(key, 2 * h + 1));
-        const i32x8 kf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        f32x16 z = {};
-        s[u] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf, qf, z, 0, 0, 0, Ksc[key * 2 + h], 0, qsc);
-      }
-      // rows of s[u]: key (2kt+u)*32 + 4h + (r&3) + 8(r>>2); column: query q
-      float mt = -INFINITY;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = (2 * kt + u) * 32 + 4 * h + (r & 3) + 8 * (r >> 2);
-          if (key >= N || (causal && key > q)) s[u][r] = -INFINITY;
-          mt = fmaxf(mt, s[u][r]);
-        }
-      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-      const float mn = fmaxf(m, mt);  // finite from the first tile on: key 0 is never masked
-      const float alpha = fexp2((m - mn) * c2);  // first tile: m = -inf -> 0
-      m = mn;
-      const float mc = m * c2;
-      l *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) oacc[dt] *= alpha;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float p = fexp2(fmaf(s[u][r], c2, -mc));
-          s[u][r] = p;
-          l += p;
-        }
-      i32x8 pf;  // P^T fragment: byte j = tile (j/16), register j%16, times 2^8
-#pragma unroll
-      for (int w = 0; w < 8; ++w) {
-        const f32x16& t = s[w >> 2];
-        const int r = 4 * (w & 3);
-        pf[w] = pack_fp8x4(t[r] * 256.f, t[r + 1] * 256.f, t[r + 2] * 256.f, t[r + 3] * 256.f);
-      }
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const int d = dt * 32 + l31;
-        const unsigned char* row = Vt + d * VROW + kt * 64 + 4 * h;
-        i32x8 vf;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) vf[w] = *reinterpret_cast<const int*>(row + (w >> 2) * 32 + 8 * (w & 3));
-        oacc[dt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(vf, pf, oacc[dt], 0, 0, 0, Vsc[d * NKT + kt], 0,
-                                                                   127 - 8);
-      }
-    }
+    for (int kt = 0; kt < NKT; ++kt)
+      f8_tile_step(Kimg + kt * 64 * 64, Ksc + kt * 128, Vt + kt * 64, VROW, Vsc + kt, NKT, kt * 64, N, q, causal, qf, qsc,
+                   c2, h, l31, m, l, oacc);
     l += __shfl_xor(l, 32, 64);
     const float mc = m * c2;
-    if (q < N) {
-      const float inv = 1.0f / l;
-      T* orow = o + ((int64_t)b * N + q) * ld_o + hh * 64;
+    if (q < N)
+      f8_store<T>(o + ((int64_t)b * N + q) * ld_o + hh * 64, lse ? lse + (int64_t)bh * N + q : nullptr, oacc, l, mc, h);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Streamed fp8 forward: attn_fwd_fp8's quantisation, MFMAs and online softmax (f8_tile_step) with no bound on
+// N.  K and V pass through a two-buffer LDS ring of 64-key chunks instead of living there whole.
+//   grid (B*H, ceil(N / 256)), 8 waves: a wave owns one 32-query tile, its Q fragment quantised once and kept in
+//   registers.  Per chunk (attn_fwd_stream's schedule): the next chunk's global loads are issued first, the
+//   tile step on the current chunk runs under their latency, then all 512 threads quantise the loaded pieces
+//   into the other buffer; one barrier per chunk.  The f32 form requests only K's piece before the step and V's
+//   after it, ahead of K's quantisation: with 16 loaded registers in flight over the step it spilled at the 128
+//   VGPRs that two workgroups per CU allow (launch bound 4 waves per SIMD); bf16's pieces are 8 registers.
+//   The step sits in its own `live` branch on purpose: as straight-line code the scheduler interleaved it with
+//   the quantisation and the kernel needed 156 (bf16) / 164 (f32) VGPRs instead of 125.
+//   A chunk is 64 keys, not 128: it is then exactly one of V's scale blocks (counted from key 0 of the head, as
+//   the resident kernel counts them) and one 16-B (bf16) piece of K and of V per thread, so both quantisations
+//   finish inside a wave -- K's row maximum over the 8 adjacent lanes of a key, V's block maximum over the 64
+//   lanes (keys) of the wave that holds 8 head dims -- and the buffer that is being written needs no second barrier.
+//   Buffer: Kimg (f8_koff) 4 KiB | V^T 64 rows of 64 + 4 bytes | 128 K scale bytes | 64 V scale bytes = 8640 B.
+// Keys past N: loaded from row N - 1 and zeroed in registers (at_load's rule), masked to -inf in the step.
+// Every wave runs every chunk and every barrier; a wave whose 32 queries all lie past N skips only the tile
+// steps and the stores (`live` is wave-uniform, `more` workgroup-uniform, no barrier sits under either).
+// The max is exact in any order and every other operation is the resident kernel's, in its order: up to 320
+// tokens o and lse are bit for bit attn_fwd_fp8's.
+// ---------------------------------------------------------------------------
+constexpr int F8S_CH = 64;                // keys per chunk = V's scale block
+constexpr int F8S_QB = F8_WAVES * 32;     // queries per workgroup
+constexpr int F8S_VROW = F8S_CH + 4;      // V^T row pitch: the resident kernel's +4 padding
+constexpr int F8S_VT = F8S_CH * 64;       // buffer offsets: V^T image, K scales, V scales
+constexpr int F8S_KSC = F8S_VT + 64 * F8S_VROW;
+constexpr int F8S_VSC = F8S_KSC + F8S_CH * 2;
+constexpr int F8S_BUF = (F8S_VSC + 64 + 15) / 16 * 16;
+static_assert(F8S_CH * 8 == F8_THREADS, "one 8-value piece of a chunk's K and of its V per thread");
+static_assert(F8_WAVES * 8 == 64, "a wave quantises 8 head dims of V");
+
+template <typename T> struct F8Raw;  // 8 values of a row as loaded, converted only when they are quantised
+template <> struct F8Raw<bf16> {
+  bf16x8 v;
+  __device__ __forceinline__ void load(const bf16* p) { v = *reinterpret_cast<const bf16x8*>(p); }
+  __device__ __forceinline__ void get(float* x, bool zero) const {
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
+    for (int u = 0; u < 8; ++u) x[u] = zero ? 0.f : (float)v[u];
+  }
+};
+template <> struct F8Raw<float> {
+  f32x4 a, b;
+  __device__ __forceinline__ void load(const float* p) {
+    a = *reinterpret_cast<const f32x4*>(p);
+    b = *reinterpret_cast<const f32x4*>(p + 4);
+  }
+  __device__ __forceinline__ void get(float* x, bool zero) const {
 #pragma unroll
-        for (int mq = 0; mq < 4; ++mq) {
-          const int d = dt * 32 + 4 * h + 8 * mq;
-          const f32x4 ov = {oacc[dt][4 * mq] * inv, oacc[dt][4 * mq + 1] * inv, oacc[dt][4 * mq + 2] * inv,
-                            oacc[dt][4 * mq + 3] * inv};
-          if constexpr (sizeof(T) == 2) *reinterpret_cast<bf16x4*>(orow + d) = bf16x4{(bf16)ov[0], (bf16)ov[1], (bf16)ov[2], (bf16)ov[3]};
-          else *reinterpret_cast<f32x4*>(orow + d) = ov;
-        }
-      if (h == 0 && lse) lse[(int64_t)bh * N + q] = (mc + __log2f(l)) * LN2;
+    for (int u = 0; u < 4; ++u) { x[u] = zero ? 0.f : a[u]; x[4 + u] = zero ? 0.f : b[u]; }
+  }
+};
+template <typename T> struct F8Piece { F8Raw<T> k, v; };
+
+// this thread's pieces of keys [j0, j0 + 64), rows clamped to N - 1.  K: key j0 + tid / 8, head dims 8 (tid % 8) ..;
+// V: key j0 + lane, head dims 8 wave ..
+template <typename T>
+__device__ __forceinline__ void f8s_fetch_k(F8Piece<T>& p, const T* base, int64_t ld_qkv, int D, int j0, int N) {
+  const int tid = threadIdx.x;
+  p.k.load(base + (int64_t)min(j0 + (tid >> 3), N - 1) * ld_qkv + D + (tid & 7) * 8);
+}
+template <typename T>
+__device__ __forceinline__ void f8s_fetch_v(F8Piece<T>& p, const T* base, int64_t ld_qkv, int D, int j0, int N) {
+  const int tid = threadIdx.x;
+  p.v.load(base + (int64_t)min(j0 + (tid & 63), N - 1) * ld_qkv + 2 * D + (tid >> 6) * 8);
+}
+// quantise the pieces into buffer buf: attn_fwd_fp8's bytes and scale bytes for these keys
+template <typename T>
+__device__ __forceinline__ void f8s_commit(unsigned char* buf, const F8Piece<T>& p, int j0, int N) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float x[8];
+  {  // K: 8 adjacent lanes hold a key's row
+    const int key = tid >> 3, c = tid & 7;
+    p.k.get(x, j0 + key >= N);
+    float amax = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) amax = fmaxf(amax, fabsf(x[u]));
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+    amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
+    const int e = e8m0_exp(amax);
+    const float inv = inv_exp2i(e);
+    typedef int i32x2_ __attribute__((ext_vector_type(2)));
+    *reinterpret_cast<i32x2_*>(buf + f8_koff(key, c >> 1) + (c & 1) * 8) =
+        i32x2_{pack_fp8x4(x[0] * inv, x[1] * inv, x[2] * inv, x[3] * inv),
+               pack_fp8x4(x[4] * inv, x[5] * inv, x[6] * inv, x[7] * inv)};
+    if ((c & 3) == 0) buf[F8S_KSC + key * 2 + (c >> 2)] = (unsigned char)(e + 127);
+  }
+  {  // V: this lane's key, head dims 8 wave + i; the block maximum of each d over the wave's 64 keys
+    p.v.get(x, j0 + lane >= N);
+    // halve the values in flight at each of the first three exchanges: 7 shuffles, after which this lane holds
+    // the maximum of d = lane / 8 over the lanes that differ from it in bits 3..5; 3 more finish it
+    const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
+    float w4[4], w2[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float keep = fabsf(b5 ? x[4 + i] : x[i]), send = fabsf(b5 ? x[i] : x[4 + i]);
+      w4[i] = fmaxf(keep, __shfl_xor(send, 32, 64));
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const float keep = b4 ? w4[2 + i] : w4[i], send = b4 ? w4[i] : w4[2 + i];
+      w2[i] = fmaxf(keep, __shfl_xor(send, 16, 64));
+    }
+    float t = fmaxf(b3 ? w2[1] : w2[0], __shfl_xor(b3 ? w2[0] : w2[1], 8, 64));
+    t = fmaxf(t, __shfl_xor(t, 4, 64));
+    t = fmaxf(t, __shfl_xor(t, 2, 64));
+    t = fmaxf(t, __shfl_xor(t, 1, 64));
+    const int e = e8m0_exp(t);
+    if ((lane & 7) == 0) buf[F8S_VSC + wave * 8 + (lane >> 3)] = (unsigned char)(e + 127);
+    const int inv_bits = __float_as_int(inv_exp2i(e));  // of d = lane / 8: lane 8 i holds head dim i's
+    float y[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) y[i] = x[i] * __int_as_float(__builtin_amdgcn_readlane(inv_bits, 8 * i));
+    const int w0 = pack_fp8x4(y[0], y[1], y[2], y[3]), w1 = pack_fp8x4(y[4], y[5], y[6], y[7]);
+    unsigned char* col = buf + F8S_VT + (wave * 8) * F8S_VROW + lane;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      col[i * F8S_VROW] = (unsigned char)(w0 >> (8 * i));
+      col[(4 + i) * F8S_VROW] = (unsigned char)(w1 >> (8 * i));
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(F8_THREADS, 4) void attn_fwd_fp8_stream(const T* __restrict__ qkv, int64_t ld_qkv, int D,
+                                                                    int H, int N, float scale, T* __restrict__ o,
+                                                                    int64_t ld_o, float* __restrict__ lse,
+                                                                    int causal) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2][F8S_BUF];
+  const int bh = blockIdx.x, b = bh / H, hh = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const T* base = qkv + (int64_t)b * N * ld_qkv + hh * 64;
+  const int h = lane >> 5, l31 = lane & 31;
+  const int q0 = blockIdx.y * F8S_QB + wave * 32, q = q0 + l31;
+  i32x8 qf;
+  int qsc;
+  f8_q_frag<T>(base + (int64_t)min(q, N - 1) * ld_qkv, h, qf, qsc);
+  const int nc = (N + F8S_CH - 1) / F8S_CH;
+  F8Piece<T> pc;
+  f8s_fetch_k<T>(pc, base, ld_qkv, D, 0, N);
+  f8s_fetch_v<T>(pc, base, ld_qkv, D, 0, N);
+  f8s_commit<T>(smem[0], pc, 0, N);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  float m = -INFINITY, l = 0.f;
+  f32x16 oacc[2] = {};
+  const bool live = q0 < N;  // wave-uniform; the trip count below does not depend on it
+  constexpr bool V_EARLY = sizeof(T) == 2;
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const unsigned char* buf = smem[c & 1];
+    const int j0 = c * F8S_CH;
+    const bool more = c + 1 < nc;  // the same in every wave of the workgroup
+    if (more) {
+      f8s_fetch_k<T>(pc, base, ld_qkv, D, j0 + F8S_CH, N);
+      if constexpr (V_EARLY) f8s_fetch_v<T>(pc, base, ld_qkv, D, j0 + F8S_CH, N);
+    }
+    if (live)
+      f8_tile_step(buf, buf + F8S_KSC, buf + F8S_VT, F8S_VROW, buf + F8S_VSC, 1, j0, N, q, causal, qf, qsc, c2, h, l31,
+                   m, l, oacc);
+    if (more) {
+      if constexpr (!V_EARLY) f8s_fetch_v<T>(pc, base, ld_qkv, D, j0 + F8S_CH, N);
+      f8s_commit<T>(smem[(c + 1) & 1], pc, j0 + F8S_CH, N);
+    }
+    __syncthreads();
+  }
+  if (!live) return;
+  l += __shfl_xor(l, 32, 64);
+  if (q < N)
+    f8_store<T>(o + ((int64_t)b * N + q) * ld_o + hh * 64, lse ? lse + (int64_t)bh * N + q : nullptr, oacc, l, m * c2, h);
 }
 
 // qkv-bias gradient partials of one (b, h): sum this workgroup's rows of dq (or dk, dv)
@@ -1958,6 +2153,7 @@ __global__ __launch_bounds__(256) void attn_bias_image(const bf16* __restrict__ 
 static int g_long_mode = -1;
 static int g_long_count = 0;      // bf16 streamed calls
 static int g_long_f32_count = 0;  // f32 streamed calls
+static int g_fp8_stream_count = 0;  // vit_sdpa_fwd_fp8_stream calls
 static bool attn_long_stream() {
   if (g_long_mode >= 0) return g_long_mode != 0;
   static const int v = [] { const char* e = getenv("VIT_ATTN_LONG"); return e && *e == '0' ? 0 : 1; }();
@@ -2264,6 +2460,33 @@ int vit_sdpa_fwd_fp8(int dtype, int B, int H, int N, int head_dim, const void* q
   }
   VIT_CHECK_LAUNCH();
   return 0;
+}
+
+// The streamed form of vit_sdpa_fwd_fp8 (attn_fwd_fp8_stream): any N >= 1, the same refusals otherwise; up to
+// 320 tokens the same bits.  Callers choose it (ops.sdpa_fwd's fp8_long past 320 tokens); nothing falls into it.
+int vit_sdpa_fwd_fp8_stream(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o,
+                            int64_t ld_o, float* lse, float scale, int causal, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (head_dim != 64 || N <= 0 || (ld_qkv % 8) || (ld_o % 4)) return (int)hipErrorInvalidValue;
+  if (dtype != VIT_BF16 && dtype != VIT_F32) return (int)hipErrorInvalidValue;
+  const int D = H * 64;
+  const dim3 grid(B * H, (N + F8S_QB - 1) / F8S_QB);
+  if (grid.y > 65535) return (int)hipErrorInvalidValue;
+  if (dtype == VIT_BF16)
+    hipLaunchKernelGGL(attn_fwd_fp8_stream<bf16>, grid, dim3(F8_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
+                       (bf16*)o, ld_o, lse, causal);
+  else
+    hipLaunchKernelGGL(attn_fwd_fp8_stream<float>, grid, dim3(F8_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
+                       scale, (float*)o, ld_o, lse, causal);
+  VIT_CHECK_LAUNCH();
+  ++g_fp8_stream_count;
+  return 0;
+}
+// Host-side count of vit_sdpa_fwd_fp8_stream calls that launched (reset != 0 zeroes it after reading).
+int vit_sdpa_fp8_stream_count(int reset) {
+  const int c = g_fp8_stream_count;
+  if (reset) g_fp8_stream_count = 0;
+  return c;
 }
 
 // SDPA backward: writes dq/dk/dv into dqkv (same column layout as qkv).

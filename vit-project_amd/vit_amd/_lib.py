@@ -61,6 +61,8 @@ SIGNATURES = {
     "vit_layer_norm_bwd_variant": [i32],
     "vit_sdpa_fwd": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, i32, vp],
     "vit_sdpa_fwd_fp8": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, i32, vp],
+    "vit_sdpa_fwd_fp8_stream": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, i32, vp],
+    "vit_sdpa_fp8_stream_count": [i32],
     "vit_sdpa_fwd_cls": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, vp],
     "vit_sdpa_cls_count": [i32],
     "vit_sdpa_bwd_variant": [i32],

@@ -268,6 +268,7 @@ class CLIP(nn.Module):
         self._shadows = None
         self._text_cache = None
         self.attention_fp8 = False  # set_attention_fp8
+        self.attention_fp8_long = False
         self.initialize_parameters()
 
     @torch.no_grad()
@@ -310,18 +311,22 @@ class CLIP(nn.Module):
                 self._shadows.add(p, T)
         self._shadows.refresh()
 
-    def set_attention_fp8(self, enable: bool = True):
+    def set_attention_fp8(self, enable: bool = True, long_sequences: bool = False):
         """Block-scaled e4m3 attention (vit_sdpa_fwd_fp8, BASELINE configs[4]) in every block whose
         forward needs no backward: the frozen blocks in front of the first trainable one in each
         tower (CLIP-HBA trains only the DoRA blocks 22-23 / 11, NEWP:484-544) and all blocks of a
         no-grad pass (evaluation, behavioural RSA).  Trainable blocks keep bf16/f32 attention.
-        The fp8 kernel holds at most 320 tokens: on ``ViT-L/14@336px`` (577 visual tokens) a forward
-        with fp8 attention enabled raises ``ValueError``; leave it off there."""
+        The resident fp8 kernel holds at most 320 tokens: on ``ViT-L/14@336px`` (577 visual tokens) a
+        forward with fp8 attention enabled raises ``ValueError`` unless ``long_sequences`` is set, which
+        sends lengths past 320 to the streamed fp8 kernel (vit_sdpa_fwd_fp8_stream; shorter ones, the text
+        tower's 77 among them, keep the resident kernel).  ``set_attention_fp8(False)`` clears both."""
         self.attention_fp8 = bool(enable)
+        self.attention_fp8_long = bool(enable) and bool(long_sequences)
 
     def _cfg(self, heads, causal, frozen=False):
         fp8 = self.attention_fp8 and (frozen or not torch.is_grad_enabled())
-        return dict(heads=heads, eps=1e-5, quick_gelu=True, dtype=self.compute_dtype, causal=causal, attn_fp8=fp8)
+        return dict(heads=heads, eps=1e-5, quick_gelu=True, dtype=self.compute_dtype, causal=causal, attn_fp8=fp8,
+                    attn_fp8_long=self.attention_fp8_long)
 
     # -- towers -----------------------------------------------------------------
     def _visual_stem(self, image, pos_embedding):
@@ -449,7 +454,7 @@ class CLIP(nn.Module):
                                       "CLIP-HBA path (switch_dora_layers freezes them, NEWP:516-544)")
         params = emb + [p for b in blocks[:k] for p in b.parameters()]
         key = (text.data_ptr(), text._version, tuple(text.shape), k, self.compute_dtype, self.attention_fp8,
-               tuple((p.data_ptr(), p._version) for p in params))
+               self.attention_fp8_long, tuple((p.data_ptr(), p._version) for p in params))
         if self.cache_frozen_text and self._text_cache is not None and self._text_cache[0] == key:
             return self._text_cache[1], k
         S, Lq = text.shape
@@ -536,7 +541,8 @@ class CLIPHBA(nn.Module):
     ``backbone_name`` and :func:`tokenize` ids are used (no network)."""
 
     def __init__(self, classnames, backbone_name="ViT-L/14", pos_embedding=False, clip_model=None,
-                 tokenized_prompts=None, compute_dtype=torch.float32, attention_fp8=False):
+                 tokenized_prompts=None, compute_dtype=torch.float32, attention_fp8=False,
+                 attention_fp8_long=False):
         super().__init__()
         self.num_clip = len(classnames)
         if clip_model is None:
@@ -547,7 +553,7 @@ class CLIPHBA(nn.Module):
         self.clip_model = clip_model
         self.clip_model.float()
         if attention_fp8:  # BASELINE configs[4]: fp8 attention in the frozen / no-grad blocks
-            self.clip_model.set_attention_fp8(True)
+            self.clip_model.set_attention_fp8(True, long_sequences=attention_fp8_long)
         self.pos_embedding = pos_embedding
         for p in self.clip_model.parameters():
             p.requires_grad = False

@@ -310,8 +310,9 @@ def _block_chain(x, params, cfg, fwd_only):
     Wqkv, Wproj, W1, W2 = _wt(qkvw, T), _wt(projw, T), _wt(fc1w, T), _wt(fc2w, T)
     causal = bool(cfg.get("causal", False))
     attn_fp8 = bool(cfg.get("attn_fp8", False))  # forward-only blocks (frozen prefix, no-grad passes)
+    attn_fp8_long = bool(cfg.get("attn_fp8_long", False))  # past 320 tokens: the streamed fp8 kernel
     if attn_fp8:
-        ops.check_fp8_tokens(N)  # before anything is queued on the side stream
+        ops.check_fp8_tokens(N, long=attn_fp8_long)  # before anything is queued on the side stream
 
     # fused residual adds (bf16 ViT, VisionTransformer._tokens): proj / fc2 store their bf16 output
     # (bias included) and the add into the f32 stream runs inside the next LayerNorm -- norm2 here,
@@ -347,7 +348,7 @@ def _block_chain(x, params, cfg, fwd_only):
             ln1(sl),
             lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
-                                 fp8=attn_fp8),
+                                 fp8=attn_fp8, fp8_long=attn_fp8_long),
             lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), out=pb[sl]),
             lambda: ops.add_layer_norm_fwd(x2[sl], pb[sl], xm[sl], n2w.detach(), n2b.detach(), eps, out=h2[sl],
                                            mean=m2[sl], rstd=r2[sl]),
@@ -401,7 +402,7 @@ def _block_chain(x, params, cfg, fwd_only):
                                        rstd=r1[sl]),
             lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
-                                 fp8=attn_fp8),
+                                 fp8=attn_fp8, fp8_long=attn_fp8_long),
             lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), epi=L.EPI_RESID, resid=x2[sl], out=xm[sl]),
             lambda: ops.layer_norm_fwd(xm[sl], n2w.detach(), n2b.detach(), eps, T, out=h2[sl], mean=m2[sl],
                                        rstd=r2[sl]),
@@ -801,6 +802,7 @@ class VisionTransformer(nn.Module):
         self._shadows = None
         self._defer_grad_join = False
         self._attn_fp8 = False
+        self._attn_fp8_long = False
         self.init_weights()
 
     # timm init_weights_vit_timm; exact RNG stream differs from timm
@@ -875,11 +877,17 @@ class VisionTransformer(nn.Module):
         with gradient hooks, which read ``.grad`` during the backward on the caller's stream."""
         self._defer_grad_join = bool(enable)
 
-    def set_attention_fp8(self, enable: bool = True):
+    def set_attention_fp8(self, enable: bool = True, long_sequences: bool = False):
         """Run attention as block-scaled e4m3 MFMA (vit_sdpa_fwd_fp8) in forward passes that build no
         autograd graph (``torch.no_grad()``: validation, ``compute_rsa_score``'s embeddings) --
-        BASELINE configs[4].  Training forwards keep the bf16 kernels their backward needs."""
+        BASELINE configs[4].  Training forwards keep the bf16 kernels their backward needs.
+
+        The resident fp8 kernel holds at most 320 tokens: past that (the 384-pixel and patch-8 models) such a
+        forward raises ``ValueError`` unless ``long_sequences`` is set, which sends those lengths to the streamed
+        fp8 kernel (vit_sdpa_fwd_fp8_stream; up to 320 tokens the resident kernel runs either way).
+        ``set_attention_fp8(False)`` clears both switches."""
         self._attn_fp8 = bool(enable)
+        self._attn_fp8_long = bool(enable) and bool(long_sequences)
 
     def set_grad_ready_hook(self, fn):
         """fn(lo, hi) is called by each block's backward once the block's gradients (the flat
@@ -917,6 +925,7 @@ class VisionTransformer(nn.Module):
         hook = getattr(self, "_grad_hook", None) if cfg["defer_bwd_join"] else None
         # fp8 attention (set_attention_fp8): forward passes that build no graph (eval / RSA)
         cfg["attn_fp8"] = self._attn_fp8 and not torch.is_grad_enabled()
+        cfg["attn_fp8_long"] = self._attn_fp8_long
         D = self.embed_dim
         if (self.compute_dtype != torch.float32 or _FUSED_RESID_F32[0]) and ops.add_layer_norm_supported(D):
             cfg["resid"] = {"pending": None}  # residual adds inside the LayerNorms (_BlockFn.forward)

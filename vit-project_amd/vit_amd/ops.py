@@ -475,28 +475,47 @@ def layer_norm_bwd(x, ldx, dy, w, mean, rstd, dx, lddx, rows, dres=None, ldres=0
 FP8_ATTN_MAX_TOKENS = 320  # vit_sdpa_fwd_fp8 holds the head's quantised K and V in LDS
 
 
-def check_fp8_tokens(N):
-    """The fp8 attention kernel has no streamed form: refuse, never fall back to another precision."""
-    if N > FP8_ATTN_MAX_TOKENS:
+def check_fp8_tokens(N, long=False):
+    """The resident fp8 attention kernel holds at most 320 tokens; past that the streamed fp8 kernel runs only
+    when asked for (``long``): otherwise refuse, never fall back to another precision."""
+    if N > FP8_ATTN_MAX_TOKENS and not long:
         raise ValueError(f"fp8 attention (vit_sdpa_fwd_fp8) supports at most {FP8_ATTN_MAX_TOKENS} tokens, got "
-                         f"{N}: switch it off (set_attention_fp8(False)) for this model")
+                         f"{N}: switch it off (set_attention_fp8(False)) for this model, or ask for the streamed "
+                         f"fp8 kernel (set_attention_fp8(True, long_sequences=True))")
 
 
-def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=False):
+def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=False, fp8_long=False):
     """softmax(q k^T * scale) v per (b, h) from the fused qkv [B*N, 3D], any N (past 288 tokens the
     streamed bf16 or f32 kernels, or the generic ones for causal / misaligned rows); fp8: the block-scaled e4m3
-    MFMA kernel (forward only: its lse is not the bf16 backward's; N <= 320)."""
+    MFMA kernels (forward only: their lse is not the bf16 backward's) -- the resident one up to 320 tokens,
+    past that the streamed one if ``fp8_long``, else ValueError."""
     if fp8:
-        check_fp8_tokens(N)
+        check_fp8_tokens(N, long=fp8_long)
     D = H * 64
     if o is None:
         o = torch.empty(B * N, D, dtype=qkv2d.dtype, device=qkv2d.device)
     if lse is None:
         lse = torch.empty(B * H * N, dtype=torch.float32, device=qkv2d.device)
     scale = 64 ** -0.5 if scale is None else scale
-    name = "vit_sdpa_fwd_fp8" if fp8 else "vit_sdpa_fwd"
+    name = "vit_sdpa_fwd"
+    if fp8:
+        name = "vit_sdpa_fwd_fp8" if N <= FP8_ATTN_MAX_TOKENS else "vit_sdpa_fwd_fp8_stream"
     call(name, L.dt(qkv2d), B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(o), o.stride(0), ptr(lse),
          float(scale), int(causal), _s(qkv2d))
+    return o, lse
+
+
+def sdpa_fwd_fp8_stream(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False):
+    """The streamed fp8 forward (vit_sdpa_fwd_fp8_stream) at any N, for tests and tools: up to 320 tokens its o
+    and lse are bit for bit the resident fp8 kernel's."""
+    D = H * 64
+    if o is None:
+        o = torch.empty(B * N, D, dtype=qkv2d.dtype, device=qkv2d.device)
+    if lse is None:
+        lse = torch.empty(B * H * N, dtype=torch.float32, device=qkv2d.device)
+    scale = 64 ** -0.5 if scale is None else scale
+    call("vit_sdpa_fwd_fp8_stream", L.dt(qkv2d), B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(o), o.stride(0),
+         ptr(lse), float(scale), int(causal), _s(qkv2d))
     return o, lse
 
 

@@ -8,8 +8,8 @@ device, and hands a batch's rows to ``CLIPHBA.forward(visual_prefix=...)`` throu
 (``ops.gather_blocks``).  Opt-in: nothing here runs unless a caller builds a cache.
 
 The key follows ``CLIP._text_prefix``: ``(data_ptr, _version)`` of the stem's and the frozen blocks'
-parameters, the cut, the compute dtype, the fp8-attention switch, ``pos_embedding`` and the images'
-``(data_ptr, _version, shape)``.  The cache holds references to those tensors, so an address in the key
+parameters, the cut, the compute dtype, the fp8-attention switch, ``pos_embedding``, the images'
+``(data_ptr, _version, shape)`` and the streamed-fp8 switch (``long_sequences``).  The cache holds references to those tensors, so an address in the key
 cannot come back as another tensor while the cache lives.  ``valid_for`` recomputes the key; a stale
 cache is rebuilt by ``ensure`` (the sweep calls it before every condition), never read.
 """
@@ -54,7 +54,8 @@ def prefix_key(model, images):
     cm = m.clip_model
     first = frozen_visual_blocks(m)
     return (tuple((p.data_ptr(), p._version) for p in _frozen_tensors(cm, first)), first, cm.compute_dtype,
-            bool(cm.attention_fp8), bool(m.pos_embedding), (images.data_ptr(), images._version, tuple(images.shape)))
+            bool(cm.attention_fp8), bool(m.pos_embedding), (images.data_ptr(), images._version, tuple(images.shape)),
+            bool(cm.attention_fp8_long))
 
 
 class VisualPrefixCache:

@@ -43,7 +43,8 @@ int vit_abi_version(void); /* 10 (round 6): vit_blaslt_workspace / vit_gemm_lib 
                               * gemm_g4.hip), the library links no vendor BLAS; 9: those two hooks (hipBLASLt);
                               * 8: vit_gemm_ms / vit_gemm_ms_config and the banded attention backward removed.
                               * Additive to 10 (no entry point or argument changed): the act-only epilogue codes
-                              * VIT_EPI_BIAS_GELU_FWD / VIT_EPI_BIAS_QGELU_FWD and vit_eval_metrics */
+                              * VIT_EPI_BIAS_GELU_FWD / VIT_EPI_BIAS_QGELU_FWD, vit_eval_metrics, and the LoRA weight
+                              * build vit_lora_weight_fwd / _bwd / _bwd_ws_floats */
 
 /* Generic MFMA GEMM C[i][j] = epi(sum_r P(i,r) Q(j,r)); layouts RC (r contiguous)
  * or CR (i/j contiguous).  Backs every nn.Linear of timm's ViT reached from
@@ -329,6 +330,22 @@ int vit_dora_weight_bwd_ws(int in, int out, int r, const float* m, const float* 
                            float* sdDnT_ws, float* slabs, int64_t slab_floats, const float* noise, void* stream);
 int vit_gemm_splitk(int p_layout, int q_layout, int M, int N, int R, const float* P, int64_t ldp, const float* Q,
                     int64_t ldq, float* C, float* slabs, int64_t slab_floats, void* stream);
+/* LoRALayer.weight (NEWP:330-332) and its backward (additive to ABI 10; csrc/lora.hip):
+ *   W[i][j] = W0[i][j] + scaling * sum_k B[i][k] A[k][j]     W0, W [n, n], B [n, r], A [r, n], f32 row-major.
+ * The reference adds B @ A ([in, out]) to W0 ([out, in]) without a transpose: the property exists only for
+ * in == out = n and is not the weight LoRALayer.forward applies; nn.MultiheadAttention reads out_proj.weight
+ * (quirk Q5), so on the CLIP-HBA path it is the weight that trains.  One launch; 1 <= r <= 64, any n >= 1
+ * (16-byte loads / stores along j when n % 4 == 0 and W0, A, W are 16-byte aligned, scalar otherwise).
+ * Backward, gW = dL/dW [n, n]:  dA [r, n] = scaling * B^T gW,  dB [n, r] = scaling * gW A^T, both overwritten
+ * (dW0 = gW is the caller's).  gW is read once in 64 x 64 tiles; each tile's shares of dA and dB go to ws and
+ * a second launch sums them in tile order: no atomics, the same bits on every run.  1 <= n <= 16384;
+ * ws holds vit_lora_weight_bwd_ws_floats(n, r) = 2 * ceil(n / 64) * r * n floats (host-only query, 0 for
+ * arguments the backward rejects) and is 16-byte aligned.  hipErrorInvalidValue for r or n out of range. */
+int vit_lora_weight_fwd(int n, int r, const float* W0, const float* A, const float* B, float scaling, float* W,
+                        void* stream);
+int vit_lora_weight_bwd(int n, int r, const float* A, const float* B, const float* gW, float scaling, float* dA,
+                        float* dB, float* ws, void* stream);
+int vit_lora_weight_bwd_ws_floats(int n, int r);
 /* torch.optim.AdamW step (NEWP:1181, NEWP:1001): tensors {float* p; const float* g; float* exp_avg;
  * float* exp_avg_sq; bf16* shadow (or null); int64 n; const float* coef}[] where coef points at
  * the tensor's {step_size, bc2_sqrt, decay, 0} in device memory: step_size = lr / (1 - beta1^step),

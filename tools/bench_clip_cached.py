@@ -18,6 +18,10 @@ failure stops the run, and the GPU clocks ``rocm-smi --showclocks`` reports are 
 Records go to --out (one JSON file per leg).
 
     python tools/bench_clip_cached.py [--out profiles/r13] [--rounds 3] [--steps 8] [--leg f32|bf16|gather]
+                                      [--adapter dora|lora]
+
+``--adapter lora`` puts the reference's LoRA pair (NEWP:339-404) where DoRA stands; its records are named
+``bench_clip_cached_lora_{dtype}.json``.
 """
 import argparse
 import json
@@ -59,8 +63,12 @@ def model_leg(a, dtype_name):
     dtype = {"f32": torch.float32, "bf16": torch.bfloat16}[dtype_name]
     torch.manual_seed(0)
     m = vit_amd.CLIPHBA([f"c{i}" for i in range(66)], "ViT-L/14", pos_embedding=True, compute_dtype=dtype)
-    vit_amd.apply_dora_to_ViT(m, n_vision_layers=2, n_transformer_layers=1, r=32)
-    vit_amd.switch_dora_layers(m, freeze_all=True, dora_state=True)
+    if a.adapter == "lora":
+        vit_amd.apply_lora_to_ViT(m, n_vision_layers=2, n_transformer_layers=1, r=32)
+        vit_amd.unfreeze_lora_layers(m, freeze_all=True)
+    else:
+        vit_amd.apply_dora_to_ViT(m, n_vision_layers=2, n_transformer_layers=1, r=32)
+        vit_amd.switch_dora_layers(m, freeze_all=True, dora_state=True)
     m = m.to(dev)
     opt = vit_amd.FusedAdamW([p for p in m.parameters() if p.requires_grad], lr=3e-4)
     crit = vit_amd.MSELoss()
@@ -144,7 +152,8 @@ def model_leg(a, dtype_name):
         steps(False, 2)
     th.join()
     sync()
-    rec = {"metric": "CLIP-HBA ViT-L/14 + DoRA (config C3), frozen visual prefix cached vs uncached, one process",
+    rec = {"metric": f"CLIP-HBA ViT-L/14 + {'LoRA' if a.adapter == 'lora' else 'DoRA'} (config C3), frozen visual "
+                     "prefix cached vs uncached, one process", "adapter": a.adapter,
            "clocks_under_load": load_clocks,
            "dtype": dtype_name, "batch": a.batch, "steps_per_round": a.steps, "rounds": a.rounds,
            "train_images": a.train, "cache_rows": rows, "cache_gib": round(sum(c.nbytes for c in caches.values()) / 2 ** 30, 3),
@@ -219,7 +228,7 @@ def driver(a):
     for leg in a.legs.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--out", a.out, "--rounds", str(a.rounds),
                "--steps", str(a.steps), "--warmup", str(a.warmup), "--batch", str(a.batch), "--train", str(a.train),
-               "--gather-rows", str(a.gather_rows), "--gather-calls", str(a.gather_calls)]
+               "--gather-rows", str(a.gather_rows), "--gather-calls", str(a.gather_calls), "--adapter", a.adapter]
         print("leg", leg, flush=True)
         rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale).returncode  # TimeoutExpired ends the run
         if rc != 0:
@@ -244,6 +253,8 @@ def main():
     ap.add_argument("--gather-rows", type=int, default=512)
     ap.add_argument("--gather-calls", type=int, default=100)
     ap.add_argument("--timeout-scale", type=float, default=1.0)
+    ap.add_argument("--adapter", choices=["dora", "lora"], default="dora",
+                    help="the adapter on the three out_proj layers: DoRA (config C3) or the reference's LoRA pair")
     a = ap.parse_args()
     if a.rounds < 3:
         ap.error("--rounds must be at least 3: the spread is part of the record")
@@ -251,7 +262,8 @@ def main():
         sys.exit(driver(a))
     rec = gather_leg(a) if a.leg == "gather" else model_leg(a, a.leg)
     os.makedirs(a.out, exist_ok=True)
-    name = "gather_blocks.json" if a.leg == "gather" else f"bench_clip_cached_{a.leg}.json"
+    tag = "" if a.adapter == "dora" else f"_{a.adapter}"
+    name = "gather_blocks.json" if a.leg == "gather" else f"bench_clip_cached{tag}_{a.leg}.json"
     with open(os.path.join(a.out, name), "w") as fh:
         json.dump(rec, fh, indent=1)
     print(json.dumps(rec), flush=True)

@@ -9,6 +9,7 @@ from .model import (VisionTransformer, create_model, cross_entropy, set_wgrad_ov
 from .pos_embed import resample_abs_pos_embed, adapt_state_dict
 from .optim import FusedSGD, FusedAdamW, CosineAnnealingLRWithWarmup
 from .dora import DoRALayer, dora_weight
+from .lora import LoRALayer, lora_weight
 from . import rsa
 from . import clip
 from . import prefix_cache
@@ -18,12 +19,13 @@ from . import data
 from . import evaluate
 from .evaluate import EvalMeter, validate
 from .clip import CLIPHBA, MSELoss, mse_loss, apply_dora_to_ViT, switch_dora_layers, count_trainable_parameters
+from .clip import apply_lora_to_ViT, unfreeze_lora_layers
 
 __all__ = ["VisionTransformer", "create_model", "cross_entropy", "set_wgrad_overlap", "FusedSGD", "FusedAdamW",
            "CosineAnnealingLRWithWarmup", "DoRALayer", "dora_weight", "rsa", "clip", "data", "CLIPHBA", "MSELoss",
            "mse_loss", "apply_dora_to_ViT", "switch_dora_layers", "count_trainable_parameters", "set_forward_only",
            "set_cls_tail", "block_forward_only", "evaluate", "EvalMeter", "validate", "resample_abs_pos_embed", "adapt_state_dict",
-           "prefix_cache", "VisualPrefixCache"]
+           "prefix_cache", "VisualPrefixCache", "LoRALayer", "lora_weight", "apply_lora_to_ViT", "unfreeze_lora_layers"]
 
 
 def load_library(path=None):

@@ -46,6 +46,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .dora import DoRALayer
+from .lora import LoRALayer
 from .model import _FUSED_RESID_F32, _BlockFn, _Shadowed, _gout, _wt, run_block
 
 SOT, EOT = 49406, 49407
@@ -609,6 +610,42 @@ def switch_dora_layers(model, freeze_all=True, dora_state=True):
                     child.delta_D_B.requires_grad = dora_state
                     if child.bias is not None:
                         child.bias.requires_grad = False
+                else:
+                    rec(child)
+        rec(model.module if isinstance(model, nn.DataParallel) else model)
+
+
+# ----------------------------------------------------------------------------
+# LoRA placement / freezing (NEWP:339-404, BASEP:225-290), the DoRA pair's siblings
+# ----------------------------------------------------------------------------
+
+def apply_lora_to_ViT(model, n_vision_layers=1, n_transformer_layers=1, r=8, lora_dropout=0.1):
+    """Replace ``attn.out_proj`` of the last n visual / text blocks with :class:`LoRALayer` (NEWP:339-373;
+    ``range(-n, 0)``, so n = 0 wraps nothing)."""
+    mm = model.module if isinstance(model, nn.DataParallel) else model
+    for idx in range(-n_vision_layers, 0):
+        blk = mm.clip_model.visual.transformer.resblocks[idx]
+        blk.attn.out_proj = LoRALayer(blk.attn.out_proj, r=r, lora_dropout=lora_dropout)
+    for idx in range(-n_transformer_layers, 0):
+        blk = mm.clip_model.transformer.resblocks[idx]
+        blk.attn.out_proj = LoRALayer(blk.attn.out_proj, r=r, lora_dropout=lora_dropout)
+    mm.clip_model._shadows = None  # the GEMM-weight registry changes with the modules
+
+
+def unfreeze_lora_layers(model, freeze_all=True):
+    """NEWP:376-404: every parameter to ``requires_grad = not freeze_all``; with ``freeze_all``, lora_A /
+    lora_B of each LoRA layer back on and its original layer's weight / bias off."""
+    for _, p in model.named_parameters():
+        p.requires_grad = not freeze_all
+    if freeze_all:
+        def rec(module):
+            for child in module.children():
+                if isinstance(child, LoRALayer):
+                    child.lora_A.requires_grad = True
+                    child.lora_B.requires_grad = True
+                    child.original_layer.weight.requires_grad = False
+                    if child.original_layer.bias is not None:
+                        child.original_layer.bias.requires_grad = False
                 else:
                     rec(child)
         rec(model.module if isinstance(model, nn.DataParallel) else model)

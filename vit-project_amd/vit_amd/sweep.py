@@ -61,13 +61,15 @@ def _module(model, path):
 
 
 def save_dora_parameters(model, dora_parameters_path, epoch, modules=DORA_MODULES):
-    """NEWP:657-694: one file per epoch, keys ``<path>.m``, ``.delta_D_A``, ``.delta_D_B`` (CPU tensors)."""
+    """NEWP:657-694: one file per epoch, keys ``<path>.m``, ``.delta_D_A``, ``.delta_D_B`` (CPU tensors).
+    A module that is a LoRA layer (it carries ``lora_A`` / ``lora_B``, NEWP:307-336) stores ``<path>.lora_A``
+    and ``<path>.lora_B`` instead, under the same file name, so the resume rules see no difference."""
     params = {}
     for path in modules:
         mod = _module(model, path)
-        params[f"{path}.m"] = mod.m.detach().cpu()
-        params[f"{path}.delta_D_A"] = mod.delta_D_A.detach().cpu()
-        params[f"{path}.delta_D_B"] = mod.delta_D_B.detach().cpu()
+        names = ("lora_A", "lora_B") if hasattr(mod, "lora_A") else ("m", "delta_D_A", "delta_D_B")
+        for name in names:
+            params[f"{path}.{name}"] = getattr(mod, name).detach().cpu()
     os.makedirs(dora_parameters_path, exist_ok=True)
     f = os.path.join(dora_parameters_path, f"epoch{epoch + 1}_dora_params.pth")
     torch.save(params, f)

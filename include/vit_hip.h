@@ -239,6 +239,31 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
 int vit_sdpa_fwd_cls(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o,
                      int64_t ld_o, float* lse, float scale, void* stream);
 int vit_sdpa_cls_count(int reset);
+/* One-query attention (additive to ABI 10): query row 0 of every image against all N keys and values, for the
+ * class-token tail of the CLIP visual tower (ln_post reads x[:, 0] alone).  VIT_BF16 or VIT_F32, head_dim 64,
+ * 1 <= N <= 2048; memory-bound K / V reads, f32 arithmetic, every reduction in a fixed order (two calls are
+ * bitwise equal), no atomics, no workspace.  The sums are ordered differently from the MFMA kernels': the
+ * results agree with vit_sdpa_fwd / vit_sdpa_bwd to rounding, not in bits.
+ *   fwd: s_j = scale * (q0 . k_j), lse = logsumexp_j s_j (natural log), o0 = sum_j softmax(s)_j v_j; K and V are
+ *        read once.  o_cls [B, D] in the qkv dtype, row b at b * ld_o (column h * 64) -- the dense o with
+ *        ld_o = N * D is a valid argument; lse_cls [B * H] f32.
+ *   bwd: p_j = exp(s_j - lse), delta = dO0 . o0 (computed in the kernel), ds_j = p_j (dO0 . v_j - delta).  Writes
+ *        every element of dqkv [B*N, 3D] (qkv layout, qkv dtype): dq row 0 of each image = scale sum_j ds_j k_j,
+ *        dq rows 1 .. N-1 exact zeros, dk_j = scale ds_j q0 and dv_j = p_j dO0 for every row.  do_cls [B, D], row
+ *        b at b * ld_do.  K and V are read once.  No qkv bias partials are produced.  Consistency step: sum_j ds_j
+ *        is zero in exact arithmetic; o0 arrives rounded to the dtype, which shifts delta and leaves a remainder
+ *        r that a common offset of the keys multiplies into dq.  The kernel takes it back out with what it has
+ *        summed by then: ds_j -= p_j r / sum_j p_j (dk_j is written from the corrected values, held in LDS: two
+ *        floats a key, hence the bound on N).
+ * head_dim != 64, N <= 0 or N > 2048, ld_qkv / ld_dqkv < 3D, a null operand, or a row stride or address that is
+ * not a multiple of 16 bytes: hipErrorInvalidValue with nothing queued.
+ * vit_sdpa_cls1_count: host-side count of launches of either kernel (reset != 0 zeroes it after reading). */
+int vit_sdpa_cls1_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o_cls,
+                      int64_t ld_o, float* lse_cls, float scale, void* stream);
+int vit_sdpa_cls1_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv,
+                      const void* o_cls, int64_t ld_o, const void* do_cls, int64_t ld_do, const float* lse_cls,
+                      void* dqkv, int64_t ld_dqkv, float scale, void* stream);
+int vit_sdpa_cls1_count(int reset);
 /* fp8 scaled-dot-product attention forward (BASELINE configs[4]: the sweep's frozen CLIP tower blocks
  * and the RSA evaluation forward; replaces the same F.scaled_dot_product_attention call as
  * vit_sdpa_fwd): q/k/v quantised in-kernel to block-scaled OCP e4m3 (E8M0 scale per 32 values),

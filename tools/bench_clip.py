@@ -5,6 +5,10 @@ the default bench line carries in both dtypes).  Prints one JSON line.
 
 ``--adapter lora`` times the same step with the reference's LoRA pair (``apply_lora_to_ViT`` /
 ``unfreeze_lora_layers``, NEWP:339-404) in place of the DoRA pair; ``dora`` (the default) is bench.py's leg itself.
+
+``--cls-tail`` times the step with the visual tower's class-token tail (``CLIP.set_cls_tail``) off
+and on, alternated on one model in one process over ``--rounds`` rounds (>= 3): medians, the round-to-round
+spread ``(max - min) / median``, the ratio, and the on-against-off relative difference of the predictions.
 """
 import argparse
 import json
@@ -57,6 +61,66 @@ def lora_leg(dev, dtype, batch, steps, warmup):
             "final_loss": round(float(loss.item()), 4)}
 
 
+def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds):
+    """The C3 step (bench.c3_leg's model, data and optimizer) with the class-token tail off and on, alternated."""
+    import statistics
+    import torch
+    import vit_amd
+    T = torch.float32 if dtype == "f32" else torch.bfloat16
+    torch.manual_seed(0)
+    m = vit_amd.CLIPHBA(["class%d" % i for i in range(66)], "ViT-L/14", pos_embedding=True, compute_dtype=T)
+    if adapter == "lora":
+        vit_amd.apply_lora_to_ViT(m, n_vision_layers=2, n_transformer_layers=1, r=32)
+        vit_amd.unfreeze_lora_layers(m, freeze_all=True)
+    else:
+        vit_amd.apply_dora_to_ViT(m, n_vision_layers=2, n_transformer_layers=1, r=32)
+        vit_amd.switch_dora_layers(m, freeze_all=True, dora_state=True)
+    m = m.to(dev)
+    opt = vit_amd.FusedAdamW([p for p in m.parameters() if p.requires_grad], lr=3e-4)
+    x = torch.randn(batch, 3, 224, 224, device=dev)
+    y = torch.randn(batch, 66, device=dev) * 0.5 + 1.0
+
+    def window(n):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(n):
+            opt.zero_grad(set_to_none=True)
+            loss = vit_amd.mse_loss(m(x), y)
+            loss.backward()
+            opt.step()
+        ev[1].record()
+        torch.cuda.synchronize(dev)
+        assert torch.isfinite(loss)
+        return ev[0].elapsed_time(ev[1]) / n
+
+    preds = {}
+    for on in (False, True):  # the same parameters: before any step moves them
+        m.clip_model.set_cls_tail(on)
+        with torch.no_grad():
+            preds[on] = m(x).double()
+    for on in (False, True):
+        m.clip_model.set_cls_tail(on)
+        window(warmup)
+    ms = {False: [], True: []}
+    for _ in range(rounds):
+        for on in (False, True):
+            m.clip_model.set_cls_tail(on)
+            ms[on].append(window(steps))
+    m.clip_model.set_cls_tail(False)
+
+    def summary(v):
+        med = statistics.median(v)
+        return {"rounds": [round(t, 3) for t in v], "median": round(med, 3), "spread": round((max(v) - min(v)) / med, 4)}
+
+    off, on = summary(ms[False]), summary(ms[True])
+    return {"ms_per_step": {"cls_tail_off": off, "cls_tail_on": on}, "cls_tail_speedup": round(off["median"] / on["median"], 4),
+            "images_per_sec": {"cls_tail_off": round(batch / off["median"] * 1e3, 2),
+                               "cls_tail_on": round(batch / on["median"] * 1e3, 2)},
+            "prediction_rel_diff_on_vs_off": float((preds[True] - preds[False]).abs().max() / preds[False].abs().max()),
+            "prediction_bound": 1e-3 if dtype == "f32" else 3e-2,
+            "batch": batch, "steps": steps, "warmup": warmup, "rounds": rounds, "dtype": dtype}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -65,10 +129,18 @@ def main():
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="compute dtype: f32 = the reference's precision (NEWP:274), bf16 opt-in")
     ap.add_argument("--adapter", choices=["dora", "lora"], default="dora")
+    ap.add_argument("--cls-tail", action="store_true",
+                    help="alternate the visual tower's class-token tail off and on in one process")
+    ap.add_argument("--rounds", type=int, default=3, help="rounds of the --cls-tail alternation (>= 3)")
     a = ap.parse_args()
     import torch
-    leg = bench.c3_leg if a.adapter == "dora" else lora_leg
-    r = leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup)
+    if a.cls_tail:
+        if a.rounds < 3:
+            ap.error("--rounds must be at least 3: the spread is part of the record")
+        r = cls_tail_leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup, a.adapter, a.rounds)
+    else:
+        leg = bench.c3_leg if a.adapter == "dora" else lora_leg
+        r = leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup)
     r["metric"] = f"images/sec CLIP-HBA ViT-L/14 + {'DoRA' if a.adapter == 'dora' else 'LoRA'} train step (config C3)"
     r["adapter"] = a.adapter
     print(json.dumps(r))

@@ -20,6 +20,11 @@ Records go to --out (one JSON file per leg).
     python tools/bench_clip_cached.py [--out profiles/r13] [--rounds 3] [--steps 8] [--leg f32|bf16|gather]
                                       [--adapter dora|lora]
 
+``--cls-tail`` adds the visual tower's class-token tail (``CLIP.set_cls_tail``): every round runs
+uncached and cached with the tail off and then on, on the same model in the same process; the record gains the
+``*_tail`` series, ``cls_tail_speedup`` for the cached and the uncached pass and the on-against-off relative
+difference of a batch's predictions; the records are named ``bench_clip_cached_clstail_{dtype}.json``.
+
 ``--adapter lora`` puts the reference's LoRA pair (NEWP:339-404) where DoRA stands; its records are named
 ``bench_clip_cached_lora_{dtype}.json``.
 """
@@ -92,6 +97,15 @@ def model_leg(a, dtype_name):
         pred_diff = float((pc - pu).abs().max() / pu.abs().max())
 
     fixed = caches["train"].take(torch.arange(a.batch))
+    tails = (False, True) if a.cls_tail else (False,)
+    vname = lambda c, t: ("cached" if c else "uncached") + ("_tail" if t else "")
+    tail_diff = None
+    if a.cls_tail:  # the same batch's predictions with the tail on against off (cached pass)
+        with torch.no_grad():
+            m.clip_model.set_cls_tail(True)
+            pt = m(visual_prefix=caches["train"].take(idx)).double()
+            m.clip_model.set_cls_tail(False)
+        tail_diff = float((pt - pc).abs().max() / pc.abs().max())
 
     def steps(cached, n):
         m.train()
@@ -116,21 +130,27 @@ def model_leg(a, dtype_name):
         "rsa_48_seconds": lambda c: S.behavioral_rsa(m, data["inference"], data["reference_rdm"],
                                                      cache_visual_prefix=caches["inference"] if c else False),
     }
-    for c in (False, True):  # every shape of the timed windows, once
-        steps(c, a.warmup)
-        passes["evaluate_362_seconds"](c)
-        passes["rsa_48_seconds"](c)
-    res = {k: {"uncached": [], "cached": []} for k in passes}
+    for t in tails:  # every shape of the timed windows, once
+        m.clip_model.set_cls_tail(t)
+        for c in (False, True):
+            steps(c, a.warmup)
+            passes["evaluate_362_seconds"](c)
+            passes["rsa_48_seconds"](c)
+    res = {k: {vname(c, t): [] for t in tails for c in (False, True)} for k in passes}
     host_ms = {"uncached": [], "cached": []}
     no_gather = []
     for _ in range(a.rounds):
-        for name, c in (("uncached", False), ("cached", True)):
-            dt, loss = _timed(lambda: steps(c, a.steps), sync)
-            assert torch.isfinite(loss)
-            res["train_step_images_per_sec"][name].append(a.batch * a.steps / dt)
-            for k in ("evaluate_362_seconds", "rsa_48_seconds"):
-                dt, _ = _timed(lambda: passes[k](c), sync)
-                res[k][name].append(dt)
+        for t in tails:
+            m.clip_model.set_cls_tail(t)
+            for c in (False, True):
+                name = vname(c, t)
+                dt, loss = _timed(lambda: steps(c, a.steps), sync)
+                assert torch.isfinite(loss)
+                res["train_step_images_per_sec"][name].append(a.batch * a.steps / dt)
+                for k in ("evaluate_362_seconds", "rsa_48_seconds"):
+                    dt, _ = _timed(lambda: passes[k](c), sync)
+                    res[k][name].append(dt)
+        m.clip_model.set_cls_tail(False)
         dt, _ = _timed(lambda: steps("fixed", a.steps), sync)
         no_gather.append(a.batch * a.steps / dt)
     # the host's cost of queueing one step, the GPU idle when it starts (inside the windows above the index
@@ -167,6 +187,16 @@ def model_leg(a, dtype_name):
         u, c = _summary(v["uncached"]), _summary(v["cached"])
         ratio = c["median"] / u["median"] if k.endswith("per_sec") else u["median"] / c["median"]
         rec[k] = {"uncached": u, "cached": c, "cached_speedup": round(ratio, 3)}
+        if a.cls_tail:
+            gain = {}
+            for base in ("uncached", "cached"):
+                rec[k][base + "_tail"] = s = _summary(v[base + "_tail"])
+                b = rec[k][base]["median"]
+                gain[base] = round(s["median"] / b if k.endswith("per_sec") else b / s["median"], 4)
+            rec[k]["cls_tail_speedup"] = gain
+    if a.cls_tail:
+        rec["cls_tail_prediction_rel_diff"] = tail_diff
+        rec["cls_tail_prediction_bound"] = 1e-3 if dtype_name == "f32" else 3e-2
     rec["train_step_images_per_sec"]["cached_without_gather"] = _summary(no_gather)
     return rec
 
@@ -229,8 +259,10 @@ def driver(a):
         cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--out", a.out, "--rounds", str(a.rounds),
                "--steps", str(a.steps), "--warmup", str(a.warmup), "--batch", str(a.batch), "--train", str(a.train),
                "--gather-rows", str(a.gather_rows), "--gather-calls", str(a.gather_calls), "--adapter", a.adapter]
+        if a.cls_tail:
+            cmd.append("--cls-tail")
         print("leg", leg, flush=True)
-        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale).returncode  # TimeoutExpired ends the run
+        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if a.cls_tail else 1)).returncode  # TimeoutExpired ends the run
         if rc != 0:
             print(f"leg {leg} failed with exit code {rc}: stopping", flush=True)
             return rc
@@ -255,6 +287,8 @@ def main():
     ap.add_argument("--timeout-scale", type=float, default=1.0)
     ap.add_argument("--adapter", choices=["dora", "lora"], default="dora",
                     help="the adapter on the three out_proj layers: DoRA (config C3) or the reference's LoRA pair")
+    ap.add_argument("--cls-tail", action="store_true",
+                    help="also run every pass with the visual tower's class-token tail on, alternated with off")
     a = ap.parse_args()
     if a.rounds < 3:
         ap.error("--rounds must be at least 3: the spread is part of the record")
@@ -262,7 +296,7 @@ def main():
         sys.exit(driver(a))
     rec = gather_leg(a) if a.leg == "gather" else model_leg(a, a.leg)
     os.makedirs(a.out, exist_ok=True)
-    tag = "" if a.adapter == "dora" else f"_{a.adapter}"
+    tag = ("" if a.adapter == "dora" else f"_{a.adapter}") + ("_clstail" if a.cls_tail else "")
     name = "gather_blocks.json" if a.leg == "gather" else f"bench_clip_cached{tag}_{a.leg}.json"
     with open(os.path.join(a.out, name), "w") as fh:
         json.dump(rec, fh, indent=1)

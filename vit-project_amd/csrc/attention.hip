@@ -17,6 +17,10 @@
 // cross-lane shuffles; P stays in registers and feeds the PV MFMA as its
 // B-operand (k-slot permutation pi), V^T comes from ds_read_b64_tr_b16.
 // f32 path (parity mode): scalar-FMA online softmax.
+// one-query path (attn_cls1_*, the CLIP visual tower's class-token tail): query row 0 of every image alone,
+// K / V straight from HBM to registers, no MFMA -- see the block in front of attn_cls1_fwd.
+#include <initializer_list>
+
 #include "common.hpp"
 #include "reduce.hpp"
 
@@ -2321,6 +2325,172 @@ static int fwd_mfma_cls(const void* qkv, int64_t ld_qkv, int D, int B, int H, in
 }
 static int g_cls_count = 0;
 
+// ---------------------------------------------------------------------------
+// One-query attention (the class-token tail of the CLIP visual tower): query row 0 of every
+// image against all N keys and values, T = bf16 or float.  Memory-bound K / V reads with no reuse, so nothing
+// is staged in LDS: one workgroup per (b, h), 8 lanes per key, each lane holding 8 of the 64 head dims (one 16-B
+// load in bf16, two in f32), a wave 8 keys and the workgroup C1_GROUPS = 32 keys per step; f32 arithmetic
+// throughout.  Every sum has a fixed order -- 8 FMAs in the lane, three xor-shuffles across the key's 8 lanes,
+// keys g, g + 32, ... in sequence inside a lane group, then the 32 groups in index order through LDS -- so two
+// calls give the same bits.  No atomics, no workspace.
+// ---------------------------------------------------------------------------
+constexpr int C1_THREADS = 256, C1_GROUPS = C1_THREADS / 8;
+constexpr int C1_MAX_TOKENS = 2048;  // the entry points' bound: the backward keeps two floats a key in LDS
+
+template <typename T> __device__ __forceinline__ void store8f(T* p, const float* x);
+template <> __device__ __forceinline__ void store8f<bf16>(bf16* p, const float* x) {
+  *reinterpret_cast<bf16x8*>(p) = bf16x8{(bf16)x[0], (bf16)x[1], (bf16)x[2], (bf16)x[3],
+                                         (bf16)x[4], (bf16)x[5], (bf16)x[6], (bf16)x[7]};
+}
+template <> __device__ __forceinline__ void store8f<float>(float* p, const float* x) {
+  *reinterpret_cast<f32x4*>(p) = f32x4{x[0], x[1], x[2], x[3]};
+  *reinterpret_cast<f32x4*>(p + 4) = f32x4{x[4], x[5], x[6], x[7]};
+}
+// a . b over the 64 head dims of which this lane holds 8: the same value in all 8 lanes of the key's group
+__device__ __forceinline__ float c1_dot(const float* a, const float* b) {
+  float s = 0.f;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) s = fmaf(a[u], b[u], s);
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  s += __shfl_xor(s, 4, 64);
+  return s;
+}
+
+// s_j = scale * (q0 . k_j), lse = logsumexp_j s_j, o0 = sum_j softmax(s)_j v_j: an online softmax per lane group
+// over its keys, the groups merged in index order.  o_cls row b at b * ld_o (column h * 64), lse_cls[b * H + h].
+template <typename T>
+__global__ __launch_bounds__(C1_THREADS) void attn_cls1_fwd(const T* __restrict__ qkv, int64_t ld_qkv, int D, int H,
+                                                            int N, float scale, T* __restrict__ o_cls, int64_t ld_o,
+                                                            float* __restrict__ lse_cls) {
+  __shared__ float gm[C1_GROUPS], gl[C1_GROUPS], gacc[C1_GROUPS][64];
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int g = threadIdx.x >> 3, c = threadIdx.x & 7;
+  const T* base = qkv + (int64_t)b * N * ld_qkv + h * 64 + c * 8;
+  float q[8], acc[8];
+  load8f<T>(base, q);
+#pragma unroll
+  for (int u = 0; u < 8; ++u) acc[u] = 0.f;
+  float m = -INFINITY, l = 0.f;
+  for (int j = g; j < N; j += C1_GROUPS) {
+    float k[8], v[8];
+    load8f<T>(base + (int64_t)j * ld_qkv + D, k);
+    load8f<T>(base + (int64_t)j * ld_qkv + 2 * D, v);
+    const float s = c1_dot(q, k) * scale;
+    const float mn = fmaxf(m, s);
+    const float corr = __expf(m - mn), p = __expf(s - mn);  // the group's first key: corr = exp(-inf) = 0
+    l = l * corr + p;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = acc[u] * corr + p * v[u];
+    m = mn;
+  }
+  if (c == 0) { gm[g] = m; gl[g] = l; }
+#pragma unroll
+  for (int u = 0; u < 8; ++u) gacc[g][c * 8 + u] = acc[u];
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    // group 0 holds key 0, so M is finite; a group without keys (N < 32) has m = -inf, l = 0 and weight 0
+    float M = gm[0];
+    for (int i = 1; i < C1_GROUPS; ++i) M = fmaxf(M, gm[i]);
+    float Lsum = 0.f, od = 0.f;
+    for (int i = 0; i < C1_GROUPS; ++i) {
+      const float w = __expf(gm[i] - M);
+      Lsum = fmaf(gl[i], w, Lsum);
+      od = fmaf(gacc[i][threadIdx.x], w, od);
+    }
+    o_cls[(int64_t)b * ld_o + h * 64 + threadIdx.x] = (T)(od / Lsum);
+    if (threadIdx.x == 0) lse_cls[bh] = M + logf(Lsum);
+  }
+}
+
+// p_j = exp(s_j - lse), delta = dO0 . o0, ds_j = p_j (dO0 . v_j - delta); dk_j = scale ds_j q0 and dv_j = p_j dO0 for
+// every row, dq row 0 = scale sum_j ds_j k_j (k_j still in registers), dq rows 1 .. N-1 = 0: the whole 64-column
+// slice of this head in dqkv [B*N, 3D] is written, by the lane group that read the row (row 0's dq after the merge).
+//
+// Consistency step.  In exact arithmetic sum_j ds_j = 0, and dq is the sum of ds_j (k_j - kbar): what a common
+// offset of the keys contributes cancels.  o0 arrives rounded to T, so delta is off by e = dO0 . (o0 - o) and the
+// sum by -e: in bf16, on keys with a large common offset, that alone puts dq 5e-2 of its largest magnitude off
+// (17 tokens, q, k += 6).  The kernel knows r = sum_j ds_j and den = sum_j p_j when the keys are through, so it
+// takes e = r / den back out: ds_j -= p_j r / den, that is dq -= scale (r / den) sum_j p_j k_j, and dk_j is written
+// from the corrected ds_j, kept per key in LDS (two floats a key) until then.  K and V are still read once.
+template <typename T>
+__global__ __launch_bounds__(C1_THREADS) void attn_cls1_bwd(const T* __restrict__ qkv, int64_t ld_qkv, int D, int H,
+                                                            int N, float scale, const T* __restrict__ o_cls,
+                                                            int64_t ld_o, const T* __restrict__ do_cls, int64_t ld_do,
+                                                            const float* __restrict__ lse_cls, T* __restrict__ dqkv,
+                                                            int64_t ld_dqkv) {
+  __shared__ float gacc[C1_GROUPS][64], gpk[C1_GROUPS][64], gr[C1_GROUPS], gden[C1_GROUPS];
+  __shared__ float sds[C1_MAX_TOKENS], sp[C1_MAX_TOKENS];
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int g = threadIdx.x >> 3, c = threadIdx.x & 7;
+  const T* base = qkv + (int64_t)b * N * ld_qkv + h * 64 + c * 8;
+  T* dbase = dqkv + (int64_t)b * N * ld_dqkv + h * 64 + c * 8;
+  float q[8], d0[8], o0[8], acc[8], pk[8], zero[8];
+  load8f<T>(base, q);
+  load8f<T>(do_cls + (int64_t)b * ld_do + h * 64 + c * 8, d0);
+  load8f<T>(o_cls + (int64_t)b * ld_o + h * 64 + c * 8, o0);
+  const float delta = c1_dot(d0, o0), lse = lse_cls[bh];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) { acc[u] = 0.f; pk[u] = 0.f; zero[u] = 0.f; }
+  float r = 0.f, den = 0.f;
+  for (int j = g; j < N; j += C1_GROUPS) {
+    float k[8], v[8], dv[8];
+    load8f<T>(base + (int64_t)j * ld_qkv + D, k);
+    load8f<T>(base + (int64_t)j * ld_qkv + 2 * D, v);
+    const float p = __expf(c1_dot(q, k) * scale - lse);
+    const float ds = p * (c1_dot(d0, v) - delta);  // the same value in the key's 8 lanes
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      acc[u] = fmaf(ds, k[u], acc[u]);
+      pk[u] = fmaf(p, k[u], pk[u]);
+      dv[u] = p * d0[u];
+    }
+    r += ds;
+    den += p;
+    if (c == 0) { sds[j] = ds; sp[j] = p; }  // j < N <= C1_MAX_TOKENS (the entry point's bound)
+    T* row = dbase + (int64_t)j * ld_dqkv;
+    if (j > 0) store8f<T>(row, zero);
+    store8f<T>(row + 2 * D, dv);
+  }
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {  // a group without keys: zeros
+    gacc[g][c * 8 + u] = acc[u];
+    gpk[g][c * 8 + u] = pk[u];
+  }
+  if (c == 0) { gr[g] = r; gden[g] = den; }
+  __syncthreads();
+  float R = 0.f, Den = 0.f;  // every thread, the groups in index order: the same bits everywhere
+  for (int i = 0; i < C1_GROUPS; ++i) { R += gr[i]; Den += gden[i]; }
+  const float corr = Den > 0.f ? R / Den : 0.f;
+  if (threadIdx.x < 64) {
+    float s = 0.f, t = 0.f;
+    for (int i = 0; i < C1_GROUPS; ++i) { s += gacc[i][threadIdx.x]; t += gpk[i][threadIdx.x]; }
+    dqkv[(int64_t)b * N * ld_dqkv + h * 64 + threadIdx.x] = (T)((s - corr * t) * scale);
+  }
+  for (int j = g; j < N; j += C1_GROUPS) {  // the keys this group stashed itself
+    const float dss = (sds[j] - sp[j] * corr) * scale;
+    float dk[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) dk[u] = dss * q[u];
+    store8f<T>(dbase + (int64_t)j * ld_dqkv + D, dk);
+  }
+}
+static int g_cls1_count = 0;
+
+// what both one-query entry points refuse before anything is queued: head_dim, N, row strides and addresses
+// that the 16-B loads and stores cannot take
+static bool cls1_args_ok(int dtype, int B, int H, int N, int head_dim, std::initializer_list<int64_t> lds,
+                         std::initializer_list<const void*> ptrs) {
+  if ((dtype != VIT_BF16 && dtype != VIT_F32) || head_dim != 64 || B <= 0 || H <= 0 || N <= 0 || N > C1_MAX_TOKENS)
+    return false;
+  const int64_t per16 = dtype == VIT_BF16 ? 8 : 4;  // elements in 16 bytes
+  for (int64_t ld : lds)
+    if (ld < 0 || ld % per16) return false;
+  for (const void* p : ptrs)
+    if (p == nullptr || ((uintptr_t)p & 15)) return false;
+  return true;
+}
+
 #define NT_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18)
 
 extern "C" {
@@ -2435,6 +2605,56 @@ int vit_sdpa_fwd_cls(int dtype, int B, int H, int N, int head_dim, const void* q
 int vit_sdpa_cls_count(int reset) {
   const int n = g_cls_count;
   if (reset) g_cls_count = 0;
+  return n;
+}
+
+// One-query forward (attn_cls1_fwd): query row 0 of every image, all N keys and values; bf16 or f32, any N up to
+// 2048.  o_cls [B, D] with row b at b * ld_o (the dense o with ld_o = N * D is a valid argument), lse_cls [B * H]
+// f32 (natural log).  head_dim != 64, N <= 0 or > 2048, a row stride or an address that is not a multiple of 16
+// bytes: hipErrorInvalidValue, nothing queued.
+int vit_sdpa_cls1_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* o_cls,
+                      int64_t ld_o, float* lse_cls, float scale, void* stream) {
+  if (!cls1_args_ok(dtype, B, H, N, head_dim, {ld_qkv, ld_o}, {qkv, o_cls}) || lse_cls == nullptr ||
+      ld_qkv < 3 * (int64_t)H * 64)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  const int D = H * 64;
+  if (dtype == VIT_BF16)
+    hipLaunchKernelGGL(attn_cls1_fwd<bf16>, dim3(B * H), dim3(C1_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N,
+                       scale, (bf16*)o_cls, ld_o, lse_cls);
+  else
+    hipLaunchKernelGGL(attn_cls1_fwd<float>, dim3(B * H), dim3(C1_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
+                       scale, (float*)o_cls, ld_o, lse_cls);
+  VIT_CHECK_LAUNCH();
+  ++g_cls1_count;
+  return 0;
+}
+
+// One-query backward (attn_cls1_bwd) from the class rows' dO (do_cls [B, D], row b at b * ld_do), the forward's
+// o_cls and lse_cls: writes every element of dqkv [B*N, 3D] (dq rows 1 .. N-1 exact zeros); delta is computed
+// in the kernel, no workspace, no bias partials.  Refusals as vit_sdpa_cls1_fwd.
+int vit_sdpa_cls1_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv,
+                      const void* o_cls, int64_t ld_o, const void* do_cls, int64_t ld_do, const float* lse_cls,
+                      void* dqkv, int64_t ld_dqkv, float scale, void* stream) {
+  if (!cls1_args_ok(dtype, B, H, N, head_dim, {ld_qkv, ld_o, ld_do, ld_dqkv}, {qkv, o_cls, do_cls, dqkv}) ||
+      lse_cls == nullptr || ld_qkv < 3 * (int64_t)H * 64 || ld_dqkv < 3 * (int64_t)H * 64)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  const int D = H * 64;
+  if (dtype == VIT_BF16)
+    hipLaunchKernelGGL(attn_cls1_bwd<bf16>, dim3(B * H), dim3(C1_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N,
+                       scale, (const bf16*)o_cls, ld_o, (const bf16*)do_cls, ld_do, lse_cls, (bf16*)dqkv, ld_dqkv);
+  else
+    hipLaunchKernelGGL(attn_cls1_bwd<float>, dim3(B * H), dim3(C1_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
+                       scale, (const float*)o_cls, ld_o, (const float*)do_cls, ld_do, lse_cls, (float*)dqkv, ld_dqkv);
+  VIT_CHECK_LAUNCH();
+  ++g_cls1_count;
+  return 0;
+}
+// Host-side count of launches of either one-query kernel (reset != 0 zeroes it after reading).
+int vit_sdpa_cls1_count(int reset) {
+  const int n = g_cls1_count;
+  if (reset) g_cls1_count = 0;
   return n;
 }
 

@@ -33,7 +33,9 @@ frozen text blocks in front of the first DoRA block see the same 66 prompts ever
 their output is cached (keyed by the prompt tensor and the parameters' versions) -- the result
 is bit-identical to recomputing it.  The frozen visual blocks see the same images in every epoch of a
 sweep; keeping their output is opt-in (``visual_prefix`` / ``forward(prefix=...)`` here, the rows live in
-``prefix_cache.VisualPrefixCache``).
+``prefix_cache.VisualPrefixCache``).  ``ln_post`` reads the class rows alone; computing the visual
+tower's last block for those rows only (the class-token tail on one-query attention kernels) is opt-in too
+(``CLIP.set_cls_tail`` / ``CLIPHBA(cls_tail=True)``): it agrees with the dense block to rounding.
 """
 from __future__ import annotations
 
@@ -47,7 +49,7 @@ from . import _lib as L
 from . import ops
 from .dora import DoRALayer
 from .lora import LoRALayer
-from .model import _FUSED_RESID_F32, _BlockFn, _Shadowed, _gout, _wt, run_block
+from .model import _FUSED_RESID_F32, _BlockFn, _Shadowed, _gout, _wt, run_block, wants_cls_tail
 
 SOT, EOT = 49406, 49407
 
@@ -270,6 +272,7 @@ class CLIP(nn.Module):
         self._text_cache = None
         self.attention_fp8 = False  # set_attention_fp8
         self.attention_fp8_long = False
+        self.cls_tail = False  # set_cls_tail
         self.initialize_parameters()
 
     @torch.no_grad()
@@ -324,6 +327,14 @@ class CLIP(nn.Module):
         self.attention_fp8 = bool(enable)
         self.attention_fp8_long = bool(enable) and bool(long_sequences)
 
+    def set_cls_tail(self, enable: bool = True):
+        """Run the visual tower's last block as the class-token tail: ``ln_post`` reads ``x[:, 0]``
+        alone, so proj, ln_2 and the MLP run for the B class rows and attention for query 0 of every head
+        (vit_sdpa_cls1_fwd / vit_sdpa_cls1_bwd).  Off by default; the results agree with the dense block's to
+        rounding, not in bits.  fp8 attention passes and a last block whose ``in_proj_bias`` is trainable keep
+        the dense block / the tail's dense attention."""
+        self.cls_tail = bool(enable)
+
     def _cfg(self, heads, causal, frozen=False):
         fp8 = self.attention_fp8 and (frozen or not torch.is_grad_enabled())
         return dict(heads=heads, eps=1e-5, quick_gelu=True, dtype=self.compute_dtype, causal=causal, attn_fp8=fp8,
@@ -359,10 +370,12 @@ class CLIP(nn.Module):
                                       v.ln_pre.bias.detach(), 1e-5, torch.float32, need_stats=False)
         return x2.reshape(B, npatch + 1, W)
 
-    def _visual_blocks(self, x, lo, hi):
+    def _visual_blocks(self, x, lo, hi, pooled=False):
         """``visual.transformer.resblocks[lo:hi]`` over the residual stream ``x``.  The block at ``hi - 1``
         writes its output out (``resid_last``) when it is the tower's last block or ``hi`` is a cut
-        (:meth:`visual_prefix`): nothing is then pending for a block that is not part of this call."""
+        (:meth:`visual_prefix`): nothing is then pending for a block that is not part of this call.  With
+        :meth:`set_cls_tail` and ``pooled`` (encode_image: ln_post reads the class rows alone) the tower's last block
+        returns its class rows alone, [B, 1, W]; :meth:`visual_prefix` never asks for that."""
         W = self.visual.conv1.out_channels
         T = self.compute_dtype
         heads = W // 64
@@ -376,6 +389,11 @@ class CLIP(nn.Module):
             cfg = self._cfg(heads, False, frozen=i < first)
             if rs is not None:
                 cfg = dict(cfg, resid=rs, resid_last=i == hi - 1)
+            # the tower's last block, whose output ln_post reads in x[:, 0] alone: the class-token tail with the
+            # one-query attention (set_cls_tail; never at a cut, fp8 passes keep the dense block)
+            if i == len(blocks) - 1 and wants_cls_tail(self.cls_tail, pooled and hi == len(blocks), "token",
+                                                           cfg["attn_fp8"]):
+                cfg = dict(cfg, cls_tail=True, cls_attn1=True)
             x = run_block(x, blocks[i].block_params(), cfg)
         return x
 
@@ -431,7 +449,7 @@ class CLIP(nn.Module):
             L.require_gpu(image)
             self._ensure_shadows()
             x, lo = self._visual_stem(image, pos_embedding), 0
-        x = self._visual_blocks(x, lo, len(blocks))
+        x = self._visual_blocks(x, lo, len(blocks), pooled=True)
         v = self.visual
         idx = self._cls_rows(x.shape[0], x.shape[1], x.device)
         return _PoolHeadFn.apply(x, idx, v.ln_post.weight, v.ln_post.bias, v.proj, 1e-5)
@@ -543,7 +561,7 @@ class CLIPHBA(nn.Module):
 
     def __init__(self, classnames, backbone_name="ViT-L/14", pos_embedding=False, clip_model=None,
                  tokenized_prompts=None, compute_dtype=torch.float32, attention_fp8=False,
-                 attention_fp8_long=False):
+                 attention_fp8_long=False, cls_tail=False):
         super().__init__()
         self.num_clip = len(classnames)
         if clip_model is None:
@@ -555,6 +573,8 @@ class CLIPHBA(nn.Module):
         self.clip_model.float()
         if attention_fp8:  # BASELINE configs[4]: fp8 attention in the frozen / no-grad blocks
             self.clip_model.set_attention_fp8(True, long_sequences=attention_fp8_long)
+        if cls_tail:  # the visual tower's last block on the class rows alone (CLIP.set_cls_tail)
+            self.clip_model.set_cls_tail(True)
         self.pos_embedding = pos_embedding
         for p in self.clip_model.parameters():
             p.requires_grad = False

@@ -269,7 +269,7 @@ class _PatchEmbedFn(torch.autograd.Function):
         return None, dw, db, dcls, dpos, None
 
 
-def _block_chain(x, params, cfg, fwd_only):
+def _block_chain(x, params, cfg, fwd_only, attn1=False):
     """The launch chain of one block's forward, shared by the autograd node (_BlockFn.forward) and the
     forward-only path (block_forward_only).  Returns (xo [B, N, D], the tensors a backward would need,
     the GEMM weight operands).  ``fwd_only``: fc1 runs the act-only epilogue and no act'(pre) tensor
@@ -280,7 +280,10 @@ def _block_chain(x, params, cfg, fwd_only):
     qkv and attention run for all rows; proj, norm2, fc1, fc2 and the residual adds run for the B class rows
     alone, read by stride N*D from the dense tensors, on compact [B, .] tensors.  xo is then [B, 1, D]: bit
     for bit the dense block's class rows (GEMM and LayerNorm rows are independent).  The half-batch
-    schedule is the same: each chain carries its images' class rows."""
+    schedule is the same: each chain carries its images' class rows.
+
+    ``attn1`` (wants_cls_attn1; the CLIP visual tower's tail): the tail's attention is the one-query
+    kernel -- o is then the compact [B, D] tensor and lse [B * H]; the dense ones are not allocated."""
     n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
     B, N, D = x.shape
     H, T, eps = cfg["heads"], cfg["dtype"], cfg["eps"]
@@ -299,8 +302,8 @@ def _block_chain(x, params, cfg, fwd_only):
     m1, r1 = (torch.empty(M, dtype=f32, device=dev) for _ in range(2))
     m2, r2 = (torch.empty(Mt, dtype=f32, device=dev) for _ in range(2))
     qkv = torch.empty(M, 3 * D, dtype=T, device=dev)
-    o = torch.empty(M, D, dtype=T, device=dev)
-    lse = torch.empty(B * H * N, dtype=f32, device=dev)
+    o = torch.empty(B if attn1 else M, D, dtype=T, device=dev)
+    lse = torch.empty(B * H * (1 if attn1 else N), dtype=f32, device=dev)
     xm, xo = torch.empty(Mt, D, dtype=f32, device=dev), torch.empty(Mt, D, dtype=f32, device=dev)
     # fc1's epilogue writes act = GELU(pre) for fc2 and dact = GELU'(pre) for the backward
     # (the erf is evaluated once; the fc2 dgrad epilogue is then a multiply); a forward-only pass has
@@ -326,7 +329,7 @@ def _block_chain(x, params, cfg, fwd_only):
     # class-token tail: the class rows of the residual stream and of the attention output, by stride
     x_cls = o_cls = xc = None
     if ct:
-        x_cls, o_cls = x2.view(B, N * D)[:, :D], o.view(B, N * D)[:, :D]
+        x_cls, o_cls = x2.view(B, N * D)[:, :D], o if attn1 else o.view(B, N * D)[:, :D]
         if rs is None:  # the EPI_RESID epilogue reads its residual at the output's row stride: compact copy
             xc = torch.empty(B, D, dtype=f32, device=dev)
 
@@ -366,9 +369,12 @@ def _block_chain(x, params, cfg, fwd_only):
         steps = [
             ln1(sl),
             lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
-            # (only query 0 of each head is read: the query-limited forward; the tail is never causal or fp8)
-            lambda: ops.sdpa_fwd_cls(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N]),
         ]
+        if attn1:  # query 0 alone, into the compact o
+            steps.append(lambda: ops.sdpa_cls1_fwd(qkv[sl], b1 - b0, H, N, o=o[cs], lse=lse[b0 * H:b1 * H]))
+        else:
+            # (only query 0 of each head is read: the query-limited forward; the tail is never causal or fp8)
+            steps.append(lambda: ops.sdpa_fwd_cls(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N]))
         if rs is not None:
             steps += [
                 lambda: ops.linear_fwd(o_cls[cs], Wproj, projb.detach(), out=pb[cs]),
@@ -443,7 +449,7 @@ def block_forward_only(x, params, cfg):
     12 tensors of ``block_params()``; returns the block output [B, N, D] (f32), bit for bit the
     training chain's."""
     with torch.no_grad():
-        return _block_chain(x, tuple(params), cfg, True)[0]
+        return _block_chain(x, tuple(params), cfg, True, _cfg_attn1(cfg, False))[0]
 
 
 def forward_only_enabled() -> bool:
@@ -495,6 +501,20 @@ def wants_cls_tail(enabled: bool, cls_only: bool, global_pool: str, attn_fp8: bo
     return bool(enabled) and bool(cls_only) and global_pool == "token" and not attn_fp8
 
 
+def wants_cls_attn1(tail: bool, requested: bool, causal: bool = False, attn_fp8: bool = False,
+                    qkv_bias_needs_grad: bool = False) -> bool:
+    """The routing rule of the one-query attention inside the class-token tail, as a pure function: only a block
+    that runs the tail and asks for it (cfg "cls_attn1": the CLIP visual tower's last block), unmasked, not fp8,
+    and whose qkv bias needs no gradient (the one-query backward produces no bias partials).  Otherwise the
+    tail keeps its attention route (sdpa_fwd_cls / sdpa_bwd)."""
+    return bool(tail) and bool(requested) and not causal and not attn_fp8 and not qkv_bias_needs_grad
+
+
+def _cfg_attn1(cfg, qkv_bias_needs_grad: bool) -> bool:
+    return wants_cls_attn1(bool(cfg.get("cls_tail")), bool(cfg.get("cls_attn1")), bool(cfg.get("causal", False)),
+                           bool(cfg.get("attn_fp8", False)), bool(qkv_bias_needs_grad))
+
+
 def wants_forward_only(enabled: bool, grad_enabled: bool, input_requires_grad: bool,
                        any_param_requires_grad: bool) -> bool:
     """The routing rule, as a pure function: a block takes the forward-only chain when the switch is on
@@ -524,7 +544,8 @@ class _BlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b, cfg):
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b)
-        xo, saved, wops = _block_chain(x, params, cfg, False)
+        attn1 = _cfg_attn1(cfg, ctx.needs_input_grad[4])
+        xo, saved, wops = _block_chain(x, params, cfg, False, attn1)
         B, N, D = x.shape
         H, T = cfg["heads"], cfg["dtype"]
         causal = bool(cfg.get("causal", False))
@@ -536,6 +557,7 @@ class _BlockFn(torch.autograd.Function):
         ctx.defer_bwd = bool(cfg.get("defer_bwd_join"))
         ctx.attn_fp8 = attn_fp8
         ctx.cls_tail = bool(cfg.get("cls_tail"))
+        ctx.cls_attn1 = attn1
         ctx.grad_hook = cfg.get("grad_hook")
         ctx.flat_span = cfg.get("flat_span")
         return xo
@@ -555,6 +577,7 @@ class _BlockFn(torch.autograd.Function):
         # reduction adds the same terms in the same order as the dense block's: the partial rows are laid
         # out as the dense launch's (spread_partials) and the weight gradients split as the dense pair.
         ct = ctx.cls_tail
+        a1 = ctx.cls_attn1  # one-query attention: o is the compact [B, D] tensor, lse [B * H]
         P = tail_pad(N, ops.ln_bwd_rows_per()) if ct else N
         Mt = B * P
         spread_sums = ct and P != N
@@ -633,16 +656,22 @@ class _BlockFn(torch.autograd.Function):
             tail = bool(compact_np)
             # (padded tail: the proj gradient has B * P rows, the qkv one M: two launches with the pair's split)
             pair_attn = rbw is not None and ng[5] and ng[3] and need_attn and not spread_sums
-            o_w = rows_padded(o.view(B, N * D)[:, :D]) if spread_sums else o
+            if a1:  # the class rows of o, padded like the gradient rows they meet (P == N: the dense layout)
+                o_w = rows_padded(o)
+            else:
+                o_w = rows_padded(o.view(B, N * D)[:, :D]) if spread_sums else o
             if ng[5] and not pair_attn:
                 side.run(lambda: ops.linear_wgrad(dxm_c, o_w, out=g[5], split=sp_attn, tail=tail, reduce_on=rbw))
             if need_attn:
                 do = ops.linear_dgrad(dxm_c, Wproj, out_dtype=T)
-                if spread_sums:  # the attention backward takes the dense dO: zero but for the class rows
-                    do = ops.pad_cols(do.view(B, P * D)[:, :D], N * D).view(M, D)
-                dqkv = ops.sdpa_bwd(qkv, o, do, lse, B, H, N, dbias=g[4], causal=causal, reduce_on=rb)
+                if a1:  # the class rows of dO, P rows apart, straight to the one-query backward
+                    dqkv = ops.sdpa_cls1_bwd(qkv, o, do.view(B, P * D)[:, :D], lse, B, H, N)
+                else:
+                    if spread_sums:  # the attention backward takes the dense dO: zero but for the class rows
+                        do = ops.pad_cols(do.view(B, P * D)[:, :D], N * D).view(M, D)
+                    dqkv = ops.sdpa_bwd(qkv, o, do, lse, B, H, N, dbias=g[4], causal=causal, reduce_on=rb)
                 if pair_attn:
-                    side.run(lambda: ops.linear_wgrad_pair((dxm_c, o, g[5]), (dqkv, h1, g[3]), rbw, tail=tail))
+                    side.run(lambda: ops.linear_wgrad_pair((dxm_c, o_w, g[5]), (dqkv, h1, g[3]), rbw, tail=tail))
                 elif ng[3]:
                     side.run(lambda: ops.linear_wgrad(dqkv, h1, out=g[3], split=sp_attn, tail=tail, reduce_on=rbw))
             if need_h1:

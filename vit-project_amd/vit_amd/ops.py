@@ -534,6 +534,42 @@ def sdpa_fwd_cls(qkv2d, B, H, N, o=None, scale=None, lse=None):
     return o, lse
 
 
+CLS1_MAX_TOKENS = 2048  # vit_sdpa_cls1_fwd / vit_sdpa_cls1_bwd refuse more
+
+
+def sdpa_cls1_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None):
+    """One-query attention forward (vit_sdpa_cls1_fwd): query row 0 of every image against all N keys and
+    values, bf16 or f32, N up to 2048.  Returns (o [B, D] in the qkv dtype, lse [B * H] f32); ``o`` may be any
+    [B, D] view with 16-byte-aligned rows (e.g. the class rows of a dense o, row stride N * D).  Agrees with
+    sdpa_fwd's row 0 to rounding, not in bits."""
+    D = H * 64
+    if o is None:
+        o = torch.empty(B, D, dtype=qkv2d.dtype, device=qkv2d.device)
+    if lse is None:
+        lse = torch.empty(B * H, dtype=torch.float32, device=qkv2d.device)
+    assert o.shape == (B, D) and o.stride(1) == 1 and o.dtype == qkv2d.dtype and lse.numel() == B * H
+    scale = 64 ** -0.5 if scale is None else scale
+    call("vit_sdpa_cls1_fwd", L.dt(qkv2d), B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(o), o.stride(0), ptr(lse),
+         float(scale), _s(qkv2d))
+    return o, lse
+
+
+def sdpa_cls1_bwd(qkv2d, o, do, lse, B, H, N, dqkv=None, scale=None):
+    """One-query attention backward (vit_sdpa_cls1_bwd) from the class rows' dO: ``o`` / ``do`` [B, D] (any row
+    stride), ``lse`` [B * H] of sdpa_cls1_fwd.  Writes every element of dqkv [B*N, 3D] (dq rows 1 .. N-1 of each
+    image exact zeros); no workspace and no qkv bias partials."""
+    D = H * 64
+    if dqkv is None:
+        dqkv = torch.empty(B * N, 3 * D, dtype=qkv2d.dtype, device=qkv2d.device)
+    assert o.shape == (B, D) and do.shape == (B, D) and o.stride(1) == 1 and do.stride(1) == 1
+    assert o.dtype == qkv2d.dtype and do.dtype == qkv2d.dtype and dqkv.dtype == qkv2d.dtype
+    assert dqkv.shape == (B * N, 3 * D) and dqkv.stride(1) == 1 and lse.numel() == B * H
+    scale = 64 ** -0.5 if scale is None else scale
+    call("vit_sdpa_cls1_bwd", L.dt(qkv2d), B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(o), o.stride(0), ptr(do),
+         do.stride(0), ptr(lse), ptr(dqkv), dqkv.stride(0), float(scale), _s(qkv2d))
+    return dqkv
+
+
 def sdpa_bwd(qkv2d, o, do, lse, B, H, N, dqkv=None, scale=None, dbias=None, causal=False, ws="", reduce_on=None):
     """dbias [3*H*64] (optional) receives the column sums of dqkv (the qkv bias gradient).
     ``ws``: workspace-name suffix (calls running concurrently on different streams need their own).

@@ -185,7 +185,9 @@ int vit_pos_grad(int B, int S, int D, const float* dx, float* dpos, float* dcls,
  * issued before this row's stores; default), 0 = the plain row loop.  Equal to rounding. */
 int vit_layer_norm_bwd_variant(int v);
 
-/* F.layer_norm forward (timm norm1/norm2/norm, eps 1e-6), one wave per row; saves mean/rstd. */
+/* F.layer_norm forward (timm norm1/norm2/norm, eps 1e-6), one wave per row; saves mean/rstd.
+ * D <= 2048.  16-byte accesses when D % 256 == 0, strides % 4 == 0 and x, y, w, b are aligned to 4 elements
+ * (16 bytes of f32, 8 of bf16); anything else takes the element-wise kernel. */
 int vit_layer_norm_fwd(int dtype_x, int dtype_y, int rows, int D, const void* x, int64_t ldx, void* y,
                        int64_t ldy, const float* w, const float* b, float* mean, float* rstd, float eps,
                        void* stream);
@@ -193,13 +195,16 @@ int vit_layer_norm_fwd(int dtype_x, int dtype_y, int rows, int D, const void* x,
  * x) and, when y is non-null, y = LayerNorm(xs) (dtype_y) with mean/rstd: timm Block's `x = x + attn(norm1(x))` /
  * `x = x + mlp(norm2(x))` residual adds (VIT Block.forward via timm) fused into the LayerNorm that
  * follows them (norm2 of the same block, norm1 of the next); y == null: the add alone (last block).
- * D % 256 == 0, strides % 4 == 0. */
+ * D % 256 == 0, strides % 4 == 0, x / r / xs / y / w / b aligned to 4 elements (there is no element-wise
+ * form: anything else is hipErrorInvalidValue). */
 int vit_add_layer_norm_fwd(int dtype_r, int dtype_y, int rows, int D, const float* x, int64_t ldx, const void* r,
                            int64_t ldr, float* xs, int64_t ldxs, void* y, int64_t ldy, const float* w, const float* b,
                            float* mean, float* rstd, float eps, void* stream);
 /* LayerNorm backward with fused residual-gradient add, optional GEMM-dtype copy
  * of dx (optionally dropping CLS rows), dgamma/dbeta, and dsum = column sums of dx
- * (bias gradient of the Linear whose output fed the residual: proj / fc2). */
+ * (bias gradient of the Linear whose output fed the residual: proj / fc2).
+ * Vector kernels when D is 768 or 1024, every stride % 4 == 0 and x, dy, w, dres, dx, dx_copy are aligned to
+ * 4 elements; the element-wise kernel otherwise. */
 int vit_layer_norm_bwd(int dtype_x, int dtype_dy, int rows, int D, const void* x, int64_t ldx,
                        const void* dy, int64_t lddy, const float* w, const float* mean, const float* rstd,
                        const float* dres, int64_t ldres, float* dx, int64_t lddx, void* dx_copy, int64_t ld_copy,
@@ -389,7 +394,9 @@ int vit_adamw_tensor_bytes(void);
  *   gather_rows   dst[i] = src[idx[i]]  (text EOT pooling x[arange, text.argmax(-1)], CLS rows)
  *   scatter_rows  dst[idx[i]] = src[i]  (their backward; dst zeroed by the caller)
  *   rownorm       y = exp(*log_scale) x / ||x|| (feature normalisation; log_scale null = 1), and backward
- *   mse           nn.MSELoss() mean (NEWP:994, CBASE criterion) and its gradient (grad_loss null = 1) */
+ *   mse           nn.MSELoss() mean (NEWP:994, CBASE criterion) and its gradient (grad_loss null = 1)
+ * token_embed needs D % 4 == 0; ids outside [0, vocab) read the table's first / last row; 16-byte accesses when
+ * table, pos and x are 16-byte aligned, one float per lane otherwise. */
 int vit_token_embed(int rows, int L, int D, int vocab, const int64_t* tokens, const float* table, const float* pos,
                     float* x, void* stream);
 int vit_gather_rows(int n, int D, const float* src, int64_t ld_src, const int64_t* idx, float* dst, int64_t ld_dst,
@@ -416,6 +423,7 @@ int vit_image_transform(int B, int S, const uint8_t* src, const int64_t* params,
                         int* coeff_ws, uint8_t* tmp_ws, float* out, const float* norm6, void* stream);
 
 /* helpers */
+/* round-to-nearest-even cast; 4 elements per lane when x is 16-byte and y 8-byte aligned, else one */
 int vit_cast_f32_bf16(const float* x, void* y, int64_t n, void* stream);
 int vit_zero(void* p, int64_t bytes, void* stream);
 

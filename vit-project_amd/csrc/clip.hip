@@ -24,6 +24,21 @@ __global__ __launch_bounds__(256) void token_embed_kernel(const int64_t* __restr
   }
 }
 
+// the same, one float per lane: a table, pos or x that is not 16-byte aligned
+__global__ __launch_bounds__(256) void token_embed_scalar_kernel(const int64_t* __restrict__ tok,
+                                                                 const float* __restrict__ table,
+                                                                 const float* __restrict__ pos, float* __restrict__ x,
+                                                                 int rows, int L, int D, int vocab) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  int64_t id = tok[row];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  const float* e = table + id * D;
+  const float* p = pos + (int64_t)(row % L) * D;
+  float* o = x + (int64_t)row * D;
+  for (int d = lane; d < D; d += 64) o[d] = e[d] + p[d];
+}
+
 // dst[i][:] = src[idx[i]][:]  (SCATTER = 0)   or   dst[idx[i]][:] = src[i][:]  (SCATTER = 1)
 template <int SCATTER>
 __global__ __launch_bounds__(256) void rows_kernel(const float* __restrict__ src, int64_t ld_src,
@@ -119,8 +134,12 @@ int vit_token_embed(int rows, int L, int D, int vocab, const int64_t* tokens, co
                     float* x, void* stream) {
   if (rows <= 0) return 0;
   if (D % 4 || L <= 0 || vocab <= 0) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(token_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, tokens, table, pos, x,
-                     rows, L, D, vocab);
+  if (((uintptr_t)table | (uintptr_t)pos | (uintptr_t)x) & 15)
+    hipLaunchKernelGGL(token_embed_scalar_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, tokens, table,
+                       pos, x, rows, L, D, vocab);
+  else
+    hipLaunchKernelGGL(token_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, tokens, table, pos, x,
+                       rows, L, D, vocab);
   VIT_CHECK_LAUNCH();
   return 0;
 }

@@ -219,6 +219,12 @@ __global__ void cast_f32_bf16_kernel(const float* __restrict__ x, bf16* __restri
   }
 }
 
+// the same cast one element per thread, for a source or destination that is not aligned to 4 elements
+__global__ void cast_f32_bf16_scalar_kernel(const float* __restrict__ x, bf16* __restrict__ y, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] = (bf16)x[i];
+}
+
 extern "C" {
 
 int vit_patch_unfold_ld(int dtype, int B, int C, int Hi, int Wi, int ps, int ldu, const float* img, void* U,
@@ -321,6 +327,13 @@ int vit_sgd_tensor_bytes(void) { return (int)sizeof(SgdTensor); }
 int vit_sgd_chunk_bytes(void) { return (int)sizeof(SgdChunk); }
 
 int vit_cast_f32_bf16(const float* x, void* y, int64_t n, void* stream) {
+  if (n <= 0) return 0;
+  if (((uintptr_t)x & 15) || ((uintptr_t)y & 7)) {
+    hipLaunchKernelGGL(cast_f32_bf16_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       x, (bf16*)y, n);
+    VIT_CHECK_LAUNCH();
+    return 0;
+  }
   int64_t threads = (n + 3) / 4;
   hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16*)y, n);
   VIT_CHECK_LAUNCH();

@@ -412,6 +412,9 @@ static void launch_fwd(int nv, dim3 grid, hipStream_t s, const void* x, int64_t 
 #undef F
 }
 
+// The vector kernels read and write 4 elements at a time: 16 bytes of f32, 8 of bf16 (null: not accessed).
+static bool ln_aligned(const void* p, int dtype) { return ((uintptr_t)p & (dtype == VIT_BF16 ? 7 : 15)) == 0; }
+
 static int g_ln_pipe = -1;  // VIT_LN_BWD_PIPE / vit_layer_norm_bwd_variant: 1 pipelined (default), 0 plain loop
 
 template <typename TX, typename TD, typename TC>
@@ -441,7 +444,9 @@ int vit_layer_norm_fwd(int dtype_x, int dtype_y, int rows, int D, const void* x,
   if (rows <= 0) return 0;
   if (D > 64 * LN_SMAX) return (int)hipErrorInvalidValue;
   dim3 grid((rows + LN_WAVES - 1) / LN_WAVES);
-  bool vec = (D % 256 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0);
+  // a misaligned base pointer (a view that starts inside a row) takes the scalar kernel, as a stride does
+  bool vec = (D % 256 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && ln_aligned(x, dtype_x) && ln_aligned(y, dtype_y) &&
+             ln_aligned(w, VIT_F32) && ln_aligned(b, VIT_F32);
   int nv = vec ? D / 256 : 0;
   if (dtype_x == VIT_F32 && dtype_y == VIT_F32) launch_fwd<float, float>(nv, grid, s, x, ldx, y, ldy, w, b, mean, rstd, rows, D, eps);
   else if (dtype_x == VIT_F32) launch_fwd<float, bf16>(nv, grid, s, x, ldx, y, ldy, w, b, mean, rstd, rows, D, eps);
@@ -453,7 +458,8 @@ int vit_layer_norm_fwd(int dtype_x, int dtype_y, int rows, int D, const void* x,
 
 // xs = x + r (f32 + bf16 / f32 -> f32; xs may alias x) and, when y is non-null, y = LayerNorm(xs) (bf16 / f32)
 // with its mean / rstd: the residual add of a Linear's bf16 output fused into the LayerNorm that
-// follows it.  D must be a multiple of 256 (ViT-B 768, ViT-L 1024) and every stride of 4 elements.
+// follows it.  D must be a multiple of 256 (ViT-B 768, ViT-L 1024), every stride of 4 elements and every
+// base pointer aligned to 4 elements (16 bytes of f32, 8 of bf16).
 int vit_add_layer_norm_fwd(int dtype_r, int dtype_y, int rows, int D, const float* x, int64_t ldx, const void* r,
                            int64_t ldr, float* xs, int64_t ldxs, void* y, int64_t ldy, const float* w, const float* b,
                            float* mean, float* rstd, float eps, void* stream) {
@@ -461,6 +467,10 @@ int vit_add_layer_norm_fwd(int dtype_r, int dtype_y, int rows, int D, const floa
   if (rows <= 0) return 0;
   if (D % 256 || D > 2048 || (ldx | ldr | ldxs | ldy) % 4) return (int)hipErrorInvalidValue;
   if (y && (!w || !b || !mean || !rstd)) return (int)hipErrorInvalidValue;
+  // there is no scalar kernel here: a misaligned base pointer is an error, as a stride is
+  if (!ln_aligned(x, VIT_F32) || !ln_aligned(r, dtype_r) || !ln_aligned(xs, VIT_F32) || !ln_aligned(y, dtype_y) ||
+      !ln_aligned(w, VIT_F32) || !ln_aligned(b, VIT_F32))
+    return (int)hipErrorInvalidValue;
   dim3 grid((rows + LN_WAVES - 1) / LN_WAVES);
   if ((dtype_r != VIT_BF16 && dtype_r != VIT_F32) || (dtype_y != VIT_BF16 && dtype_y != VIT_F32))
     return (int)hipErrorInvalidValue;
@@ -527,7 +537,8 @@ static int ln_bwd(int dtype_x, int dtype_dy, int rows, int D, const void* x, int
   float* ps = dsum ? partial + 2 * (int64_t)nblk * D : nullptr;
   float* scratch = want ? partial + 3 * (int64_t)nblk * D : nullptr;
   bool vec = (D % 256 == 0) && (ldx % 4 == 0) && (lddy % 4 == 0) && (lddx % 4 == 0) && (ldres % 4 == 0) &&
-             (ld_copy % 4 == 0);
+             (ld_copy % 4 == 0) && ln_aligned(x, dtype_x) && ln_aligned(dy, dtype_dy) && ln_aligned(w, VIT_F32) &&
+             ln_aligned(dres, VIT_F32) && ln_aligned(dx, VIT_F32) && ln_aligned(dx_copy, dtype_copy);
   int nv = vec ? D / 256 : 0;
 #define LB(TX, TD) \
   if (dtype_copy == VIT_BF16) launch_bwd<TX, TD, bf16>(nv, nblk, s, x, ldx, dy, lddy, w, mean, rstd, dres, ldres, dx, lddx, dx_copy, ld_copy, compact_np, pg, pb, ps, rows, D, rows_per, res_every); \

@@ -48,7 +48,14 @@ int vit_abi_version(void); /* 10 (round 6): vit_blaslt_workspace / vit_gemm_lib 
 
 /* Generic MFMA GEMM C[i][j] = epi(sum_r P(i,r) Q(j,r)); layouts RC (r contiguous)
  * or CR (i/j contiguous).  Backs every nn.Linear of timm's ViT reached from
- * VIT:139 (forward) and VIT:142 (backward). */
+ * VIT:139 (forward) and VIT:142 (backward).
+ * Kernel choice (every GEMM entry point below goes through it).  The MFMA kernels need, for bf16: a reduction
+ * R % 32 == 0, N % 4 == 0, a CR operand's extent % 8, ldp / ldq % 8 and 16-byte-aligned P and Q (g4 for the plain
+ * bf16 store: R % 64, N % 8); for f32: R % 32, N % 4, a CR extent % 4, ldp / ldq % 4, aligned P and Q and at least
+ * 64 output tiles of 128 x 128 (times the split).  Their epilogues move 16 bytes at a time, so they also need C,
+ * aux_out, bias, aux (the residual / saved act'), pos_embed and the column-sum partial rows 16-byte aligned and
+ * ldc (shared by aux_out) and ld_aux multiples of 16 bytes (% 8 in bf16, % 4 in f32).  Anything else runs the
+ * generic kernel (one element at a time, any alignment and stride), with the same result on exact data. */
 int vit_gemm(int dtype, int out_dtype, int p_layout, int q_layout, int epi, int M, int N, int R,
              const void* P, int64_t ldp, const void* Q, int64_t ldq, void* C, int64_t ldc,
              const float* bias, const void* aux, int64_t ld_aux, void* aux_out, int allow_fast, void* stream);
@@ -79,8 +86,9 @@ int vit_gemm_g4_count(int reset);
 
 /* Tuning / test hook: the fc2 GELU' input gradient (vit_linear_dgrad with EPI_GELU_BWD / EPI_QGELU_BWD, bf16)
  * on g4 (1: the act' tile arrives by LDS-DMA in the two stage slots past the stream's end, products in place,
- * column partials for the fc1 bias gradient) or on the 8-wave V1 kernel (0); -1 keeps.  Returns the previous
- * setting (default VIT_G4_GELU, else 0). */
+ * column partials for the fc1 bias gradient; needs a reduction of at least 128) or on the 8-wave V1 kernel (0);
+ * bit 1 (2, 3) also puts the fc1 GELU pair forward on g4; -1 keeps.  Returns the previous setting (default
+ * VIT_G4_GELU, else 1). */
 int vit_gemm_g4_gelu(int on);
 
 /* Stream-K workspace for the fp32 MFMA GEMMs launched on `stream` (the reference-precision C3 path,
@@ -106,8 +114,13 @@ int vit_linear_fwd(int dtype, int out_dtype, int epi, int M, int N, int K, const
                    void* act_out, void* stream);
 
 /* F.linear input gradient dX = dY W (+ GELU' epilogue) -- autograd of VIT:142.  dbias (optional) =
- * column sums of dX as stored (bias gradient of the Linear that produced dX's forward value, e.g.
- * fc1.bias from fc2's dgrad), fused into the epilogue; partial >= vit_linear_dgrad_partial_floats. */
+ * column sums of dX (bias gradient of the Linear that produced dX's forward value, e.g. fc1.bias from
+ * fc2's dgrad); partial >= vit_linear_dgrad_partial_floats, else hipErrorInvalidValue with nothing launched.
+ * What is summed depends on the path.  On the MFMA kernels the sums are fused into the epilogue and take its f32
+ * values BEFORE they are rounded to dX's type: with the GELU' epilogue, the column sums of the f32 products
+ * acc * act'.  On the generic path (and when only `partial` is not 16-byte aligned) a second kernel reads dX
+ * back: the column sums of dX AS STORED.  The two agree for an f32 dX and differ by the bf16 roundings
+ * otherwise; each is a fixed-order sum. */
 int vit_linear_dgrad(int dtype, int out_dtype, int epi, int M, int N, int K, const void* dY, int64_t lddy,
                      const void* W, void* dX, int64_t lddx, const void* pre, float* dbias, float* partial,
                      int64_t partial_floats, int defer_reduce, void* stream);
@@ -117,7 +130,9 @@ int vit_linear_dgrad(int dtype, int out_dtype, int epi, int M, int N, int K, con
 int vit_linear_dgrad_partial_floats(int M, int K);
 
 /* F.linear weight gradient dW (f32) = dY^T X, split-K over rows with fp32 slabs
- * in `workspace` (>= split*N*K*4 bytes) -- autograd of VIT:142. */
+ * in `workspace` (>= split*N*K*4 bytes, else hipErrorInvalidValue with nothing launched) -- autograd of
+ * VIT:142.  The slab sum moves 16 bytes at a time: with N*K % 4 != 0, or a workspace or dW that is not 16-byte
+ * aligned, the call runs unsplit (the same sum in one pass); a misaligned dW also keeps the generic kernel. */
 int vit_linear_wgrad(int dtype, int M, int N, int K, const void* dY, int64_t lddy, const void* X,
                      int64_t ldx, float* dW, int split, void* workspace, int64_t ws_bytes, void* stream);
 /* The same weight gradient as split-K partials only: slabs[z][N*K] f32 for

@@ -1107,6 +1107,26 @@ static bool any_fast_ok(int dtype, int pl, int ql, int M, int N, int R, const vo
   return fast_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) || fast_f32_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq);
 }
 
+// The MFMA epilogues (bf16 and f32 alike) reach everything besides P and Q in 16-byte pieces: C and aux_out
+// by epi_vec's vstore, the permlane pairs, the bf16 image sweep and g4's buffer stores; bias, the residual /
+// act' rows and pos_embed by f32x4 / bf16x8 loads; the column-sum partial rows by csum_flush's f32x4 stores.
+// fast_ok / fast_f32_ok speak for P and Q only, so the dispatcher asks this of the rest before it takes an
+// MFMA kernel: every base 16-byte aligned and the row strides of C (shared by aux_out and pos) and aux a
+// multiple of 16 bytes.  Anything else runs the generic kernel, which moves one element at a time.
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static bool epi_fast_ok(int epi, int dtype, int out_dtype, const Epi& e) {
+  if (!aligned16(e.C) || e.ldc % (out_dtype == VIT_F32 ? 4 : 8)) return false;
+  if (!aligned16(e.bias) || !aligned16(e.csum)) return false;  // null is aligned
+  if (epi_act(epi) && !epi_act_only(epi) && !aligned16(e.aux_out)) return false;
+  if (epi == EPI_RESID || epi == EPI_GELU_BWD || epi == EPI_QGELU_BWD) {
+    // the residual stream is f32; the saved act' has the input dtype
+    const int per16 = (epi == EPI_RESID || dtype == VIT_F32) ? 4 : 8;
+    if (!aligned16(e.aux) || e.ld_aux % per16) return false;
+  }
+  if (epi == EPI_PATCH && !aligned16(e.pos)) return false;
+  return true;
+}
+
 static int g_variant = -1;  // -1: per-shape choice; 1, 2, 5: force big::V<n>, 8, 9: ping-pong (tuning)
 static int g_dbg = 0;
 
@@ -1382,7 +1402,8 @@ static int gemm_dispatch(int dtype, int out_dtype, int pl, int ql, int M, int N,
     if (pl != LAY_RC || ql != LAY_RC || split > 1) return (int)hipErrorInvalidValue;
   }
   if (M <= 0 || N <= 0) return 0;
-  if (allow_fast && fast_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) && (e.ldc % 4 == 0) && pl == LAY_RC) {
+  const bool epi_ok = epi_fast_ok(EPI, dtype, out_dtype, e);
+  if (allow_fast && fast_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) && epi_ok && pl == LAY_RC) {
     // an RC P past the 32-bit staging offsets: launch row chunks with every row-indexed operand
     // shifted (the patch epilogue's row remap and split slabs are not row-shiftable: generic path)
     const int rows = rc_chunk_rows(M, ldp);
@@ -1407,7 +1428,7 @@ static int gemm_dispatch(int dtype, int out_dtype, int pl, int ql, int M, int N,
       }
     }
   }
-  if (allow_fast && fast_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) && (e.ldc % 4 == 0)) {
+  if (allow_fast && fast_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) && epi_ok) {
 #define FAST(PLx, QLx)                                                                                  \
     if (out_dtype == VIT_F32) {                                                                         \
       if constexpr (fast_combo<PLx, QLx, EPI, float>()) return launch_fast<PLx, QLx, EPI, float, bf16>(P, ldp, Q, ldq, M, N, R, split, e, s); \
@@ -1420,8 +1441,8 @@ static int gemm_dispatch(int dtype, int out_dtype, int pl, int ql, int M, int N,
     if (pl == LAY_CR && ql == LAY_RC) { FAST(LAY_CR, LAY_RC) }
 #undef FAST
   }
-  if (allow_fast && out_dtype == VIT_F32 && fast_f32_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) && (e.ldc % 4 == 0) &&
-      ((uintptr_t)e.C & 15) == 0 && f32_grid_ok(M, N, split)) {
+  if (allow_fast && out_dtype == VIT_F32 && fast_f32_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) && epi_ok &&
+      f32_grid_ok(M, N, split)) {
     if (pl == LAY_RC && ql == LAY_RC) return launch_f32<LAY_RC, LAY_RC, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
     if constexpr (!epi_act_only(EPI)) {  // (act-only: forward layout only, checked above)
       if (pl == LAY_RC && ql == LAY_CR) return launch_f32<LAY_RC, LAY_CR, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
@@ -1564,12 +1585,15 @@ int vit_linear_dgrad(int dtype, int out_dtype, int epi, int M, int N, int K, con
   Epi e = make_epi();
   e.C = dX; e.ldc = lddx; e.aux = pre; e.ld_aux = lddx;
   const int rows = (M + 63) / 64;
-  const bool fast = any_fast_ok(dtype, LAY_RC, LAY_CR, M, K, N, dY, W, lddy, K) && (lddx % 4 == 0) &&
-                    (dtype == VIT_BF16 || (out_dtype == VIT_F32 && ((uintptr_t)dX & 15) == 0 && f32_grid_ok(M, K, 1)));
-  if (dbias) {
-    if (partial == nullptr || partial_floats < vit_linear_dgrad_partial_floats(M, K)) return (int)hipErrorInvalidValue;
-    if (fast) e.csum = partial;
-  }
+  if (dbias && (partial == nullptr || partial_floats < vit_linear_dgrad_partial_floats(M, K)))
+    return (int)hipErrorInvalidValue;
+  // the dispatcher's own rule (gemm_dispatch), with the partial rows among the epilogue's operands: a
+  // misaligned `partial` alone keeps the GEMM on its MFMA kernel without fused sums, and the column sums
+  // come from the stored dX (colsum_partial_kernel below), as on the generic path
+  if (dbias) e.csum = partial;
+  const bool fast = any_fast_ok(dtype, LAY_RC, LAY_CR, M, K, N, dY, W, lddy, K) && epi_fast_ok(epi, dtype, out_dtype, e) &&
+                    (dtype == VIT_BF16 || (out_dtype == VIT_F32 && f32_grid_ok(M, K, 1)));
+  if (!fast) e.csum = nullptr;
   int rc = gemm_any(epi, dtype, out_dtype, LAY_RC, LAY_CR, M, K, N, dY, lddy, W, K, 1, e, s);
   if (rc || !dbias || M <= 0) return rc;
   if (!fast) {  // generic path: column sums of the stored output
@@ -1615,10 +1639,13 @@ int vit_linear_wgrad(int dtype, int M, int N, int K, const void* dY, int64_t ldd
   if (M <= 0) return (int)hipMemsetAsync(dW, 0, (size_t)N * K * 4, s);
   // the MFMA kernel takes the BK-aligned rows; a ragged tail (M % 32) is added by the generic kernel
   const int tail = M % 32;
-  const bool fast = (M - tail) > 0 && any_fast_ok(dtype, LAY_CR, LAY_CR, N, K, M - tail, dY, X, lddy, ldx) &&
-                    (dtype == VIT_BF16 || (((uintptr_t)dW & 15) == 0 && f32_grid_ok(N, K, split)));
-  const int R0 = fast ? M - tail : M;
   if (split > 1 && (workspace == nullptr || ws_bytes < (int64_t)split * N * K * 4)) return (int)hipErrorInvalidValue;
+  // the slab sum moves 16 bytes at a time through slabs of N * K floats each: a slab size that is no multiple
+  // of 4 or a misaligned workspace / dW runs unsplit (the same sum, one pass)
+  if (split > 1 && (((int64_t)N * K) % 4 || !aligned16(workspace) || !aligned16(dW))) split = 1;
+  const bool fast = (M - tail) > 0 && any_fast_ok(dtype, LAY_CR, LAY_CR, N, K, M - tail, dY, X, lddy, ldx) &&
+                    aligned16(dW) && (dtype == VIT_BF16 || f32_grid_ok(N, K, split));
+  const int R0 = fast ? M - tail : M;
   Epi e = make_epi();
   int rc;
   if (split == 1) {

@@ -695,6 +695,8 @@ int g4_launch(int q_layout, int ep, const void* P, int64_t ldp, const void* Q, i
   g4_env();
   if (split > 1 || R <= 0 || R % g4::BK || N < 8 || N % 8 || e.slab || M <= 0) return -1;
   if ((int64_t)M * e.ldc * 2 >= ((int64_t)1 << 31) || e.ldc % 8) return -1;  // buffer-store offsets are int32
+  // 16-byte buffer stores into C / aux_out, f32x4 bias loads and column-partial stores
+  if (((uintptr_t)e.C | (uintptr_t)e.bias | (uintptr_t)e.csum | (ep == 2 ? (uintptr_t)e.aux_out : 0)) & 15) return -1;
   if (ep == 2) {  // fc1 GELU pair forward: C = GELU'(pre), aux_out = GELU(pre), pre = bf16(P Q^T + bias)
     if (!(g_g4[6] & 2) || q_layout != LAY_RC || !e.aux_out || e.csum) return -1;
     return launch<LAY_RC>(2, P, ldp, Q, ldq, M, N, R, e, s);

@@ -300,6 +300,26 @@ int vit_sdpa_fwd_fp8_stream(int dtype, int B, int H, int N, int head_dim, const 
                             void* o, int64_t ld_o, float* lse, float scale, int causal, void* stream);
 /* Host-side count of vit_sdpa_fwd_fp8_stream calls that launched (reset != 0 zeroes it after reading). */
 int vit_sdpa_fp8_stream_count(int reset);
+/* The quantise-once form of vit_sdpa_fwd_fp8_stream (additive to ABI 10): K and V are quantised once per
+ * head into a workspace and the forward streams the ready-made e4m3 images and E8M0 scale bytes through
+ * the LDS ring, instead of quantising them again in every 256-query block.
+ * vit_sdpa_fp8_kv_bytes: the workspace size in bytes for (B, H, N); its layout is private to the library
+ * (hipErrorInvalidValue for B, H or N < 1 or a null `bytes`). */
+int vit_sdpa_fp8_kv_bytes(int B, int H, int N, int64_t* bytes);
+/* The pre-pass: quantises K and V of the fused qkv (dtype VIT_BF16 or VIT_F32) exactly as
+ * vit_sdpa_fwd_fp8_stream does and writes every byte of the first vit_sdpa_fp8_kv_bytes bytes of ws, which
+ * is then a pure function of K and V.  Refusals (hipErrorInvalidValue, nothing launched): head_dim != 64,
+ * N < 1, ld_qkv % 8, a null ws, ws not 16-byte aligned, ws_bytes below vit_sdpa_fp8_kv_bytes. */
+int vit_sdpa_fp8_quant_kv(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* ws,
+                          int64_t ws_bytes, void* stream);
+/* The consumer: o and lse bit for bit vit_sdpa_fwd_fp8_stream's at every N, with K and V read from ws (as
+ * vit_sdpa_fp8_quant_kv left it for the same B, H, N) and nowhere else; qkv is read for Q alone, ws is not
+ * written, lse may be null.  Refusals as the pre-pass, and ld_o % 4.  Forward only. */
+int vit_sdpa_fwd_fp8_pre(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv,
+                         const void* ws, int64_t ws_bytes, void* o, int64_t ld_o, float* lse, float scale,
+                         int causal, void* stream);
+/* Host-side count of vit_sdpa_fwd_fp8_pre calls that launched (reset != 0 zeroes it after reading). */
+int vit_sdpa_fp8_pre_count(int reset);
 /* SDPA backward into dqkv (qkv layout). delta_ws >= B*H*N floats.  dbias (optional, [3*H*64]) =
  * column sums of dqkv (the qkv Linear's bias gradient), fused into the kernels;
  * partial >= vit_sdpa_bwd_partial_floats(B, N, H*64).  dbias == NULL with partial != NULL (bf16

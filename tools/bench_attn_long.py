@@ -8,7 +8,9 @@ variant's round-to-round spread are reported.
                                     [--reps 20] [--fp8]
 
 --fp8 (forward only): the streamed fp8 kernel against the streamed forward of --dtype at --n, and the resident fp8
-kernel against the streamed one at --n-resident (<= 320).
+kernel against the streamed one at --n-resident (<= 320).  At both lengths also the pre-quantised form (DESIGN
+§4.20): the pre-pass alone, the consumer alone (on a workspace made beforehand) and the pair as ops.sdpa_fwd runs it
+past 320 tokens (workspace from the caching allocator in every call).
 
 Prints one JSON line per (variant, round) and a final summary line.  --no-generic / --no-streamed skip a
 variant (a tree without the streamed kernels can still time its resident kernels with --n 0).
@@ -54,19 +56,35 @@ def time_case(c, reps):
 def main_fp8(a, dtype):
     """--fp8, forward only: at --n the streamed fp8 kernel (ops.sdpa_fwd(fp8=True, fp8_long=True)) against the
     streamed forward of --dtype; at --n-resident the resident fp8 kernel against the streamed one
-    (ops.sdpa_fwd_fp8_stream).  The variants alternate over --rounds rounds in this one process."""
+    (ops.sdpa_fwd_fp8_stream).  At both lengths the pre-quantised form: pre-pass alone, consumer alone, the pair.
+    The variants alternate over --rounds rounds in this one process."""
     L.lib().vit_sdpa_long_config(1)
     variants = []
+
+    def pre_variants(c, at):
+        """The pre-quantised form on case c: its three timings, names suffixed with `at`."""
+        B, H, N = c["B"], c["H"], c["N"]
+        ws = ops.sdpa_fp8_quant_kv(c["qkv"], B, H, N)
+
+        def pair():
+            w = ops.sdpa_fp8_quant_kv(c["qkv"], B, H, N)  # allocated per call, as ops.sdpa_fwd(fp8_pre=True) does
+            return ops.sdpa_fwd_fp8_pre(c["qkv"], w, B, H, N, o=c["o"], lse=c["lse"])
+        return [("fp8 pre-pass" + at, c, lambda: ops.sdpa_fp8_quant_kv(c["qkv"], B, H, N, ws=ws)),
+                ("fp8 consumer" + at, c, lambda: ops.sdpa_fwd_fp8_pre(c["qkv"], ws, B, H, N, o=c["o"], lse=c["lse"])),
+                ("fp8 pre-pass + consumer" + at, c, pair)]
+
     if a.n:
         c = case(a.batch, a.heads, a.n, dtype)
         fwd = lambda c=c, **kw: ops.sdpa_fwd(c["qkv"], c["B"], c["H"], c["N"], o=c["o"], lse=c["lse"], **kw)
         variants += [(f"streamed {a.dtype}", c, fwd), ("streamed fp8", c, lambda: fwd(fp8=True, fp8_long=True))]
+        variants += pre_variants(c, "")
     if a.n_resident:
         r = case(a.batch, a.heads, a.n_resident, dtype)
         variants += [("resident fp8 @ n_resident",  r, lambda: ops.sdpa_fwd(r["qkv"], r["B"], r["H"], r["N"], o=r["o"],
                                                                               lse=r["lse"], fp8=True)),
                      ("streamed fp8 @ n_resident", r, lambda: ops.sdpa_fwd_fp8_stream(r["qkv"], r["B"], r["H"], r["N"],
                                                                                        o=r["o"], lse=r["lse"]))]
+        variants += pre_variants(r, " @ n_resident")
     res = {name: [] for name, *_ in variants}
     try:
         for rnd in range(a.rounds):
@@ -86,8 +104,12 @@ def main_fp8(a, dtype):
            "n_resident": a.n_resident, "median_fwd_ms": med, "spread": spread}
     if a.n:
         out[f"streamed_{a.dtype}_over_streamed_fp8"] = round(med[f"streamed {a.dtype}"] / med["streamed fp8"], 3)
+        out["pair_over_streamed_fp8"] = round(med["fp8 pre-pass + consumer"] / med["streamed fp8"], 3)
+        out[f"pair_over_streamed_{a.dtype}"] = round(med["fp8 pre-pass + consumer"] / med[f"streamed {a.dtype}"], 3)
     if a.n_resident:
         out["streamed_fp8_over_resident_fp8"] = round(med["streamed fp8 @ n_resident"] / med["resident fp8 @ n_resident"], 3)
+        out["pair_over_resident_fp8"] = round(med["fp8 pre-pass + consumer @ n_resident"]
+                                              / med["resident fp8 @ n_resident"], 3)
     print(json.dumps(out), flush=True)
 
 

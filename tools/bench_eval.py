@@ -6,8 +6,8 @@
         bf16 forward chains' half-batch row counts (27580 / 22852 x 3072 x 768) and at C3's fc1
         (16448 x 4096 x 1024, bf16 with QuickGELU and fp32); bytes written are computed from shapes.
   vit   ViT-B/16 no-grad forward, images/s, set_forward_only(True) against (False).
-  vit384fp8  vit_base_patch16_384 no-grad forward (577 tokens), bf16 attention against the streamed fp8 kernel
-        (not in the default --what; use --batch 64).
+  vit384fp8  vit_base_patch16_384 no-grad forward (577 tokens), three legs alternated: bf16 attention, the streamed
+        fp8 kernel and the pre-quantised fp8 pair (not in the default --what; use --batch 64).
 
 Each pair is warmed up, then timed ``repeats`` times in the order A B A B ..., ``iters`` launches (or
 forwards) per timing; the record holds every repeat, the medians, the A/B difference and the repeat
@@ -114,32 +114,49 @@ def bench_vit(repeats, iters, batch):
 
 def bench_vit384_fp8(repeats, iters, batch):
     """vit_base_patch16_384 (577 tokens, bf16) no-grad forward: bf16 attention against the streamed fp8 kernel
-    (set_attention_fp8(True, long_sequences=True))."""
+    (set_attention_fp8(True, long_sequences=True)) and the pre-quantised pair (..., prequantize=True)."""
     import vit_amd
     from vit_amd import _lib as L
     torch.manual_seed(0)
     m = vit_amd.create_model("vit_base_patch16_384", num_classes=1000, compute_dtype=torch.bfloat16).cuda().eval()
     x = torch.randn(batch, 3, 384, 384, device="cuda")
 
-    def run(on):
+    def run(on, pre=False):
         def f():
-            m.set_attention_fp8(on, long_sequences=on)
+            m.set_attention_fp8(on, long_sequences=on, prequantize=pre)
             with torch.no_grad():
                 return m(x)
         return f
 
+    fa, fb, fc = run(False), run(True), run(True, True)
     c0 = L.lib().vit_sdpa_fp8_stream_count(0)
-    y_off, y_on = run(False)().float(), run(True)().float()
+    y_off, y_on = fa().float(), fb().float()
     streamed = L.lib().vit_sdpa_fp8_stream_count(0) - c0
-    ta, tb = alternate(run(False), run(True), repeats, iters, warmup=3)
+    p0 = L.lib().vit_sdpa_fp8_pre_count(0)
+    y_pre = fc().float()
+    pre = L.lib().vit_sdpa_fp8_pre_count(0) - p0
+    for _ in range(3):
+        fa(), fb(), fc()
+    torch.cuda.synchronize()
+    ta, tb, tc = [], [], []
+    for _ in range(repeats):  # A B C A B C ...
+        ta.append(_time(fa, iters))
+        tb.append(_time(fb, iters))
+        tc.append(_time(fc, iters))
     m.set_attention_fp8(False)
-    r = {"case": "vit_b16_384_nograd_forward", "a": "bf16 attention", "b": "streamed fp8 attention", "batch": batch,
-         "iters": iters, "fp8_stream_calls_per_forward": streamed,
+    r = {"case": "vit_b16_384_nograd_forward", "a": "bf16 attention", "b": "streamed fp8 attention",
+         "c": "pre-quantised fp8 attention", "batch": batch,
+         "iters": iters, "fp8_stream_calls_per_forward": streamed, "fp8_pre_calls_per_forward": pre,
          "logits_max_abs_diff": round((y_on - y_off).abs().max().item(), 5),
-         "logits_max_abs": round(y_off.abs().max().item(), 5)}
+         "logits_max_abs": round(y_off.abs().max().item(), 5),
+         "c_bitwise_equal_b": bool(torch.equal(y_pre, y_on))}
     r.update(summary(ta, tb))
-    r["a_images_per_s"] = round(batch / r["a_median_ms"] * 1e3, 1)
-    r["b_images_per_s"] = round(batch / r["b_median_ms"] * 1e3, 1)
+    mc = statistics.median(tc)
+    r.update({"c_ms": [round(t, 4) for t in tc], "c_median_ms": round(mc, 4),
+              "c_over_a": round(mc / r["a_median_ms"], 4), "c_over_b": round(mc / r["b_median_ms"], 4),
+              "c_spread": round((max(tc) - min(tc)) / mc, 4)})
+    for leg in "abc":
+        r[leg + "_images_per_s"] = round(batch / r[leg + "_median_ms"] * 1e3, 1)
     return [r]
 
 

@@ -644,6 +644,102 @@ __global__ __launch_bounds__(F8_THREADS, 4) void attn_fwd_fp8_stream(const T* __
     f8_store<T>(o + ((int64_t)b * N + q) * ld_o + hh * 64, lse ? lse + (int64_t)bh * N + q : nullptr, oacc, l, m * c2, h);
 }
 
+// ---------------------------------------------------------------------------
+// Quantise-once form of the streamed fp8 forward (opt-in).  attn_fwd_fp8_stream quantises a head's K and V once
+// per 256-query block; here attn_fp8_quant_kv does it once per head into a workspace and attn_fwd_fp8_pre streams
+// the ready-made chunk images through the same ring.
+//   workspace: [B*H][ceil(N / 64)] chunk images of F8S_BUF bytes, each byte for byte the ring buffer that
+//   f8s_commit builds (Kimg | V^T | K scales | V scales), so the consumer's copy into LDS is lane-linear: 540
+//   16-B pieces for 512 threads.  V^T's 4 pad bytes per row, which nothing reads, are written as zero: the
+//   workspace is a pure function of K and V.
+//   attn_fp8_quant_kv: grid (B*H, ceil(N / 64)), one chunk per workgroup: f8s_fetch_k / f8s_fetch_v / f8s_commit
+//   into LDS, one barrier, coalesced 16-B stores.  Keys past N: the streamed kernel's rule (row N - 1, zeroed).
+//   attn_fwd_fp8_pre: attn_fwd_fp8_stream's grid, wave-to-query mapping, ring, loop and barriers; the fetch is
+//   this thread's pieces of the next image (requested before the tile step, 4 or 8 registers in flight over it),
+//   the commit their LDS write.  Q is still quantised here, once per wave.  The bytes in LDS and every operation
+//   on them are the streamed kernel's: o and lse are its bits at every N.
+// ---------------------------------------------------------------------------
+constexpr int F8P_PIECES = F8S_BUF / 16;            // 16-B pieces of a chunk image
+constexpr int F8P_TAIL = F8P_PIECES - F8_THREADS;   // threads that move a second piece
+static_assert(F8S_BUF % 16 == 0 && F8P_TAIL >= 0 && F8P_TAIL <= F8_THREADS, "one or two pieces per thread");
+static_assert(F8S_VROW % 4 == 0 && F8S_VT % 4 == 0 && F8S_VROW - F8S_CH == 4, "V^T's pad is one aligned word per row");
+typedef int f8p_piece __attribute__((ext_vector_type(4)));
+
+template <typename T>
+__global__ __launch_bounds__(F8_THREADS) void attn_fp8_quant_kv(const T* __restrict__ qkv, int64_t ld_qkv, int D, int H,
+                                                                int N, unsigned char* __restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) unsigned char buf[F8S_BUF];
+  const int bh = blockIdx.x, b = bh / H, hh = bh - b * H;
+  const int tid = threadIdx.x, j0 = blockIdx.y * F8S_CH;
+  const T* base = qkv + (int64_t)b * N * ld_qkv + hh * 64;
+  F8Piece<T> pc;
+  f8s_fetch_k<T>(pc, base, ld_qkv, D, j0, N);
+  f8s_fetch_v<T>(pc, base, ld_qkv, D, j0, N);
+  if (tid < 64) *reinterpret_cast<int*>(buf + F8S_VT + tid * F8S_VROW + F8S_CH) = 0;  // the pad f8s_commit leaves
+  f8s_commit<T>(buf, pc, j0, N);
+  __syncthreads();
+  f8p_piece* dst = reinterpret_cast<f8p_piece*>(ws + ((int64_t)bh * gridDim.y + blockIdx.y) * F8S_BUF);
+  const f8p_piece* src = reinterpret_cast<const f8p_piece*>(buf);
+  dst[tid] = src[tid];
+  if (tid < F8P_TAIL) dst[F8_THREADS + tid] = src[F8_THREADS + tid];
+}
+
+struct F8PrePiece { f8p_piece a, b; };
+__device__ __forceinline__ void f8p_fetch(F8PrePiece& p, const unsigned char* img) {
+  const int tid = threadIdx.x;
+  const f8p_piece* src = reinterpret_cast<const f8p_piece*>(img);
+  p.a = src[tid];
+  if (tid < F8P_TAIL) p.b = src[F8_THREADS + tid];
+}
+__device__ __forceinline__ void f8p_commit(unsigned char* buf, const F8PrePiece& p) {
+  const int tid = threadIdx.x;
+  f8p_piece* dst = reinterpret_cast<f8p_piece*>(buf);
+  dst[tid] = p.a;
+  if (tid < F8P_TAIL) dst[F8_THREADS + tid] = p.b;
+}
+
+template <typename T>
+__global__ __launch_bounds__(F8_THREADS, 4) void attn_fwd_fp8_pre(const T* __restrict__ qkv, int64_t ld_qkv, int H,
+                                                                 int N, const unsigned char* __restrict__ ws,
+                                                                 float scale, T* __restrict__ o, int64_t ld_o,
+                                                                 float* __restrict__ lse, int causal) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2][F8S_BUF];
+  const int bh = blockIdx.x, b = bh / H, hh = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const T* base = qkv + (int64_t)b * N * ld_qkv + hh * 64;
+  const int h = lane >> 5, l31 = lane & 31;
+  const int q0 = blockIdx.y * F8S_QB + wave * 32, q = q0 + l31;
+  i32x8 qf;
+  int qsc;
+  f8_q_frag<T>(base + (int64_t)min(q, N - 1) * ld_qkv, h, qf, qsc);
+  const int nc = (N + F8S_CH - 1) / F8S_CH;
+  const unsigned char* img = ws + (int64_t)bh * nc * F8S_BUF;  // this head's chunk images
+  F8PrePiece pc = {};
+  f8p_fetch(pc, img);
+  f8p_commit(smem[0], pc);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  float m = -INFINITY, l = 0.f;
+  f32x16 oacc[2] = {};
+  const bool live = q0 < N;  // wave-uniform; the trip count below does not depend on it
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const unsigned char* buf = smem[c & 1];
+    const int j0 = c * F8S_CH;
+    const bool more = c + 1 < nc;  // the same in every wave of the workgroup
+    if (more) f8p_fetch(pc, img + (int64_t)(c + 1) * F8S_BUF);
+    if (live)
+      f8_tile_step(buf, buf + F8S_KSC, buf + F8S_VT, F8S_VROW, buf + F8S_VSC, 1, j0, N, q, causal, qf, qsc, c2, h, l31,
+                   m, l, oacc);
+    if (more) f8p_commit(smem[(c + 1) & 1], pc);
+    __syncthreads();
+  }
+  if (!live) return;
+  l += __shfl_xor(l, 32, 64);
+  if (q < N)
+    f8_store<T>(o + ((int64_t)b * N + q) * ld_o + hh * 64, lse ? lse + (int64_t)bh * N + q : nullptr, oacc, l, m * c2, h);
+}
+
 // qkv-bias gradient partials of one (b, h): sum this workgroup's rows of dq (or dk, dv)
 // -- per lane over its rows, across the 16 lanes of a row group, across the 8 waves
 // through LDS (reused after the main loop) -- into out[0..63] (and out[D..] for dk,
@@ -2158,6 +2254,7 @@ static int g_long_mode = -1;
 static int g_long_count = 0;      // bf16 streamed calls
 static int g_long_f32_count = 0;  // f32 streamed calls
 static int g_fp8_stream_count = 0;  // vit_sdpa_fwd_fp8_stream calls
+static int g_fp8_pre_count = 0;     // vit_sdpa_fwd_fp8_pre calls
 static bool attn_long_stream() {
   if (g_long_mode >= 0) return g_long_mode != 0;
   static const int v = [] { const char* e = getenv("VIT_ATTN_LONG"); return e && *e == '0' ? 0 : 1; }();
@@ -2706,6 +2803,65 @@ int vit_sdpa_fwd_fp8_stream(int dtype, int B, int H, int N, int head_dim, const 
 int vit_sdpa_fp8_stream_count(int reset) {
   const int c = g_fp8_stream_count;
   if (reset) g_fp8_stream_count = 0;
+  return c;
+}
+
+// The quantise-once pair (attn_fp8_quant_kv, attn_fwd_fp8_pre).  The workspace layout is private to this file:
+// callers size it with vit_sdpa_fp8_kv_bytes.
+static int64_t fp8_kv_bytes(int B, int H, int N) {
+  return (int64_t)B * H * ((N + F8S_CH - 1) / F8S_CH) * F8S_BUF;
+}
+static bool fp8_pre_args_ok(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv,
+                            const void* ws, int64_t ws_bytes) {
+  if (head_dim != 64 || B < 1 || H < 1 || N < 1 || (ld_qkv % 8) || qkv == nullptr) return false;
+  if (dtype != VIT_BF16 && dtype != VIT_F32) return false;
+  if (ws == nullptr || ((uintptr_t)ws % 16) || ws_bytes < fp8_kv_bytes(B, H, N)) return false;
+  return (N + F8S_CH - 1) / F8S_CH <= 65535;  // grid.y of the pre-pass; the consumer's is smaller
+}
+int vit_sdpa_fp8_kv_bytes(int B, int H, int N, int64_t* bytes) {
+  if (B < 1 || H < 1 || N < 1 || bytes == nullptr) return (int)hipErrorInvalidValue;
+  *bytes = fp8_kv_bytes(B, H, N);
+  return 0;
+}
+// The pre-pass: K and V of qkv, quantised as vit_sdpa_fwd_fp8_stream quantises them, into ws (every byte of the
+// first vit_sdpa_fp8_kv_bytes bytes is written).
+int vit_sdpa_fp8_quant_kv(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, void* ws,
+                          int64_t ws_bytes, void* stream) {
+  if (!fp8_pre_args_ok(dtype, B, H, N, head_dim, qkv, ld_qkv, ws, ws_bytes)) return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  const int D = H * 64;
+  const dim3 grid(B * H, (N + F8S_CH - 1) / F8S_CH);
+  if (dtype == VIT_BF16)
+    hipLaunchKernelGGL(attn_fp8_quant_kv<bf16>, grid, dim3(F8_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N,
+                       (unsigned char*)ws);
+  else
+    hipLaunchKernelGGL(attn_fp8_quant_kv<float>, grid, dim3(F8_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
+                       (unsigned char*)ws);
+  VIT_CHECK_LAUNCH();
+  return 0;
+}
+// The consumer: vit_sdpa_fwd_fp8_stream's o and lse, bit for bit, with K and V taken from ws alone (qkv is read
+// for Q).  Same refusals, and ws as in vit_sdpa_fp8_quant_kv.
+int vit_sdpa_fwd_fp8_pre(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv, const void* ws,
+                         int64_t ws_bytes, void* o, int64_t ld_o, float* lse, float scale, int causal, void* stream) {
+  if (!fp8_pre_args_ok(dtype, B, H, N, head_dim, qkv, ld_qkv, ws, ws_bytes) || (ld_o % 4) || o == nullptr)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(B * H, (N + F8S_QB - 1) / F8S_QB);
+  if (dtype == VIT_BF16)
+    hipLaunchKernelGGL(attn_fwd_fp8_pre<bf16>, grid, dim3(F8_THREADS), 0, s, (const bf16*)qkv, ld_qkv, H, N,
+                       (const unsigned char*)ws, scale, (bf16*)o, ld_o, lse, causal);
+  else
+    hipLaunchKernelGGL(attn_fwd_fp8_pre<float>, grid, dim3(F8_THREADS), 0, s, (const float*)qkv, ld_qkv, H, N,
+                       (const unsigned char*)ws, scale, (float*)o, ld_o, lse, causal);
+  VIT_CHECK_LAUNCH();
+  ++g_fp8_pre_count;
+  return 0;
+}
+// Host-side count of vit_sdpa_fwd_fp8_pre calls that launched (reset != 0 zeroes it after reading).
+int vit_sdpa_fp8_pre_count(int reset) {
+  const int c = g_fp8_pre_count;
+  if (reset) g_fp8_pre_count = 0;
   return c;
 }
 

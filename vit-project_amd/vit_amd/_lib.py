@@ -63,6 +63,10 @@ SIGNATURES = {
     "vit_sdpa_fwd_fp8": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, i32, vp],
     "vit_sdpa_fwd_fp8_stream": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, i32, vp],
     "vit_sdpa_fp8_stream_count": [i32],
+    "vit_sdpa_fp8_kv_bytes": [i32, i32, i32, vp],
+    "vit_sdpa_fp8_quant_kv": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp],
+    "vit_sdpa_fwd_fp8_pre": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, f32, i32, vp],
+    "vit_sdpa_fp8_pre_count": [i32],
     "vit_sdpa_fwd_cls": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, vp],
     "vit_sdpa_cls_count": [i32],
     "vit_sdpa_cls1_fwd": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, vp],

@@ -272,6 +272,7 @@ class CLIP(nn.Module):
         self._text_cache = None
         self.attention_fp8 = False  # set_attention_fp8
         self.attention_fp8_long = False
+        self.attention_fp8_pre = False
         self.cls_tail = False  # set_cls_tail
         self.initialize_parameters()
 
@@ -315,7 +316,7 @@ class CLIP(nn.Module):
                 self._shadows.add(p, T)
         self._shadows.refresh()
 
-    def set_attention_fp8(self, enable: bool = True, long_sequences: bool = False):
+    def set_attention_fp8(self, enable: bool = True, long_sequences: bool = False, prequantize: bool = False):
         """Block-scaled e4m3 attention (vit_sdpa_fwd_fp8, BASELINE configs[4]) in every block whose
         forward needs no backward: the frozen blocks in front of the first trainable one in each
         tower (CLIP-HBA trains only the DoRA blocks 22-23 / 11, NEWP:484-544) and all blocks of a
@@ -323,9 +324,12 @@ class CLIP(nn.Module):
         The resident fp8 kernel holds at most 320 tokens: on ``ViT-L/14@336px`` (577 visual tokens) a
         forward with fp8 attention enabled raises ``ValueError`` unless ``long_sequences`` is set, which
         sends lengths past 320 to the streamed fp8 kernel (vit_sdpa_fwd_fp8_stream; shorter ones, the text
-        tower's 77 among them, keep the resident kernel).  ``set_attention_fp8(False)`` clears both."""
-        self.attention_fp8 = bool(enable)
-        self.attention_fp8_long = bool(enable) and bool(long_sequences)
+        tower's 77 among them, keep the resident kernel).  ``prequantize`` (with ``long_sequences``; alone it
+        would do nothing and raises ``ValueError``) quantises K and V of those lengths once per head into a
+        per-call workspace for the pre-quantised kernel (vit_sdpa_fp8_quant_kv, vit_sdpa_fwd_fp8_pre): the
+        streamed kernel's bits, so no cache key depends on it.  ``set_attention_fp8(False)`` clears all three."""
+        self.attention_fp8, self.attention_fp8_long, self.attention_fp8_pre = ops.fp8_switches(
+            enable, long_sequences, prequantize)
 
     def set_cls_tail(self, enable: bool = True):
         """Run the visual tower's last block as the class-token tail: ``ln_post`` reads ``x[:, 0]``
@@ -338,7 +342,7 @@ class CLIP(nn.Module):
     def _cfg(self, heads, causal, frozen=False):
         fp8 = self.attention_fp8 and (frozen or not torch.is_grad_enabled())
         return dict(heads=heads, eps=1e-5, quick_gelu=True, dtype=self.compute_dtype, causal=causal, attn_fp8=fp8,
-                    attn_fp8_long=self.attention_fp8_long)
+                    attn_fp8_long=self.attention_fp8_long, attn_fp8_pre=self.attention_fp8_pre)
 
     # -- towers -----------------------------------------------------------------
     def _visual_stem(self, image, pos_embedding):
@@ -561,7 +565,7 @@ class CLIPHBA(nn.Module):
 
     def __init__(self, classnames, backbone_name="ViT-L/14", pos_embedding=False, clip_model=None,
                  tokenized_prompts=None, compute_dtype=torch.float32, attention_fp8=False,
-                 attention_fp8_long=False, cls_tail=False):
+                 attention_fp8_long=False, cls_tail=False, attention_fp8_prequant=False):
         super().__init__()
         self.num_clip = len(classnames)
         if clip_model is None:
@@ -572,7 +576,8 @@ class CLIPHBA(nn.Module):
         self.clip_model = clip_model
         self.clip_model.float()
         if attention_fp8:  # BASELINE configs[4]: fp8 attention in the frozen / no-grad blocks
-            self.clip_model.set_attention_fp8(True, long_sequences=attention_fp8_long)
+            self.clip_model.set_attention_fp8(True, long_sequences=attention_fp8_long,
+                                              prequantize=attention_fp8_prequant)
         if cls_tail:  # the visual tower's last block on the class rows alone (CLIP.set_cls_tail)
             self.clip_model.set_cls_tail(True)
         self.pos_embedding = pos_embedding

@@ -314,6 +314,7 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False):
     causal = bool(cfg.get("causal", False))
     attn_fp8 = bool(cfg.get("attn_fp8", False))  # forward-only blocks (frozen prefix, no-grad passes)
     attn_fp8_long = bool(cfg.get("attn_fp8_long", False))  # past 320 tokens: the streamed fp8 kernel
+    attn_fp8_pre = bool(cfg.get("attn_fp8_pre", False))  # ... from K and V quantised once per head
     if attn_fp8:
         ops.check_fp8_tokens(N, long=attn_fp8_long)  # before anything is queued on the side stream
 
@@ -351,7 +352,7 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False):
             ln1(sl),
             lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
-                                 fp8=attn_fp8, fp8_long=attn_fp8_long),
+                                 fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre),
             lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), out=pb[sl]),
             lambda: ops.add_layer_norm_fwd(x2[sl], pb[sl], xm[sl], n2w.detach(), n2b.detach(), eps, out=h2[sl],
                                            mean=m2[sl], rstd=r2[sl]),
@@ -408,7 +409,7 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False):
                                        rstd=r1[sl]),
             lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
-                                 fp8=attn_fp8, fp8_long=attn_fp8_long),
+                                 fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre),
             lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), epi=L.EPI_RESID, resid=x2[sl], out=xm[sl]),
             lambda: ops.layer_norm_fwd(xm[sl], n2w.detach(), n2b.detach(), eps, T, out=h2[sl], mean=m2[sl],
                                        rstd=r2[sl]),
@@ -832,6 +833,7 @@ class VisionTransformer(nn.Module):
         self._defer_grad_join = False
         self._attn_fp8 = False
         self._attn_fp8_long = False
+        self._attn_fp8_pre = False
         self.init_weights()
 
     # timm init_weights_vit_timm; exact RNG stream differs from timm
@@ -906,7 +908,7 @@ class VisionTransformer(nn.Module):
         with gradient hooks, which read ``.grad`` during the backward on the caller's stream."""
         self._defer_grad_join = bool(enable)
 
-    def set_attention_fp8(self, enable: bool = True, long_sequences: bool = False):
+    def set_attention_fp8(self, enable: bool = True, long_sequences: bool = False, prequantize: bool = False):
         """Run attention as block-scaled e4m3 MFMA (vit_sdpa_fwd_fp8) in forward passes that build no
         autograd graph (``torch.no_grad()``: validation, ``compute_rsa_score``'s embeddings) --
         BASELINE configs[4].  Training forwards keep the bf16 kernels their backward needs.
@@ -914,9 +916,12 @@ class VisionTransformer(nn.Module):
         The resident fp8 kernel holds at most 320 tokens: past that (the 384-pixel and patch-8 models) such a
         forward raises ``ValueError`` unless ``long_sequences`` is set, which sends those lengths to the streamed
         fp8 kernel (vit_sdpa_fwd_fp8_stream; up to 320 tokens the resident kernel runs either way).
-        ``set_attention_fp8(False)`` clears both switches."""
-        self._attn_fp8 = bool(enable)
-        self._attn_fp8_long = bool(enable) and bool(long_sequences)
+        ``prequantize`` (with ``long_sequences``; alone it would do nothing and raises ``ValueError``) quantises
+        K and V of those lengths once per head into a per-call workspace (vit_sdpa_fp8_quant_kv) for the
+        pre-quantised kernel (vit_sdpa_fwd_fp8_pre): the streamed kernel's bits.
+        ``set_attention_fp8(False)`` clears all three switches."""
+        self._attn_fp8, self._attn_fp8_long, self._attn_fp8_pre = ops.fp8_switches(
+            enable, long_sequences, prequantize)
 
     def set_grad_ready_hook(self, fn):
         """fn(lo, hi) is called by each block's backward once the block's gradients (the flat
@@ -955,6 +960,7 @@ class VisionTransformer(nn.Module):
         # fp8 attention (set_attention_fp8): forward passes that build no graph (eval / RSA)
         cfg["attn_fp8"] = self._attn_fp8 and not torch.is_grad_enabled()
         cfg["attn_fp8_long"] = self._attn_fp8_long
+        cfg["attn_fp8_pre"] = self._attn_fp8_pre
         D = self.embed_dim
         if (self.compute_dtype != torch.float32 or _FUSED_RESID_F32[0]) and ops.add_layer_norm_supported(D):
             cfg["resid"] = {"pending": None}  # residual adds inside the LayerNorms (_BlockFn.forward)

@@ -484,11 +484,24 @@ def check_fp8_tokens(N, long=False):
                          f"fp8 kernel (set_attention_fp8(True, long_sequences=True))")
 
 
-def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=False, fp8_long=False):
+def fp8_switches(enable, long_sequences=False, prequantize=False):
+    """The three stored switches of ``set_attention_fp8`` (fp8, streamed past 320 tokens, pre-quantised K / V):
+    the pre-quantised kernel is a form of the streamed one, so asking for it without ``long_sequences`` would
+    be a silent no-op and raises instead."""
+    if enable and prequantize and not long_sequences:
+        raise ValueError("set_attention_fp8(prequantize=True) needs long_sequences=True: up to 320 tokens the "
+                         "resident fp8 kernel already quantises K and V once per head")
+    on = bool(enable)
+    return on, on and bool(long_sequences), on and bool(long_sequences) and bool(prequantize)
+
+
+def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=False, fp8_long=False, fp8_pre=False):
     """softmax(q k^T * scale) v per (b, h) from the fused qkv [B*N, 3D], any N (past 288 tokens the
     streamed bf16 or f32 kernels, or the generic ones for causal / misaligned rows); fp8: the block-scaled e4m3
     MFMA kernels (forward only: their lse is not the bf16 backward's) -- the resident one up to 320 tokens,
-    past that the streamed one if ``fp8_long``, else ValueError."""
+    past that the streamed one if ``fp8_long``, else ValueError.  ``fp8_pre`` (with ``fp8`` and ``fp8_long``,
+    past 320 tokens only): K and V are quantised once into a workspace that lives for this call and the
+    pre-quantised kernel streams it -- the streamed kernel's bits."""
     if fp8:
         check_fp8_tokens(N, long=fp8_long)
     D = H * 64
@@ -497,6 +510,9 @@ def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=Fal
     if lse is None:
         lse = torch.empty(B * H * N, dtype=torch.float32, device=qkv2d.device)
     scale = 64 ** -0.5 if scale is None else scale
+    if fp8 and fp8_long and fp8_pre and N > FP8_ATTN_MAX_TOKENS:
+        ws = sdpa_fp8_quant_kv(qkv2d, B, H, N)  # from the caching allocator, on this stream; not kept
+        return sdpa_fwd_fp8_pre(qkv2d, ws, B, H, N, o=o, scale=scale, lse=lse, causal=causal)
     name = "vit_sdpa_fwd"
     if fp8:
         name = "vit_sdpa_fwd_fp8" if N <= FP8_ATTN_MAX_TOKENS else "vit_sdpa_fwd_fp8_stream"
@@ -516,6 +532,38 @@ def sdpa_fwd_fp8_stream(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=Fal
     scale = 64 ** -0.5 if scale is None else scale
     call("vit_sdpa_fwd_fp8_stream", L.dt(qkv2d), B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(o), o.stride(0),
          ptr(lse), float(scale), int(causal), _s(qkv2d))
+    return o, lse
+
+
+def sdpa_fp8_kv_bytes(B, H, N):
+    """Bytes of the quantised K / V workspace of :func:`sdpa_fp8_quant_kv` (vit_sdpa_fp8_kv_bytes)."""
+    n = L.i64(0)
+    call("vit_sdpa_fp8_kv_bytes", B, H, N, L.C.addressof(n))
+    return int(n.value)
+
+
+def sdpa_fp8_quant_kv(qkv2d, B, H, N, ws=None):
+    """The pre-pass of the pre-quantised fp8 forward (vit_sdpa_fp8_quant_kv) at any N: K and V of qkv2d as
+    block-scaled e4m3 in ``ws`` (a uint8 tensor of at least sdpa_fp8_kv_bytes bytes; allocated if None).
+    Returns ``ws``."""
+    if ws is None:
+        ws = torch.empty(sdpa_fp8_kv_bytes(B, H, N), dtype=torch.uint8, device=qkv2d.device)
+    call("vit_sdpa_fp8_quant_kv", L.dt(qkv2d), B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(ws),
+         ws.numel() * ws.element_size(), _s(qkv2d))
+    return ws
+
+
+def sdpa_fwd_fp8_pre(qkv2d, ws, B, H, N, o=None, scale=None, lse=None, causal=False):
+    """The pre-quantised fp8 forward (vit_sdpa_fwd_fp8_pre) at any N, for tests and tools: Q from qkv2d, K and
+    V from ``ws`` (sdpa_fp8_quant_kv); o and lse are bit for bit sdpa_fwd_fp8_stream's."""
+    D = H * 64
+    if o is None:
+        o = torch.empty(B * N, D, dtype=qkv2d.dtype, device=qkv2d.device)
+    if lse is None:
+        lse = torch.empty(B * H * N, dtype=torch.float32, device=qkv2d.device)
+    scale = 64 ** -0.5 if scale is None else scale
+    call("vit_sdpa_fwd_fp8_pre", L.dt(qkv2d), B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(ws),
+         ws.numel() * ws.element_size(), ptr(o), o.stride(0), ptr(lse), float(scale), int(causal), _s(qkv2d))
     return o, lse
 
 

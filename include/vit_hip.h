@@ -284,6 +284,21 @@ int vit_sdpa_cls1_bwd(int dtype, int B, int H, int N, int head_dim, const void* 
                       const void* o_cls, int64_t ld_o, const void* do_cls, int64_t ld_do, const float* lse_cls,
                       void* dqkv, int64_t ld_dqkv, float scale, void* stream);
 int vit_sdpa_cls1_count(int reset);
+/* One-query attention at a row per sequence (additive to ABI 10), forward only: the query of (b, h) is row
+ * qrow[b] of sequence b, the keys and values rows 0 .. nk - 1 with nk = qrow[b] + 1 if causal != 0, else N.  For
+ * the last block of the CLIP text tower, of whose output ln_final reads the EOT row alone.  The
+ * device code, decomposition and summation order are vit_sdpa_cls1_fwd's: qrow[b] = 0 for every b with causal = 0
+ * gives that call's o and lse bit for bit, and a causal call equals the unmasked call on the first qrow[b] + 1
+ * rows.  qrow: int64 [B] on the device; the host cannot see its values, so the kernel clamps each to [0, N - 1].
+ * No K / V row >= nk is loaded; nothing but o_row [B, D] (qkv dtype, row b at b * ld_o, column h * 64) and
+ * lse_row [B * H] (f32, natural log) is stored.  There is no backward: a caller takes this route only where no
+ * attention backward follows.  head_dim != 64, N <= 0 or N > 2048, ld_qkv < 3D, a null operand (qrow included),
+ * or a row stride or address that is not a multiple of 16 bytes: hipErrorInvalidValue with nothing queued.
+ * vit_sdpa_row1_count: host-side count of its launches (reset != 0 zeroes it after reading). */
+int vit_sdpa_row1_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv,
+                      const int64_t* qrow, int causal, void* o_row, int64_t ld_o, float* lse_row, float scale,
+                      void* stream);
+int vit_sdpa_row1_count(int reset);
 /* fp8 scaled-dot-product attention forward (BASELINE configs[4]: the sweep's frozen CLIP tower blocks
  * and the RSA evaluation forward; replaces the same F.scaled_dot_product_attention call as
  * vit_sdpa_fwd): q/k/v quantised in-kernel to block-scaled OCP e4m3 (E8M0 scale per 32 values),

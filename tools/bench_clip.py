@@ -9,6 +9,9 @@ the default bench line carries in both dtypes).  Prints one JSON line.
 ``--cls-tail`` times the step with the visual tower's class-token tail (``CLIP.set_cls_tail``) off
 and on, alternated on one model in one process over ``--rounds`` rounds (>= 3): medians, the round-to-round
 spread ``(max - min) / median``, the ratio, and the on-against-off relative difference of the predictions.
+
+``--eot-tail`` does the same for the text tower's EOT tail (``CLIP.set_eot_tail``); given together
+with ``--cls-tail`` the class-token tail stays on throughout and the EOT tail alone alternates.
 """
 import argparse
 import json
@@ -61,8 +64,9 @@ def lora_leg(dev, dtype, batch, steps, warmup):
             "final_loss": round(float(loss.item()), 4)}
 
 
-def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds):
-    """The C3 step (bench.c3_leg's model, data and optimizer) with the class-token tail off and on, alternated."""
+def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds, which="cls", cls_fixed=False):
+    """The C3 step (bench.c3_leg's model, data and optimizer) with the class-token tail (``which`` = "cls") or the
+    EOT tail ("eot"; ``cls_fixed``: the class-token tail on throughout) off and on, alternated."""
     import statistics
     import torch
     import vit_amd
@@ -79,6 +83,10 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds):
     opt = vit_amd.FusedAdamW([p for p in m.parameters() if p.requires_grad], lr=3e-4)
     x = torch.randn(batch, 3, 224, 224, device=dev)
     y = torch.randn(batch, 66, device=dev) * 0.5 + 1.0
+    switch = m.clip_model.set_cls_tail if which == "cls" else m.clip_model.set_eot_tail
+    if which == "eot":
+        m.clip_model.set_cls_tail(cls_fixed)
+    key = which + "_tail"
 
     def window(n):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -95,27 +103,28 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds):
 
     preds = {}
     for on in (False, True):  # the same parameters: before any step moves them
-        m.clip_model.set_cls_tail(on)
+        switch(on)
         with torch.no_grad():
             preds[on] = m(x).double()
     for on in (False, True):
-        m.clip_model.set_cls_tail(on)
+        switch(on)
         window(warmup)
     ms = {False: [], True: []}
     for _ in range(rounds):
         for on in (False, True):
-            m.clip_model.set_cls_tail(on)
+            switch(on)
             ms[on].append(window(steps))
-    m.clip_model.set_cls_tail(False)
+    switch(False)
 
     def summary(v):
         med = statistics.median(v)
         return {"rounds": [round(t, 3) for t in v], "median": round(med, 3), "spread": round((max(v) - min(v)) / med, 4)}
 
     off, on = summary(ms[False]), summary(ms[True])
-    return {"ms_per_step": {"cls_tail_off": off, "cls_tail_on": on}, "cls_tail_speedup": round(off["median"] / on["median"], 4),
-            "images_per_sec": {"cls_tail_off": round(batch / off["median"] * 1e3, 2),
-                               "cls_tail_on": round(batch / on["median"] * 1e3, 2)},
+    return {"ms_per_step": {key + "_off": off, key + "_on": on}, key + "_speedup": round(off["median"] / on["median"], 4),
+            "images_per_sec": {key + "_off": round(batch / off["median"] * 1e3, 2),
+                               key + "_on": round(batch / on["median"] * 1e3, 2)},
+            "cls_tail_throughout": bool(which == "eot" and cls_fixed),
             "prediction_rel_diff_on_vs_off": float((preds[True] - preds[False]).abs().max() / preds[False].abs().max()),
             "prediction_bound": 1e-3 if dtype == "f32" else 3e-2,
             "batch": batch, "steps": steps, "warmup": warmup, "rounds": rounds, "dtype": dtype}
@@ -131,13 +140,17 @@ def main():
     ap.add_argument("--adapter", choices=["dora", "lora"], default="dora")
     ap.add_argument("--cls-tail", action="store_true",
                     help="alternate the visual tower's class-token tail off and on in one process")
-    ap.add_argument("--rounds", type=int, default=3, help="rounds of the --cls-tail alternation (>= 3)")
+    ap.add_argument("--eot-tail", action="store_true",
+                    help="alternate the text tower's EOT tail off and on in one process (with --cls-tail: that tail on "
+                         "throughout)")
+    ap.add_argument("--rounds", type=int, default=3, help="rounds of the --cls-tail / --eot-tail alternation (>= 3)")
     a = ap.parse_args()
     import torch
-    if a.cls_tail:
+    if a.cls_tail or a.eot_tail:
         if a.rounds < 3:
             ap.error("--rounds must be at least 3: the spread is part of the record")
-        r = cls_tail_leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup, a.adapter, a.rounds)
+        r = cls_tail_leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup, a.adapter, a.rounds,
+                         "eot" if a.eot_tail else "cls", a.cls_tail)
     else:
         leg = bench.c3_leg if a.adapter == "dora" else lora_leg
         r = leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup)

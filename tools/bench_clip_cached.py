@@ -25,6 +25,10 @@ uncached and cached with the tail off and then on, on the same model in the same
 ``*_tail`` series, ``cls_tail_speedup`` for the cached and the uncached pass and the on-against-off relative
 difference of a batch's predictions; the records are named ``bench_clip_cached_clstail_{dtype}.json``.
 
+``--eot-tail`` does the same for the text tower's EOT tail (``CLIP.set_eot_tail``): the ``*_tail``
+series and ``eot_tail_speedup`` are then that switch's; given together with ``--cls-tail`` the class-token tail
+stays on throughout and the EOT tail alone alternates.  Records: ``bench_clip_cached_eottail[_clstail]_{dtype}.json``.
+
 ``--adapter lora`` puts the reference's LoRA pair (NEWP:339-404) where DoRA stands; its records are named
 ``bench_clip_cached_lora_{dtype}.json``.
 """
@@ -97,15 +101,21 @@ def model_leg(a, dtype_name):
         pred_diff = float((pc - pu).abs().max() / pu.abs().max())
 
     fixed = caches["train"].take(torch.arange(a.batch))
-    tails = (False, True) if a.cls_tail else (False,)
+    tails = (False, True) if (a.cls_tail or a.eot_tail) else (False,)
+    # the switch that alternates: the EOT tail if asked for (the class-token tail then stays as --cls-tail says)
+    set_tail = m.clip_model.set_eot_tail if a.eot_tail else m.clip_model.set_cls_tail
+    tail_key = "eot_tail" if a.eot_tail else "cls_tail"
+    if a.eot_tail:
+        m.clip_model.set_cls_tail(a.cls_tail)
     vname = lambda c, t: ("cached" if c else "uncached") + ("_tail" if t else "")
     tail_diff = None
-    if a.cls_tail:  # the same batch's predictions with the tail on against off (cached pass)
+    if len(tails) > 1:  # the same batch's predictions with the tail on against off (cached pass)
         with torch.no_grad():
-            m.clip_model.set_cls_tail(True)
+            p0 = m(visual_prefix=caches["train"].take(idx)).double()
+            set_tail(True)
             pt = m(visual_prefix=caches["train"].take(idx)).double()
-            m.clip_model.set_cls_tail(False)
-        tail_diff = float((pt - pc).abs().max() / pc.abs().max())
+            set_tail(False)
+        tail_diff = float((pt - p0).abs().max() / p0.abs().max())
 
     def steps(cached, n):
         m.train()
@@ -131,7 +141,7 @@ def model_leg(a, dtype_name):
                                                      cache_visual_prefix=caches["inference"] if c else False),
     }
     for t in tails:  # every shape of the timed windows, once
-        m.clip_model.set_cls_tail(t)
+        set_tail(t)
         for c in (False, True):
             steps(c, a.warmup)
             passes["evaluate_362_seconds"](c)
@@ -141,7 +151,7 @@ def model_leg(a, dtype_name):
     no_gather = []
     for _ in range(a.rounds):
         for t in tails:
-            m.clip_model.set_cls_tail(t)
+            set_tail(t)
             for c in (False, True):
                 name = vname(c, t)
                 dt, loss = _timed(lambda: steps(c, a.steps), sync)
@@ -150,7 +160,7 @@ def model_leg(a, dtype_name):
                 for k in ("evaluate_362_seconds", "rsa_48_seconds"):
                     dt, _ = _timed(lambda: passes[k](c), sync)
                     res[k][name].append(dt)
-        m.clip_model.set_cls_tail(False)
+        set_tail(False)
         dt, _ = _timed(lambda: steps("fixed", a.steps), sync)
         no_gather.append(a.batch * a.steps / dt)
     # the host's cost of queueing one step, the GPU idle when it starts (inside the windows above the index
@@ -187,16 +197,17 @@ def model_leg(a, dtype_name):
         u, c = _summary(v["uncached"]), _summary(v["cached"])
         ratio = c["median"] / u["median"] if k.endswith("per_sec") else u["median"] / c["median"]
         rec[k] = {"uncached": u, "cached": c, "cached_speedup": round(ratio, 3)}
-        if a.cls_tail:
+        if len(tails) > 1:
             gain = {}
             for base in ("uncached", "cached"):
                 rec[k][base + "_tail"] = s = _summary(v[base + "_tail"])
                 b = rec[k][base]["median"]
                 gain[base] = round(s["median"] / b if k.endswith("per_sec") else b / s["median"], 4)
-            rec[k]["cls_tail_speedup"] = gain
-    if a.cls_tail:
-        rec["cls_tail_prediction_rel_diff"] = tail_diff
-        rec["cls_tail_prediction_bound"] = 1e-3 if dtype_name == "f32" else 3e-2
+            rec[k][tail_key + "_speedup"] = gain
+    if len(tails) > 1:
+        rec[tail_key + "_prediction_rel_diff"] = tail_diff
+        rec[tail_key + "_prediction_bound"] = 1e-3 if dtype_name == "f32" else 3e-2
+        rec["cls_tail_throughout"] = bool(a.eot_tail and a.cls_tail)
     rec["train_step_images_per_sec"]["cached_without_gather"] = _summary(no_gather)
     return rec
 
@@ -261,8 +272,10 @@ def driver(a):
                "--gather-rows", str(a.gather_rows), "--gather-calls", str(a.gather_calls), "--adapter", a.adapter]
         if a.cls_tail:
             cmd.append("--cls-tail")
+        if a.eot_tail:
+            cmd.append("--eot-tail")
         print("leg", leg, flush=True)
-        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if a.cls_tail else 1)).returncode  # TimeoutExpired ends the run
+        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if (a.cls_tail or a.eot_tail) else 1)).returncode  # TimeoutExpired ends the run
         if rc != 0:
             print(f"leg {leg} failed with exit code {rc}: stopping", flush=True)
             return rc
@@ -289,6 +302,9 @@ def main():
                     help="the adapter on the three out_proj layers: DoRA (config C3) or the reference's LoRA pair")
     ap.add_argument("--cls-tail", action="store_true",
                     help="also run every pass with the visual tower's class-token tail on, alternated with off")
+    ap.add_argument("--eot-tail", action="store_true",
+                    help="also run every pass with the text tower's EOT tail on, alternated with off (with --cls-tail: "
+                         "that tail on throughout)")
     a = ap.parse_args()
     if a.rounds < 3:
         ap.error("--rounds must be at least 3: the spread is part of the record")
@@ -296,7 +312,8 @@ def main():
         sys.exit(driver(a))
     rec = gather_leg(a) if a.leg == "gather" else model_leg(a, a.leg)
     os.makedirs(a.out, exist_ok=True)
-    tag = ("" if a.adapter == "dora" else f"_{a.adapter}") + ("_clstail" if a.cls_tail else "")
+    tag = (("" if a.adapter == "dora" else f"_{a.adapter}") + ("_eottail" if a.eot_tail else "")
+           + ("_clstail" if a.cls_tail else ""))
     name = "gather_blocks.json" if a.leg == "gather" else f"bench_clip_cached{tag}_{a.leg}.json"
     with open(os.path.join(a.out, name), "w") as fh:
         json.dump(rec, fh, indent=1)

@@ -18,7 +18,8 @@
 // B-operand (k-slot permutation pi), V^T comes from ds_read_b64_tr_b16.
 // f32 path (parity mode): scalar-FMA online softmax.
 // one-query path (attn_cls1_*, the CLIP visual tower's class-token tail): query row 0 of every image alone,
-// K / V straight from HBM to registers, no MFMA -- see the block in front of attn_cls1_fwd.
+// K / V straight from HBM to registers, no MFMA -- see the block in front of attn_cls1_fwd; attn_row1_fwd is the
+// same forward at a row per sequence, causal or not (the CLIP text tower's EOT tail).
 #include <initializer_list>
 
 #include "common.hpp"
@@ -2454,25 +2455,26 @@ __device__ __forceinline__ float c1_dot(const float* a, const float* b) {
   return s;
 }
 
-// s_j = scale * (q0 . k_j), lse = logsumexp_j s_j, o0 = sum_j softmax(s)_j v_j: an online softmax per lane group
-// over its keys, the groups merged in index order.  o_cls row b at b * ld_o (column h * 64), lse_cls[b * H + h].
+// The one-query forward of one (b, h), shared by attn_cls1_fwd (query row 0, all N keys) and attn_row1_fwd (a
+// query row per sequence, causal or not): s_j = scale * (q . k_j) over keys j < nk, lse = logsumexp_j s_j,
+// o = sum_j softmax(s)_j v_j -- an online softmax per lane group over its keys g, g + 32, ..., the groups merged
+// in index order.  seq: the sequence's row 0 at this head's column plus this lane's 8 dims; the query is row qr.
+// 1 <= nk: group 0 holds key 0, so the merged maximum is finite.  No row >= nk of K / V is read; the only stores
+// are the head's 64 columns at o_head and one float at lse_dst.
 template <typename T>
-__global__ __launch_bounds__(C1_THREADS) void attn_cls1_fwd(const T* __restrict__ qkv, int64_t ld_qkv, int D, int H,
-                                                            int N, float scale, T* __restrict__ o_cls, int64_t ld_o,
-                                                            float* __restrict__ lse_cls) {
+__device__ __forceinline__ void c1_fwd_body(const T* __restrict__ seq, int64_t ld_qkv, int D, int qr, int nk,
+                                            float scale, T* __restrict__ o_head, float* __restrict__ lse_dst) {
   __shared__ float gm[C1_GROUPS], gl[C1_GROUPS], gacc[C1_GROUPS][64];
-  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const int g = threadIdx.x >> 3, c = threadIdx.x & 7;
-  const T* base = qkv + (int64_t)b * N * ld_qkv + h * 64 + c * 8;
   float q[8], acc[8];
-  load8f<T>(base, q);
+  load8f<T>(seq + (int64_t)qr * ld_qkv, q);
 #pragma unroll
   for (int u = 0; u < 8; ++u) acc[u] = 0.f;
   float m = -INFINITY, l = 0.f;
-  for (int j = g; j < N; j += C1_GROUPS) {
+  for (int j = g; j < nk; j += C1_GROUPS) {
     float k[8], v[8];
-    load8f<T>(base + (int64_t)j * ld_qkv + D, k);
-    load8f<T>(base + (int64_t)j * ld_qkv + 2 * D, v);
+    load8f<T>(seq + (int64_t)j * ld_qkv + D, k);
+    load8f<T>(seq + (int64_t)j * ld_qkv + 2 * D, v);
     const float s = c1_dot(q, k) * scale;
     const float mn = fmaxf(m, s);
     const float corr = __expf(m - mn), p = __expf(s - mn);  // the group's first key: corr = exp(-inf) = 0
@@ -2486,7 +2488,7 @@ __global__ __launch_bounds__(C1_THREADS) void attn_cls1_fwd(const T* __restrict_
   for (int u = 0; u < 8; ++u) gacc[g][c * 8 + u] = acc[u];
   __syncthreads();
   if (threadIdx.x < 64) {
-    // group 0 holds key 0, so M is finite; a group without keys (N < 32) has m = -inf, l = 0 and weight 0
+    // group 0 holds key 0, so M is finite; a group without keys (nk < 32) has m = -inf, l = 0 and weight 0
     float M = gm[0];
     for (int i = 1; i < C1_GROUPS; ++i) M = fmaxf(M, gm[i]);
     float Lsum = 0.f, od = 0.f;
@@ -2495,9 +2497,36 @@ __global__ __launch_bounds__(C1_THREADS) void attn_cls1_fwd(const T* __restrict_
       Lsum = fmaf(gl[i], w, Lsum);
       od = fmaf(gacc[i][threadIdx.x], w, od);
     }
-    o_cls[(int64_t)b * ld_o + h * 64 + threadIdx.x] = (T)(od / Lsum);
-    if (threadIdx.x == 0) lse_cls[bh] = M + logf(Lsum);
+    o_head[threadIdx.x] = (T)(od / Lsum);
+    if (threadIdx.x == 0) *lse_dst = M + logf(Lsum);
   }
+}
+
+// Query row 0 of every image against all N keys.  o_cls row b at b * ld_o (column h * 64), lse_cls[b * H + h].
+template <typename T>
+__global__ __launch_bounds__(C1_THREADS) void attn_cls1_fwd(const T* __restrict__ qkv, int64_t ld_qkv, int D, int H,
+                                                            int N, float scale, T* __restrict__ o_cls, int64_t ld_o,
+                                                            float* __restrict__ lse_cls) {
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  c1_fwd_body<T>(qkv + (int64_t)b * N * ld_qkv + h * 64 + (threadIdx.x & 7) * 8, ld_qkv, D, 0, N, scale,
+                 o_cls + (int64_t)b * ld_o + h * 64, lse_cls + bh);
+}
+
+// Query row qrow[b] of sequence b (clamped to [0, N - 1]: the host never sees the values) against keys
+// 0 .. nk - 1, nk = qrow[b] + 1 under the causal mask and N without it (the CLIP text tower's EOT rows, DESIGN
+// §4.21).  o_row row b at b * ld_o (column h * 64), lse_row[b * H + h].  No backward: the caller takes this route
+// only where no attention backward follows.
+template <typename T>
+__global__ __launch_bounds__(C1_THREADS) void attn_row1_fwd(const T* __restrict__ qkv, int64_t ld_qkv, int D, int H,
+                                                            int N, const int64_t* __restrict__ qrow, int causal,
+                                                            float scale, T* __restrict__ o_row, int64_t ld_o,
+                                                            float* __restrict__ lse_row) {
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  int64_t r = qrow[b];
+  r = r < 0 ? 0 : (r > N - 1 ? N - 1 : r);
+  const int qr = (int)r;
+  c1_fwd_body<T>(qkv + (int64_t)b * N * ld_qkv + h * 64 + (threadIdx.x & 7) * 8, ld_qkv, D, qr, causal ? qr + 1 : N,
+                 scale, o_row + (int64_t)b * ld_o + h * 64, lse_row + bh);
 }
 
 // p_j = exp(s_j - lse), delta = dO0 . o0, ds_j = p_j (dO0 . v_j - delta); dk_j = scale ds_j q0 and dv_j = p_j dO0 for
@@ -2573,6 +2602,7 @@ __global__ __launch_bounds__(C1_THREADS) void attn_cls1_bwd(const T* __restrict_
   }
 }
 static int g_cls1_count = 0;
+static int g_row1_count = 0;
 
 // what both one-query entry points refuse before anything is queued: head_dim, N, row strides and addresses
 // that the 16-B loads and stores cannot take
@@ -2752,6 +2782,35 @@ int vit_sdpa_cls1_bwd(int dtype, int B, int H, int N, int head_dim, const void* 
 int vit_sdpa_cls1_count(int reset) {
   const int n = g_cls1_count;
   if (reset) g_cls1_count = 0;
+  return n;
+}
+
+// One-query forward at a row per sequence (attn_row1_fwd): query row qrow[b] (int64 on the device, clamped to
+// [0, N - 1] in the kernel) against keys 0 .. qrow[b] (causal != 0) or all N keys; bf16 or f32, any N up to 2048.
+// o_row [B, D] with row b at b * ld_o, lse_row [B * H] f32 (natural log).  qrow[b] = 0 without the mask is
+// vit_sdpa_cls1_fwd bit for bit.  Refusals as vit_sdpa_cls1_fwd, a null qrow among them.
+int vit_sdpa_row1_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, int64_t ld_qkv,
+                      const int64_t* qrow, int causal, void* o_row, int64_t ld_o, float* lse_row, float scale,
+                      void* stream) {
+  if (!cls1_args_ok(dtype, B, H, N, head_dim, {ld_qkv, ld_o}, {qkv, o_row}) || lse_row == nullptr ||
+      qrow == nullptr || ld_qkv < 3 * (int64_t)H * 64)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  const int D = H * 64;
+  if (dtype == VIT_BF16)
+    hipLaunchKernelGGL(attn_row1_fwd<bf16>, dim3(B * H), dim3(C1_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N,
+                       qrow, causal != 0, scale, (bf16*)o_row, ld_o, lse_row);
+  else
+    hipLaunchKernelGGL(attn_row1_fwd<float>, dim3(B * H), dim3(C1_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
+                       qrow, causal != 0, scale, (float*)o_row, ld_o, lse_row);
+  VIT_CHECK_LAUNCH();
+  ++g_row1_count;
+  return 0;
+}
+// Host-side count of attn_row1_fwd launches (reset != 0 zeroes it after reading).
+int vit_sdpa_row1_count(int reset) {
+  const int n = g_row1_count;
+  if (reset) g_row1_count = 0;
   return n;
 }
 

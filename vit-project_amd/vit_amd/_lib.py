@@ -72,6 +72,8 @@ SIGNATURES = {
     "vit_sdpa_cls1_fwd": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, vp],
     "vit_sdpa_cls1_bwd": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, f32, vp],
     "vit_sdpa_cls1_count": [i32],
+    "vit_sdpa_row1_fwd": [i32, i32, i32, i32, i32, vp, i64, vp, i32, vp, i64, vp, f32, vp],
+    "vit_sdpa_row1_count": [i32],
     "vit_sdpa_bwd_variant": [i32],
     "vit_sdpa_long_config": [i32],
     "vit_sdpa_long_count": [i32],

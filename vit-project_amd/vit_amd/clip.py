@@ -36,6 +36,8 @@ sweep; keeping their output is opt-in (``visual_prefix`` / ``forward(prefix=...)
 ``prefix_cache.VisualPrefixCache``).  ``ln_post`` reads the class rows alone; computing the visual
 tower's last block for those rows only (the class-token tail on one-query attention kernels) is opt-in too
 (``CLIP.set_cls_tail`` / ``CLIPHBA(cls_tail=True)``): it agrees with the dense block to rounding.
+``ln_final`` likewise reads one row per prompt, the EOT row; the text tower's last block on those rows alone is the
+EOT tail (``CLIP.set_eot_tail`` / ``CLIPHBA(eot_tail=True)``), opt-in in the same way.
 """
 from __future__ import annotations
 
@@ -274,6 +276,7 @@ class CLIP(nn.Module):
         self.attention_fp8_long = False
         self.attention_fp8_pre = False
         self.cls_tail = False  # set_cls_tail
+        self.eot_tail = False  # set_eot_tail
         self.initialize_parameters()
 
     @torch.no_grad()
@@ -338,6 +341,19 @@ class CLIP(nn.Module):
         rounding, not in bits.  fp8 attention passes and a last block whose ``in_proj_bias`` is trainable keep
         the dense block / the tail's dense attention."""
         self.cls_tail = bool(enable)
+
+    def set_eot_tail(self, enable: bool = True):
+        """Run the text tower's last block on the EOT rows alone: ``ln_final`` reads one row per
+        prompt, at ``text.argmax(-1)``, so proj, ln_2 and the MLP run for the S EOT rows and attention for the one
+        query at that position against the keys in front of it (vit_sdpa_row1_fwd, causal); ln_1 and the qkv GEMM
+        still run for all rows.  Off by default; the results agree with the dense block's to rounding, not in bits.
+
+        Only the last block is eligible, and only while nothing upstream of its out_proj needs a gradient
+        (``model.wants_row_tail``): the one-query route has no attention backward.  That is the reference
+        configuration (``apply_dora_to_ViT(..., n_transformer_layers=1)``, likewise LoRA) and every ``no_grad``
+        pass.  With two trainable text blocks the last one's input needs a gradient, and with a trainable ln_1 or
+        in_proj its own parameters do: the block then runs dense, as do fp8 attention passes."""
+        self.eot_tail = bool(enable)
 
     def _cfg(self, heads, causal, frozen=False):
         fp8 = self.attention_fp8 and (frozen or not torch.is_grad_enabled())
@@ -495,15 +511,28 @@ class CLIP(nn.Module):
         self._ensure_shadows()
         text = text.reshape(-1, text.shape[-1])
         x, k = self._text_prefix(text)
-        for blk in list(self.transformer.resblocks)[k:]:
-            x = run_block(x, blk.block_params(), self._cfg(blk.attn.num_heads, True))
+        S, Lq = text.shape
         c = getattr(self, "_idx_cache", {})
         key = ("eot", text.data_ptr(), text._version, tuple(text.shape))
         if key not in c:
-            S, Lq = text.shape
             c[key] = torch.arange(S, device=text.device) * Lq + text.argmax(dim=-1)
             self._idx_cache = c
-        return _PoolHeadFn.apply(x, c[key], self.ln_final.weight, self.ln_final.bias, self.text_projection, 1e-5)
+        idx = c[key]
+        blocks = list(self.transformer.resblocks)
+        for i in range(k, len(blocks)):
+            blk = blocks[i]
+            cfg = self._cfg(blk.attn.num_heads, True)
+            # the tower's last block, whose output ln_final reads at the EOT rows alone: the EOT tail
+            # (set_eot_tail; the block itself keeps the dense chain where its attention needs a backward)
+            if self.eot_tail and i == len(blocks) - 1:
+                pkey = ("eot_pos",) + key[1:]
+                if pkey not in c:
+                    c[pkey] = text.argmax(dim=-1)
+                cfg = dict(cfg, row_tail=c[pkey])
+            x = run_block(x, blk.block_params(), cfg)
+        if self.eot_tail and x.shape[1] == 1:  # the block took the tail: row s of [S, 1, W] is prompt s's EOT row
+            idx = self._cls_rows(S, 1, x.device)
+        return _PoolHeadFn.apply(x, idx, self.ln_final.weight, self.ln_final.bias, self.text_projection, 1e-5)
 
     def forward(self, image=None, text=None, pos_embedding=True, prefix=None):
         if text is None:
@@ -565,7 +594,7 @@ class CLIPHBA(nn.Module):
 
     def __init__(self, classnames, backbone_name="ViT-L/14", pos_embedding=False, clip_model=None,
                  tokenized_prompts=None, compute_dtype=torch.float32, attention_fp8=False,
-                 attention_fp8_long=False, cls_tail=False, attention_fp8_prequant=False):
+                 attention_fp8_long=False, cls_tail=False, attention_fp8_prequant=False, eot_tail=False):
         super().__init__()
         self.num_clip = len(classnames)
         if clip_model is None:
@@ -580,6 +609,8 @@ class CLIPHBA(nn.Module):
                                               prequantize=attention_fp8_prequant)
         if cls_tail:  # the visual tower's last block on the class rows alone (CLIP.set_cls_tail)
             self.clip_model.set_cls_tail(True)
+        if eot_tail:  # the text tower's last block on the EOT rows alone (CLIP.set_eot_tail)
+            self.clip_model.set_eot_tail(True)
         self.pos_embedding = pos_embedding
         for p in self.clip_model.parameters():
             p.requires_grad = False

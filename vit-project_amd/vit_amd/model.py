@@ -269,7 +269,7 @@ class _PatchEmbedFn(torch.autograd.Function):
         return None, dw, db, dcls, dpos, None
 
 
-def _block_chain(x, params, cfg, fwd_only, attn1=False):
+def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
     """The launch chain of one block's forward, shared by the autograd node (_BlockFn.forward) and the
     forward-only path (block_forward_only).  Returns (xo [B, N, D], the tensors a backward would need,
     the GEMM weight operands).  ``fwd_only``: fc1 runs the act-only epilogue and no act'(pre) tensor
@@ -283,7 +283,13 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False):
     schedule is the same: each chain carries its images' class rows.
 
     ``attn1`` (wants_cls_attn1; the CLIP visual tower's tail): the tail's attention is the one-query
-    kernel -- o is then the compact [B, D] tensor and lse [B * H]; the dense ones are not allocated."""
+    kernel -- o is then the compact [B, D] tensor and lse [B * H]; the dense ones are not allocated.
+
+    ``row_tail`` (wants_row_tail; the CLIP text tower's last block): an int64 [B] device tensor of
+    positions, one live row per sequence.  norm1 and qkv run for all rows, attention for the query at that row
+    alone (sdpa_row1_fwd under the block's causal flag, compact o and lse), and everything behind it for the B
+    live rows as in the class-token tail, the residual rows gathered by index instead of read by stride.  xo is
+    [B, 1, D].  Only for a block upstream of whose proj nothing needs a gradient: there is no attention backward."""
     n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
     B, N, D = x.shape
     H, T, eps = cfg["heads"], cfg["dtype"], cfg["eps"]
@@ -296,7 +302,10 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False):
     x2 = x.reshape(M, D)
     F = fc1w.shape[0]
     f32 = torch.float32
-    ct = bool(cfg.get("cls_tail"))
+    rt = row_tail is not None
+    assert not (rt and cfg.get("cls_tail")), "a block runs the class-token tail or the row tail, not both"
+    ct = bool(cfg.get("cls_tail")) or rt
+    attn1 = attn1 or rt
     Mt = B if ct else M  # rows of everything downstream of attention
     h1, h2 = torch.empty(M, D, dtype=T, device=dev), torch.empty(Mt, D, dtype=T, device=dev)
     m1, r1 = (torch.empty(M, dtype=f32, device=dev) for _ in range(2))
@@ -328,8 +337,12 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False):
     if rs is not None:
         pb, yb = torch.empty(Mt, D, dtype=T, device=dev), torch.empty(Mt, D, dtype=T, device=dev)
     # class-token tail: the class rows of the residual stream and of the attention output, by stride
-    x_cls = o_cls = xc = None
-    if ct:
+    x_cls = o_cls = xc = rt_flat = None
+    if rt:  # the live rows of the residual stream, gathered into a compact tensor by their flat row index
+        rt_flat = _row_tail_flat(row_tail, B, N)
+        x_cls = xc = torch.empty(B, D, dtype=f32, device=dev)
+        o_cls = o
+    elif ct:
         x_cls, o_cls = x2.view(B, N * D)[:, :D], o if attn1 else o.view(B, N * D)[:, :D]
         if rs is None:  # the EPI_RESID epilogue reads its residual at the output's row stride: compact copy
             xc = torch.empty(B, D, dtype=f32, device=dev)
@@ -371,7 +384,13 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False):
             ln1(sl),
             lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
         ]
-        if attn1:  # query 0 alone, into the compact o
+        if rt:  # the query at each sequence's live row alone, into the compact o; then that row of the stream
+            steps += [
+                lambda: ops.sdpa_row1_fwd(qkv[sl], row_tail[cs], b1 - b0, H, N, causal=causal, o=o[cs],
+                                          lse=lse[b0 * H:b1 * H]),
+                lambda: ops.gather_rows(x2, rt_flat[cs], out=xc[cs]),
+            ]
+        elif attn1:  # query 0 alone, into the compact o
             steps.append(lambda: ops.sdpa_cls1_fwd(qkv[sl], b1 - b0, H, N, o=o[cs], lse=lse[b0 * H:b1 * H]))
         else:
             # (only query 0 of each head is read: the query-limited forward; the tail is never causal or fp8)
@@ -386,8 +405,9 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False):
                 lambda: ops.add_layer_norm_fwd(xm[cs], yb[cs], xo[cs]),
             ]
         else:
+            if not rt:
+                steps.append(lambda: ops.pad_cols(x_cls[cs], D, out=xc[cs]))
             steps += [
-                lambda: ops.pad_cols(x_cls[cs], D, out=xc[cs]),
                 lambda: ops.linear_fwd(o_cls[cs], Wproj, projb.detach(), epi=L.EPI_RESID, resid=xc[cs], out=xm[cs]),
                 lambda: ops.layer_norm_fwd(xm[cs], n2w.detach(), n2b.detach(), eps, T, out=h2[cs], mean=m2[cs],
                                            rstd=r2[cs]),
@@ -450,7 +470,7 @@ def block_forward_only(x, params, cfg):
     12 tensors of ``block_params()``; returns the block output [B, N, D] (f32), bit for bit the
     training chain's."""
     with torch.no_grad():
-        return _block_chain(x, tuple(params), cfg, True, _cfg_attn1(cfg, False))[0]
+        return _block_chain(x, tuple(params), cfg, True, _cfg_attn1(cfg, False), _cfg_row_tail(cfg, False))[0]
 
 
 def forward_only_enabled() -> bool:
@@ -516,6 +536,37 @@ def _cfg_attn1(cfg, qkv_bias_needs_grad: bool) -> bool:
                            bool(cfg.get("attn_fp8", False)), bool(qkv_bias_needs_grad))
 
 
+def wants_row_tail(requested: bool, attn_fp8: bool = False, upstream_needs_grad: bool = False) -> bool:
+    """The routing rule of the row tail (cfg "row_tail": the CLIP text tower's last block), as a
+    pure function: the cfg asks for it, the block's attention is not fp8, and nothing upstream of proj -- the block
+    input, norm1, the qkv weight and bias -- needs a gradient, so that no attention backward can follow the
+    one-query forward.  The forward-only chain qualifies; any other block runs the dense chain."""
+    return bool(requested) and not attn_fp8 and not upstream_needs_grad
+
+
+def _cfg_row_tail(cfg, upstream_needs_grad: bool):
+    """The cfg's "row_tail" positions if the block takes the row tail, else None."""
+    rows = cfg.get("row_tail")
+    ok = wants_row_tail(rows is not None, bool(cfg.get("attn_fp8", False)), bool(upstream_needs_grad))
+    return rows if ok else None
+
+
+_ROW_TAIL_FLAT = [None]
+
+
+def _row_tail_flat(rows: torch.Tensor, B: int, N: int) -> torch.Tensor:
+    """Flat row indices b * N + clamp(rows[b], 0, N - 1) into the [B * N, D] stream for vit_gather_rows (which
+    takes its indices as given), kept while the same positions tensor comes back: the prompts do not change."""
+    if rows.dtype != torch.int64 or tuple(rows.shape) != (B,):
+        raise ValueError(f"row_tail must be an int64 [{B}] tensor of positions, got {rows.dtype} {tuple(rows.shape)}")
+    key = (rows.data_ptr(), rows._version, B, N, rows.device)
+    hit = _ROW_TAIL_FLAT[0]
+    if hit is None or hit[0] != key:
+        flat = torch.arange(B, dtype=torch.int64, device=rows.device) * N + rows.clamp(0, N - 1)
+        hit = _ROW_TAIL_FLAT[0] = (key, flat, rows)  # (rows is held so that its address is not reused)
+    return hit[1]
+
+
 def wants_forward_only(enabled: bool, grad_enabled: bool, input_requires_grad: bool,
                        any_param_requires_grad: bool) -> bool:
     """The routing rule, as a pure function: a block takes the forward-only chain when the switch is on
@@ -546,7 +597,8 @@ class _BlockFn(torch.autograd.Function):
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b, cfg):
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b)
         attn1 = _cfg_attn1(cfg, ctx.needs_input_grad[4])
-        xo, saved, wops = _block_chain(x, params, cfg, False, attn1)
+        row_tail = _cfg_row_tail(cfg, any(ctx.needs_input_grad[0:5]))
+        xo, saved, wops = _block_chain(x, params, cfg, False, attn1, row_tail)
         B, N, D = x.shape
         H, T = cfg["heads"], cfg["dtype"]
         causal = bool(cfg.get("causal", False))
@@ -557,8 +609,10 @@ class _BlockFn(torch.autograd.Function):
         ctx.meta = (B, N, D, H, T, cfg.get("compact_np", 0), cfg["quick_gelu"], causal)
         ctx.defer_bwd = bool(cfg.get("defer_bwd_join"))
         ctx.attn_fp8 = attn_fp8
-        ctx.cls_tail = bool(cfg.get("cls_tail"))
-        ctx.cls_attn1 = attn1
+        # (the row tail's backward is the class-token tail's on one-query attention: compact o, the live row first)
+        ctx.row_tail = row_tail is not None
+        ctx.cls_tail = bool(cfg.get("cls_tail")) or ctx.row_tail
+        ctx.cls_attn1 = attn1 or ctx.row_tail
         ctx.grad_hook = cfg.get("grad_hook")
         ctx.flat_span = cfg.get("flat_span")
         return xo
@@ -610,6 +664,9 @@ class _BlockFn(torch.autograd.Function):
         need_mlp_in = any(ng[0:11])     # anything upstream of fc2 (its input gradient path)
         need_attn = any(ng[0:5])        # anything upstream of proj
         need_h1 = any(ng[0:3])
+        # the row tail is taken only where nothing upstream of proj needs a gradient (wants_row_tail): no attention
+        # backward, no res_every LayerNorm backward, no scatter of the live rows
+        assert not (ctx.row_tail and need_attn), "row tail: a gradient upstream of proj was asked for"
         if need_attn and ctx.attn_fp8:
             raise RuntimeError("this block's attention ran in fp8 (forward only); its backward needs the bf16 "
                                "forward: enable fp8 attention only for frozen blocks / no-grad passes")

@@ -602,6 +602,25 @@ def sdpa_cls1_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None):
     return o, lse
 
 
+def sdpa_row1_fwd(qkv2d, qrow, B, H, N, causal=False, o=None, scale=None, lse=None):
+    """One-query attention forward at a row per sequence (vit_sdpa_row1_fwd): query row ``qrow[b]`` (int64 [B] on
+    the device, clamped to [0, N - 1] by the kernel) against keys ``0 .. qrow[b]`` (``causal``) or all N; bf16 or
+    f32, N up to 2048.  Returns (o [B, D] in the qkv dtype, lse [B * H] f32); ``o`` may be any [B, D] view with
+    16-byte-aligned rows.  ``qrow = 0`` without the mask is :func:`sdpa_cls1_fwd` bit for bit; against sdpa_fwd's
+    row ``qrow[b]`` it agrees to rounding.  Forward only: there is no matching backward."""
+    D = H * 64
+    if o is None:
+        o = torch.empty(B, D, dtype=qkv2d.dtype, device=qkv2d.device)
+    if lse is None:
+        lse = torch.empty(B * H, dtype=torch.float32, device=qkv2d.device)
+    assert o.shape == (B, D) and o.stride(1) == 1 and o.dtype == qkv2d.dtype and lse.numel() == B * H
+    assert qrow.dtype == torch.int64 and qrow.shape == (B,) and qrow.stride(0) == 1 and qrow.device == qkv2d.device
+    scale = 64 ** -0.5 if scale is None else scale
+    call("vit_sdpa_row1_fwd", L.dt(qkv2d), B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(qrow), int(bool(causal)),
+         ptr(o), o.stride(0), ptr(lse), float(scale), _s(qkv2d))
+    return o, lse
+
+
 def sdpa_cls1_bwd(qkv2d, o, do, lse, B, H, N, dqkv=None, scale=None):
     """One-query attention backward (vit_sdpa_cls1_bwd) from the class rows' dO: ``o`` / ``do`` [B, D] (any row
     stride), ``lse`` [B * H] of sdpa_cls1_fwd.  Writes every element of dqkv [B*N, 3D] (dq rows 1 .. N-1 of each

@@ -99,6 +99,21 @@ int vit_gemm_g4_gelu(int on);
  * 32 registered streams a new stream keeps the plain launch. */
 int vit_gemm_streamk_workspace(void* stream, float* part, int64_t part_bytes, int* counters, int ncounters);
 
+/* fp32 GEMM arithmetic on the MFMA path (clip_model.float(), NEWP:274; compute_dtype float32):
+ * 0 = v_mfma_f32_16x16x4_f32, exact f32 products (default); 1 = each operand as hi + lo bf16
+ * (hi = bf16_rne(x), lo = bf16_rne(x - hi)), three bf16 MFMA products (hi*lo, lo*hi, hi*hi), f32
+ * accumulate: held to |C - C64| <= (3 * 2^-18 + (R + 3) * 2^-24) |P| |Q|^T on random normal-range data (4.4e-6
+ * rms relative error; every rounding at its limit at once would be 3 * 2^-16), exact where both operands are
+ * bf16 values; -1 keeps.  Returns the previous setting (default VIT_F32_MATMUL = highest |
+ * high, else 0).  The setting is "at most bf16x3": f32 GEMMs that do not take the MFMA path (under 64
+ * output tiles, misaligned operands, allow_fast = 0) run the generic kernel and are exact f32 in either
+ * mode.  Non-finite in, non-finite out: an infinite (or past-bf16-range) operand gives NaN in mode 1 where
+ * mode 0 gives +-inf.  Process-wide, read at launch time.  Additive to ABI 10.  Host-only, no GPU call. */
+int vit_gemm_f32_precision(int mode);
+/* Host-side launch counts since the last reset: every launch of the f32 MFMA path / those in mode 1. */
+int vit_gemm_f32_count(int reset);
+int vit_gemm_f32_split_count(int reset);
+
 /* Host-only query (no GPU call): rows per launch the bf16 MFMA path uses for a row-contiguous
  * operand of M rows x ld elements (its staging offsets are 32-bit: larger operands are split
  * into row chunks, a multiple of 256 rows each); M when one launch fits, 0 if none does. */

@@ -83,10 +83,13 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds, which="cls",
     opt = vit_amd.FusedAdamW([p for p in m.parameters() if p.requires_grad], lr=3e-4)
     x = torch.randn(batch, 3, 224, 224, device=dev)
     y = torch.randn(batch, 66, device=dev) * 0.5 + 1.0
-    switch = m.clip_model.set_cls_tail if which == "cls" else m.clip_model.set_eot_tail
-    if which == "eot":
+    if which == "f32":  # the fp32 GEMM mode ("high" = bf16x3) off and on, the class-token tail as cls_fixed says
+        switch = lambda on: vit_amd.set_float32_matmul_precision("high" if on else "highest")
+    else:
+        switch = m.clip_model.set_cls_tail if which == "cls" else m.clip_model.set_eot_tail
+    if which in ("eot", "f32"):
         m.clip_model.set_cls_tail(cls_fixed)
-    key = which + "_tail"
+    key = "f32_high" if which == "f32" else which + "_tail"
 
     def window(n):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -124,8 +127,10 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds, which="cls",
     return {"ms_per_step": {key + "_off": off, key + "_on": on}, key + "_speedup": round(off["median"] / on["median"], 4),
             "images_per_sec": {key + "_off": round(batch / off["median"] * 1e3, 2),
                                key + "_on": round(batch / on["median"] * 1e3, 2)},
-            "cls_tail_throughout": bool(which == "eot" and cls_fixed),
+            "cls_tail_throughout": bool(which in ("eot", "f32") and cls_fixed),
             "prediction_rel_diff_on_vs_off": float((preds[True] - preds[False]).abs().max() / preds[False].abs().max()),
+            "prediction_rms_rel_diff_on_vs_off": float(((preds[True] - preds[False]).pow(2).mean()
+                                                        / preds[False].pow(2).mean()).sqrt()),
             "prediction_bound": 1e-3 if dtype == "f32" else 3e-2,
             "batch": batch, "steps": steps, "warmup": warmup, "rounds": rounds, "dtype": dtype}
 
@@ -144,18 +149,27 @@ def main():
                     help="alternate the text tower's EOT tail off and on in one process (with --cls-tail: that tail on "
                          "throughout)")
     ap.add_argument("--rounds", type=int, default=3, help="rounds of the --cls-tail / --eot-tail alternation (>= 3)")
+    ap.add_argument("--f32-matmul", choices=["highest", "high"], default=None,
+                    help="fp32 GEMM arithmetic of the whole run (vit_amd.set_float32_matmul_precision; high = bf16x3)")
+    ap.add_argument("--f32-ab", action="store_true",
+                    help="alternate --f32-matmul highest and high in one process (with --cls-tail: that tail on throughout)")
     a = ap.parse_args()
     import torch
-    if a.cls_tail or a.eot_tail:
+    if a.f32_matmul:
+        import vit_amd
+        vit_amd.set_float32_matmul_precision(a.f32_matmul)
+    if a.cls_tail or a.eot_tail or a.f32_ab:
         if a.rounds < 3:
             ap.error("--rounds must be at least 3: the spread is part of the record")
         r = cls_tail_leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup, a.adapter, a.rounds,
-                         "eot" if a.eot_tail else "cls", a.cls_tail)
+                         "f32" if a.f32_ab else "eot" if a.eot_tail else "cls", a.cls_tail)
     else:
         leg = bench.c3_leg if a.adapter == "dora" else lora_leg
         r = leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup)
     r["metric"] = f"images/sec CLIP-HBA ViT-L/14 + {'DoRA' if a.adapter == 'dora' else 'LoRA'} train step (config C3)"
     r["adapter"] = a.adapter
+    if a.f32_matmul:
+        r["f32_matmul"] = a.f32_matmul
     print(json.dumps(r))
 
 

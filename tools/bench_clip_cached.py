@@ -29,6 +29,11 @@ difference of a batch's predictions; the records are named ``bench_clip_cached_c
 series and ``eot_tail_speedup`` are then that switch's; given together with ``--cls-tail`` the class-token tail
 stays on throughout and the EOT tail alone alternates.  Records: ``bench_clip_cached_eottail[_clstail]_{dtype}.json``.
 
+``--f32-matmul highest|high`` sets the fp32 GEMM arithmetic of the whole run (``vit_amd.set_float32_matmul_precision``;
+``high`` = bf16x3).  ``--f32-ab`` alternates the two instead, as the tails are alternated (the
+``*_tail`` series are then the ``high`` passes, on prefix caches built in ``high``; ``--cls-tail`` keeps that tail
+on throughout): ``f32_high_speedup``, records ``bench_clip_cached_f32high[_clstail]_{dtype}.json``.
+
 ``--adapter lora`` puts the reference's LoRA pair (NEWP:339-404) where DoRA stands; its records are named
 ``bench_clip_cached_lora_{dtype}.json``.
 """
@@ -101,12 +106,22 @@ def model_leg(a, dtype_name):
         pred_diff = float((pc - pu).abs().max() / pu.abs().max())
 
     fixed = caches["train"].take(torch.arange(a.batch))
-    tails = (False, True) if (a.cls_tail or a.eot_tail) else (False,)
+    tails = (False, True) if (a.cls_tail or a.eot_tail or a.f32_ab) else (False,)
     # the switch that alternates: the EOT tail if asked for (the class-token tail then stays as --cls-tail says)
     set_tail = m.clip_model.set_eot_tail if a.eot_tail else m.clip_model.set_cls_tail
     tail_key = "eot_tail" if a.eot_tail else "cls_tail"
-    if a.eot_tail:
+    if a.eot_tail or a.f32_ab:
         m.clip_model.set_cls_tail(a.cls_tail)
+    if a.f32_ab:  # the fp32 GEMM mode alternates; each mode reads the prefix caches built in it
+        vit_amd.set_float32_matmul_precision("high")
+        by_mode = {False: caches, True: S.prefix_caches_for(m, data, None, a.batch)}
+        vit_amd.set_float32_matmul_precision("highest")
+        tail_key = "f32_high"
+
+        def set_tail(on):
+            nonlocal caches
+            vit_amd.set_float32_matmul_precision("high" if on else "highest")
+            caches = by_mode[on]
     vname = lambda c, t: ("cached" if c else "uncached") + ("_tail" if t else "")
     tail_diff = None
     if len(tails) > 1:  # the same batch's predictions with the tail on against off (cached pass)
@@ -207,7 +222,7 @@ def model_leg(a, dtype_name):
     if len(tails) > 1:
         rec[tail_key + "_prediction_rel_diff"] = tail_diff
         rec[tail_key + "_prediction_bound"] = 1e-3 if dtype_name == "f32" else 3e-2
-        rec["cls_tail_throughout"] = bool(a.eot_tail and a.cls_tail)
+        rec["cls_tail_throughout"] = bool((a.eot_tail or a.f32_ab) and a.cls_tail)
     rec["train_step_images_per_sec"]["cached_without_gather"] = _summary(no_gather)
     return rec
 
@@ -274,8 +289,12 @@ def driver(a):
             cmd.append("--cls-tail")
         if a.eot_tail:
             cmd.append("--eot-tail")
+        if a.f32_ab:
+            cmd.append("--f32-ab")
+        if a.f32_matmul:
+            cmd += ["--f32-matmul", a.f32_matmul]
         print("leg", leg, flush=True)
-        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if (a.cls_tail or a.eot_tail) else 1)).returncode  # TimeoutExpired ends the run
+        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if (a.cls_tail or a.eot_tail or a.f32_ab) else 1)).returncode  # TimeoutExpired ends the run
         if rc != 0:
             print(f"leg {leg} failed with exit code {rc}: stopping", flush=True)
             return rc
@@ -305,15 +324,24 @@ def main():
     ap.add_argument("--eot-tail", action="store_true",
                     help="also run every pass with the text tower's EOT tail on, alternated with off (with --cls-tail: "
                          "that tail on throughout)")
+    ap.add_argument("--f32-matmul", choices=["highest", "high"], default=None,
+                    help="fp32 GEMM arithmetic of the whole run (high = bf16x3)")
+    ap.add_argument("--f32-ab", action="store_true",
+                    help="alternate the fp32 GEMM modes highest and high (with --cls-tail: that tail on throughout)")
     a = ap.parse_args()
     if a.rounds < 3:
         ap.error("--rounds must be at least 3: the spread is part of the record")
+    if a.f32_ab and (a.eot_tail or a.f32_matmul):
+        ap.error("--f32-ab alternates the fp32 GEMM mode alone")
     if a.leg is None:
         sys.exit(driver(a))
+    if a.f32_matmul:
+        import vit_amd
+        vit_amd.set_float32_matmul_precision(a.f32_matmul)
     rec = gather_leg(a) if a.leg == "gather" else model_leg(a, a.leg)
     os.makedirs(a.out, exist_ok=True)
     tag = (("" if a.adapter == "dora" else f"_{a.adapter}") + ("_eottail" if a.eot_tail else "")
-           + ("_clstail" if a.cls_tail else ""))
+           + ("_f32high" if (a.f32_ab or a.f32_matmul == "high") else "") + ("_clstail" if a.cls_tail else ""))
     name = "gather_blocks.json" if a.leg == "gather" else f"bench_clip_cached{tag}_{a.leg}.json"
     with open(os.path.join(a.out, name), "w") as fh:
         json.dump(rec, fh, indent=1)

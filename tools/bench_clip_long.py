@@ -4,6 +4,10 @@ tokens on the streamed f32 kernels against the generic ones (vit_sdpa_long_confi
 --rounds rounds in one process.  Prints one JSON line: the median images/s of each variant and their ratio.
 
     python tools/bench_clip_long.py [--batch 16] [--steps 5] [--warmup 2] [--rounds 3] [--steps-generic 2]
+                                    [--f32-matmul highest|high] [--f32-ab]
+
+``--f32-matmul`` sets the fp32 GEMM arithmetic of the run (``high`` = bf16x3); ``--f32-ab``
+alternates ``highest`` and ``high`` instead, both on the streamed attention kernels.
 """
 import argparse
 import json
@@ -30,7 +34,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--prompts", type=int, default=66)
+    ap.add_argument("--f32-matmul", choices=["highest", "high"], default=None)
+    ap.add_argument("--f32-ab", action="store_true")
     a = ap.parse_args()
+    if a.f32_matmul:
+        vit_amd.set_float32_matmul_precision(a.f32_matmul)
     dev = torch.device("cuda", 0)
     lib = L.lib()
     torch.manual_seed(0)
@@ -64,6 +72,22 @@ def main():
         assert torch.isfinite(loss)
         return a.batch * steps / dt, lib.vit_sdpa_long_f32_count(0) - c0
 
+    if a.f32_ab:
+        ips = {"highest": [], "high": []}
+        try:
+            for rnd in range(a.rounds):
+                for name in ips:
+                    vit_amd.set_float32_matmul_precision(name)
+                    ips[name].append(round(run(1, a.steps, a.warmup if rnd == 0 else 1)[0], 2))
+        finally:
+            lib.vit_sdpa_long_config(-1)
+            vit_amd.set_float32_matmul_precision("highest")
+        med = {k: statistics.median(v) for k, v in ips.items()}
+        print(json.dumps({"metric": "images/sec CLIP-HBA ViT-L/14@336px + DoRA fp32 train step", "batch": a.batch,
+                          "steps": a.steps, "rounds": a.rounds, "images_per_sec": ips, "median": med,
+                          "spread": {k: round((max(v) - min(v)) / med[k], 4) for k, v in ips.items()},
+                          "high_over_highest": round(med["high"] / med["highest"], 3)}), flush=True)
+        return
     ips = {"streamed": [], "generic": []}
     try:
         for rnd in range(a.rounds):

@@ -1,7 +1,12 @@
 """fp32 MFMA GEMM timing at config C3's shapes (CLIP ViT-L/14 visual tower, B=64: M = 64 x 257 rows),
 with and without the stream's stream-K workspace (f32m::gemm_sk_kernel vs one tile per workgroup).
 
-    python tools/bench_f32.py [--batch 64] [--reps 20] [--json out.jsonl]
+    python tools/bench_f32.py [--batch 64] [--reps 20] [--precision highest|high] [--pairs N] [--json out.jsonl]
+
+``--precision`` sets the fp32 GEMM arithmetic (vit_amd.set_float32_matmul_precision; "high" = bf16x3, DESIGN
+§4.22).  ``--pairs N`` times every case N times in "highest" and "high", alternating, in this one process, and
+prints per case the median of each, their ratio and the spread (max - min over median) of each side.  TFLOP/s
+count 2 M N R in both modes.  ``sum`` is a float64 checksum of the case's output (to compare two builds).
 """
 import argparse
 import json
@@ -36,7 +41,10 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--json", default="")
+    ap.add_argument("--precision", choices=["highest", "high"], default="highest")
+    ap.add_argument("--pairs", type=int, default=0)
     a = ap.parse_args()
+    ops.set_float32_matmul_precision(a.precision)
     dev = torch.device("cuda", 0)
     M, D = a.batch * 257, 1024
     g = torch.Generator(device=dev).manual_seed(0)
@@ -60,8 +68,30 @@ def main():
     }
     st = L.stream_ptr(dev)
     out = []
+    if a.pairs:
+        ops._SK.pop(st, None)
+        ops._streamk(dev)
+        for name, (fn, flop) in cases.items():
+            t = {"highest": [], "high": []}
+            for _ in range(a.pairs):
+                for mode in ("highest", "high"):
+                    ops.set_float32_matmul_precision(mode)
+                    t[mode].append(timeit(fn, a.reps))
+            ops.set_float32_matmul_precision("highest")
+            med = {m: sorted(v)[len(v) // 2] for m, v in t.items()}
+            row = {"case": name, "M": M, "gflop": round(flop / 1e9, 2), "pairs": a.pairs}
+            for m in t:
+                row[m + "_us"] = round(med[m] * 1e6, 1)
+                row[m + "_tf"] = round(flop / med[m] / 1e12, 1)
+                row[m + "_spread"] = round((max(t[m]) - min(t[m])) / med[m], 4)
+            row["speedup"] = round(med["highest"] / med["high"], 3)
+            print(json.dumps(row), flush=True)
+            out.append(row)
+        cases = {}
     for name, (fn, flop) in cases.items():
-        row = {"case": name, "M": M, "gflop": round(flop / 1e9, 2)}
+        row = {"case": name, "M": M, "gflop": round(flop / 1e9, 2), "precision": a.precision}
+        r = fn()
+        row["sum"] = float((r[0] if isinstance(r, tuple) else r).double().sum())
         for mode in ("plain", "streamk"):
             if mode == "plain":  # unregistered, and marked registered so the ops do not register it
                 L.lib().vit_gemm_streamk_workspace(st, None, 0, None, 0)

@@ -1324,17 +1324,29 @@ static double ragged_waste(int64_t tiles, int slots) {
   return 1.0 - (double)tiles / (double)(rounds * slots);
 }
 
-template <int PL, int QL, int EPI, typename TO>
-static int launch_f32(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
-                      const Epi& e, hipStream_t s) {
+// fp32 arithmetic of the f32 MFMA path (vit_gemm_f32_precision): 0 = v_mfma_f32_16x16x4_f32, 1 = bf16x3
+// (f32m SPLIT = 1).  Process-wide, read at launch time; the initial value comes from VIT_F32_MATMUL
+// (highest | high), so spawned workers inherit it.  Host-side launch counts for tests and tools.
+static int f32_precision_env() {
+  const char* s = getenv("VIT_F32_MATMUL");
+  return s && strcmp(s, "high") == 0 ? 1 : 0;
+}
+static int g_f32_split = f32_precision_env();
+static int g_f32_count = 0, g_f32_split_count = 0;
+
+template <int PL, int QL, int EPI, typename TO, int SPLIT>
+static int launch_f32_mode(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
+                           const Epi& e, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)f32m::gemm_kernel<PL, QL, EPI, TO, float>,
+    (void)hipFuncSetAttribute((const void*)f32m::gemm_kernel<PL, QL, EPI, TO, float, SPLIT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, f32m::LDS);
-    (void)hipFuncSetAttribute((const void*)f32m::gemm_sk_kernel<PL, QL, EPI, TO, float>,
+    (void)hipFuncSetAttribute((const void*)f32m::gemm_sk_kernel<PL, QL, EPI, TO, float, SPLIT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, f32m::LDS + 16);
     attr = true;
   }
+  ++g_f32_count;
+  g_f32_split_count += SPLIT;
   const int64_t tiles = (int64_t)((M + f32m::BM - 1) / f32m::BM) * ((N + f32m::BN - 1) / f32m::BN);
   const int G = 2 * num_cus();  // two workgroups per CU
   if (split <= 1 && R % f32m::BK == 0 && tiles >= G && ragged_waste(tiles, G) > 0.03) {
@@ -1344,7 +1356,7 @@ static int launch_f32(const void* P, int64_t ldp, const void* Q, int64_t ldq, in
       // tile by k-steps from the start was 2-7 % slower on the tall forwards, round 3; that form and the
       // VIT_GEMM_STREAMK A/B switch were removed in round 5)
       const int dp_rounds = (int)(tiles / G) - 1;
-      hipLaunchKernelGGL((f32m::gemm_sk_kernel<PL, QL, EPI, TO, float>), dim3(G), dim3(f32m::THREADS),
+      hipLaunchKernelGGL((f32m::gemm_sk_kernel<PL, QL, EPI, TO, float, SPLIT>), dim3(G), dim3(f32m::THREADS),
                          f32m::LDS + 16, s, (const float*)P, ldp, (const float*)Q, ldq, M, N, R, dp_rounds, e,
                          w->part, w->cnt);
       VIT_CHECK_LAUNCH();
@@ -1354,10 +1366,19 @@ static int launch_f32(const void* P, int64_t ldp, const void* Q, int64_t ldq, in
   const int r_chunk = r_chunk_for(R, split, f32m::BK);
   const int nz = (R + r_chunk - 1) / r_chunk;
   dim3 grid(((M + f32m::BM - 1) / f32m::BM) * ((N + f32m::BN - 1) / f32m::BN) * nz);
-  hipLaunchKernelGGL((f32m::gemm_kernel<PL, QL, EPI, TO, float>), grid, dim3(f32m::THREADS), f32m::LDS, s,
+  hipLaunchKernelGGL((f32m::gemm_kernel<PL, QL, EPI, TO, float, SPLIT>), grid, dim3(f32m::THREADS), f32m::LDS, s,
                      (const float*)P, ldp, (const float*)Q, ldq, M, N, R, r_chunk, e);
   VIT_CHECK_LAUNCH();
   return 0;
+}
+
+// the one place every f32 MFMA-path GEMM goes through: forward (every epilogue), input and weight gradient,
+// split-K partials and their accumulate tails, the padded patch embedding, the stream-K form
+template <int PL, int QL, int EPI, typename TO>
+static int launch_f32(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
+                      const Epi& e, hipStream_t s) {
+  if (g_f32_split) return launch_f32_mode<PL, QL, EPI, TO, 1>(P, ldp, Q, ldq, M, N, R, split, e, s);
+  return launch_f32_mode<PL, QL, EPI, TO, 0>(P, ldp, Q, ldq, M, N, R, split, e, s);
 }
 
 template <typename T, int EPI, typename TO, typename TA>
@@ -1514,6 +1535,19 @@ int vit_gemm_group(int fwd, int dgrad) { g_group[0] = fwd; g_group[1] = dgrad; r
 
 // Tuning hook: force GEMM configuration big::V<v> (-1 restores the per-shape heuristic).
 int vit_gemm_variant(int v) { g_variant = v; g_dbg = v >= 100 ? v / 100 : 0; return 0; }
+
+// fp32 GEMM arithmetic on the MFMA path: 0 = exact f32 products (default), 1 = bf16x3 (gemm_f32.inc,
+// SPLIT = 1), -1 keeps; returns the previous setting.  GEMMs that do not take that path (under 64 tiles,
+// misaligned operands, allow_fast = 0) run the generic kernel and are exact f32 in either mode: the
+// setting is "at most bf16x3".  Host-only, no GPU call.
+int vit_gemm_f32_precision(int mode) {
+  const int prev = g_f32_split;
+  if (mode == 0 || mode == 1) g_f32_split = mode;
+  return prev;
+}
+// Host-side launch counts since the last reset: every launch of the f32 MFMA path / those in mode 1.
+int vit_gemm_f32_count(int reset) { const int c = g_f32_count; if (reset) g_f32_count = 0; return c; }
+int vit_gemm_f32_split_count(int reset) { const int c = g_f32_split_count; if (reset) g_f32_split_count = 0; return c; }
 
 // Raw dispatcher (exported for tests/benchmarks of individual layouts).
 int vit_gemm(int dtype, int out_dtype, int p_layout, int q_layout, int epi, int M, int N, int R,

@@ -17,6 +17,24 @@
 //   CR [32 k][cols f32]: 512-B k-rows, chunk c of k-row r at r*512 + ((c ^ (((r >> 2) & 3) << 2)) << 4)
 // global_load_lds writes lane L's 16 B at piece + 16 L, so each lane loads the global chunk that
 // belongs in its slot (the swizzle is an involution).
+//
+// SPLIT = 1 ("high", vit_gemm_f32_precision(1), DESIGN 4.22): the same staging, LDS images, fragment
+// reads, ring, epilogue and stream-K code, but the products run as bf16x3.  Per k-step a wave reads the
+// fragments of both 16-deep halves, splits every f32 value x in registers into
+//   hi = bf16_rne(x),  lo = bf16_rne(x - float(hi))     (the subtraction is exact in f32)
+// with v_cvt_pk_bf16_f32, packs the value of k = 16h + 4g + t as element j = 4h + t of a bf16x8 operand
+// (the same rule for P and Q, so their reduction slots line up) and issues, per fragment pair,
+//   acc += P_hi Q_lo;  acc += P_lo Q_hi;  acc += P_hi Q_hi       (v_mfma_f32_16x16x32_bf16, this order)
+// P_lo Q_lo is dropped: tested to |C - C64| <= (3 * 2^-18 + (R + 3) * 2^-24) |P| |Q|^T on random normal-range
+// data (DESIGN 4.22 for what a worst case adds), and the exact sum when both operands are bf16 values (lo = 0).  The C/D lane map of 16x16x32_bf16 is that
+// of 16x16x4_f32, so the epilogue and the stream-K fragment images are unchanged.  48 MFMA-pipe cycles x
+// 16 fragment pairs per k-step against 256 x 16; the split is 3 VALU per value (half a cvt, an unpack, a
+// subtract, half a cvt), 64 values per lane per k-step.  The subtracts are single v_sub_f32 on purpose:
+// packed f32 VALU beside MFMAs is an anti-lever (MI355X_MICROARCH.md, "price of one filler").
+// Non-finite in, non-finite out: x = +-inf gives hi = +-inf, lo = NaN, and a finite |x| that rounds past the
+// bf16 range gives hi = +-inf, lo = -+inf; either way the element is NaN where the f32 form gives +-inf.
+// The setting is "at most bf16x3": GEMMs that do not take this path run the generic scalar-FMA kernel
+// and are exact f32 in either mode.
 namespace f32m {
 
 constexpr int BM = 128, BN = 128, BK = 32, THREADS = 256, WAVES = 4, S = 2;
@@ -78,9 +96,36 @@ __device__ __forceinline__ f32x4 frag(uint32_t img, int s, int h, int lane) {
   }
 }
 
+// SPLIT = 1: two f32 -> packed bf16 pair (RNE), and the 8 values of a lane's fragment (x0: k half 0, x1: k half
+// 1) -> hi / lo bf16x8 operands, element j = 4h + t
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float sub_f32(float a, float b) {  // one v_sub_f32, never SLP-packed
+  float r;
+  asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, bf16x8& hi, bf16x8& lo) {
+  const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+  u32x4_ H, L;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const float a = x[2 * p], b = x[2 * p + 1];
+    H[p] = cvt_pk_bf16(a, b);
+    const float ah = __uint_as_float(H[p] << 16), bh = __uint_as_float(H[p] & 0xffff0000u);
+    L[p] = cvt_pk_bf16(sub_f32(a, ah), sub_f32(b, bh));
+  }
+  hi = __builtin_bit_cast(bf16x8, H);
+  lo = __builtin_bit_cast(bf16x8, L);
+}
+
 // acc += P(i0.., rb + kb*BK ..) Q(j0.., ...)^T over k-steps [kb, ke) of one tile (the LDS ring restarts
 // per call; a __syncthreads before the first issue protects a previous call's reads)
-template <int PL, int QL>
+template <int PL, int QL, int SPLIT>
 __device__ __forceinline__ void mainloop(const float* __restrict__ P, int64_t ldp, const float* __restrict__ Q,
                                          int64_t ldq, int M, int N, int i0, int j0, int rb, int kb, int ke,
                                          f32x4 (&acc)[AI][AJ], char* smem, int wave, int lane) {
@@ -97,24 +142,53 @@ __device__ __forceinline__ void mainloop(const float* __restrict__ P, int64_t ld
     big::lds_barrier();
     const bool more = kt + 1 < ke;
     const uint32_t cur = big::lds_addr(smem + (kt % S) * STAGE);
+    if constexpr (SPLIT) {
+      // both halves' fragments before any MFMA; the next stage's P pieces before the first half's reads,
+      // its Q pieces before the second's (the same split issue)
+      f32x4 pf[2][AI], qf[2][AJ];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      // the next stage's P pieces before the first half's fragment reads, its Q pieces before the
-      // second's (as gemm_tile's split issue: not one burst behind the barrier)
-      if (more) issue(kt + 1, h + 1);
-      f32x4 pf[AI], qf[AJ];
+      for (int h = 0; h < 2; ++h) {
+        if (more) issue(kt + 1, h + 1);
 #pragma unroll
-      for (int b = 0; b < AJ; ++b) qf[b] = frag<QL, BN>(cur + PIMG, wj * AJ + b, h, lane);
+        for (int b = 0; b < AJ; ++b) qf[h][b] = frag<QL, BN>(cur + PIMG, wj * AJ + b, h, lane);
 #pragma unroll
-      for (int a = 0; a < AI; ++a) pf[a] = frag<PL, BM>(cur, wi * AI + a, h, lane);
+        for (int a = 0; a < AI; ++a) pf[h][a] = frag<PL, BM>(cur, wi * AI + a, h, lane);
+      }
       big::lgkm_wait0();
+      bf16x8 qh[AJ], ql[AJ];
 #pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
+      for (int b = 0; b < AJ; ++b) split8(qf[0][b], qf[1][b], qh[b], ql[b]);
 #pragma unroll
-        for (int a = 0; a < AI; ++a)
+      for (int a = 0; a < AI; ++a) {  // one P fragment's packs at a time (8 VGPRs live, not 32)
+        bf16x8 ph, pl;
+        split8(pf[0][a], pf[1][a], ph, pl);
 #pragma unroll
-          for (int b = 0; b < AJ; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[b][tt], pf[a][tt], acc[a][b], 0, 0, 0);
+        for (int b = 0; b < AJ; ++b) {
+          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ql[b], ph, acc[a][b], 0, 0, 0);  // P_hi Q_lo
+          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qh[b], pl, acc[a][b], 0, 0, 0);  // P_lo Q_hi
+          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qh[b], ph, acc[a][b], 0, 0, 0);  // P_hi Q_hi
+        }
+      }
+    } else {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        // the next stage's P pieces before the first half's fragment reads, its Q pieces before the
+        // second's (as gemm_tile's split issue: not one burst behind the barrier)
+        if (more) issue(kt + 1, h + 1);
+        f32x4 pf[AI], qf[AJ];
+#pragma unroll
+        for (int b = 0; b < AJ; ++b) qf[b] = frag<QL, BN>(cur + PIMG, wj * AJ + b, h, lane);
+#pragma unroll
+        for (int a = 0; a < AI; ++a) pf[a] = frag<PL, BM>(cur, wi * AI + a, h, lane);
+        big::lgkm_wait0();
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+          for (int a = 0; a < AI; ++a)
+#pragma unroll
+            for (int b = 0; b < AJ; ++b)
+              acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[b][tt], pf[a][tt], acc[a][b], 0, 0, 0);
+      }
     }
     // every wave's reads of this slot retire (lgkm_wait0) before the next barrier, so the
     // slot can be refilled after it (WAR)
@@ -128,7 +202,7 @@ __device__ __forceinline__ void epilogue(const Epi& e, const f32x4 (&acc)[AI][AJ
   VIT_EPI_FRAG(AI, AJ, i0 + wi * 64, j0 + wj * 64, )
 }
 
-template <int PL, int QL, int EPI, typename TO, typename TA>
+template <int PL, int QL, int EPI, typename TO, typename TA, int SPLIT>
 __global__ __launch_bounds__(THREADS, 2) void gemm_kernel(const float* __restrict__ P, int64_t ldp,
                                                           const float* __restrict__ Q, int64_t ldq, int M, int N,
                                                           int R, int r_chunk, Epi e) {
@@ -149,7 +223,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_kernel(const float* __restric
   for (int a = 0; a < AI; ++a)
 #pragma unroll
     for (int b = 0; b < AJ; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  mainloop<PL, QL>(P, ldp, Q, ldq, M, N, i0, j0, rb, 0, nk, acc, smem, wave, lane);
+  mainloop<PL, QL, SPLIT>(P, ldp, Q, ldq, M, N, i0, j0, rb, 0, nk, acc, smem, wave, lane);
   epilogue<EPI, TO, TA>(e, acc, M, N, i0, j0, z, wave, lane);
 }
 
@@ -165,7 +239,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_kernel(const float* __restric
 // "In-launch split-K reduction") and runs the tile's epilogue.  Sums in a fixed order: the result does
 // not depend on arrival order.  (Sharing all k-steps from the start measured 2-7 % slower on the tall
 // forwards: co-resident workgroups sat at different k offsets of the blocks they share.)
-template <int PL, int QL, int EPI, typename TO, typename TA>
+template <int PL, int QL, int EPI, typename TO, typename TA, int SPLIT>
 __global__ __launch_bounds__(THREADS, 2) void gemm_sk_kernel(const float* __restrict__ P, int64_t ldp,
                                                              const float* __restrict__ Q, int64_t ldq, int M, int N,
                                                              int R, int dp_rounds, Epi e,
@@ -186,7 +260,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_sk_kernel(const float* __rest
 #pragma unroll
       for (int b = 0; b < AJ; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();  // the previous tile's LDS reads are done before the ring restarts
-    mainloop<PL, QL>(P, ldp, Q, ldq, M, N, ti * BM, tj * BN, 0, 0, nk, acc, smem, wave, lane);
+    mainloop<PL, QL, SPLIT>(P, ldp, Q, ldq, M, N, ti * BM, tj * BN, 0, 0, nk, acc, smem, wave, lane);
     epilogue<EPI, TO, TA>(e, acc, M, N, ti * BM, tj * BN, 0, wave, lane);
   }
   const int tbase = dp_rounds * G;
@@ -206,7 +280,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_sk_kernel(const float* __rest
 #pragma unroll
       for (int b = 0; b < AJ; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();  // the previous segment's LDS reads are done before the ring restarts
-    mainloop<PL, QL>(P, ldp, Q, ldq, M, N, i0, j0, 0, k0, k1, acc, smem, wave, lane);
+    mainloop<PL, QL, SPLIT>(P, ldp, Q, ldq, M, N, i0, j0, 0, k0, k1, acc, smem, wave, lane);
     s += k1 - k0;
     if (k0 == 0 && k1 == nk) {
       epilogue<EPI, TO, TA>(e, acc, M, N, i0, j0, 0, wave, lane);

@@ -849,6 +849,37 @@ def mse_bwd(pred, target, grad_loss=None):
     return d
 
 
+_F32_MATMUL = ("highest", "high")  # vit_gemm_f32_precision 0 / 1
+
+
+def set_float32_matmul_precision(precision):
+    """The arithmetic of the fp32 MFMA GEMMs (``compute_dtype=torch.float32``), after
+    ``torch.set_float32_matmul_precision``:
+
+    - ``"highest"`` (the default): ``v_mfma_f32_16x16x4_f32``, exact f32 products;
+    - ``"high"``: each f32 operand as the sum of two bfloat16 (``hi = bf16(x)``, ``lo = bf16(x - hi)``) and
+      three bf16 MFMA products with f32 accumulation: about 4.4e-6 rms relative error on random data, tested to
+      ``|C - C64| <= (3 * 2^-18 + (R + 3) * 2^-24) |P||Q|^T``; exact when both operands hold bf16 values.
+      At most bf16x3: GEMMs too small or misaligned for the MFMA path stay exact f32.  An infinite operand
+      gives NaN where ``"highest"`` gives an infinity.
+
+    ``"medium"`` is refused: operands rounded to one bfloat16 are ``compute_dtype=torch.bfloat16``.  The
+    setting is process-wide and read when a GEMM is launched, so a backward pass runs in the mode current
+    when it runs, not the one its forward ran in; cached frozen-prefix tensors carry the mode in their keys and
+    are rebuilt after a switch.  The environment variable ``VIT_F32_MATMUL=high`` sets the initial value when
+    the library loads (spawned workers inherit it).  bf16 models, attention, LayerNorm and everything else
+    are untouched.  Host-only: works without a GPU."""
+    if precision == "medium":
+        raise ValueError('float32 matmul precision "medium" (operands rounded to one bfloat16) is not a mode of '
+                         'the fp32 path: build the model with compute_dtype=torch.bfloat16')
+    if precision not in _F32_MATMUL:
+        raise ValueError(f'float32 matmul precision must be "highest" or "high", got {precision!r}')
+    L.lib().vit_gemm_f32_precision(_F32_MATMUL.index(precision))
+
+
+def get_float32_matmul_precision() -> str:
+    """``"highest"`` or ``"high"``: see :func:`set_float32_matmul_precision`."""
+    return _F32_MATMUL[L.lib().vit_gemm_f32_precision(-1)]
 
 
 def gemm(P, p_layout, Q, q_layout, M, N, R, out=None, out_dtype=torch.float32, bias=None):

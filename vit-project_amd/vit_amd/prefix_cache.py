@@ -9,7 +9,10 @@ device, and hands a batch's rows to ``CLIPHBA.forward(visual_prefix=...)`` throu
 
 The key follows ``CLIP._text_prefix``: ``(data_ptr, _version)`` of the stem's and the frozen blocks'
 parameters, the cut, the compute dtype, the fp8-attention switch, ``pos_embedding``, the images'
-``(data_ptr, _version, shape)`` and the streamed-fp8 switch (``long_sequences``).  The cache holds references to those tensors, so an address in the key
+``(data_ptr, _version, shape)`` and the streamed-fp8 switch (``long_sequences``).  Under
+``set_float32_matmul_precision("high")`` the compute-dtype element is the pair ``(compute_dtype, "high")``: rows
+built in one fp32 GEMM mode are rebuilt in the other, never read, and the key's length, its last element and
+its default-mode value stay what they were.  The cache holds references to those tensors, so an address in the key
 cannot come back as another tensor while the cache lives.  ``valid_for`` recomputes the key; a stale
 cache is rebuilt by ``ensure`` (the sweep calls it before every condition), never read.
 """
@@ -48,12 +51,19 @@ def _frozen_tensors(cm, first):
     return stem + [p for b in list(v.transformer.resblocks)[:first] for p in b.parameters()]
 
 
+def compute_key(cm):
+    """The arithmetic the cached rows were computed in: the compute dtype, paired with the fp32 GEMM mode when
+    that is not the default ``"highest"`` (``ops.set_float32_matmul_precision``)."""
+    mode = ops.get_float32_matmul_precision()
+    return cm.compute_dtype if mode == "highest" else (cm.compute_dtype, mode)
+
+
 def prefix_key(model, images):
     """What the cached tokens depend on, as a hashable tuple (see the module docstring)."""
     m = _hba(model)
     cm = m.clip_model
     first = frozen_visual_blocks(m)
-    return (tuple((p.data_ptr(), p._version) for p in _frozen_tensors(cm, first)), first, cm.compute_dtype,
+    return (tuple((p.data_ptr(), p._version) for p in _frozen_tensors(cm, first)), first, compute_key(cm),
             bool(cm.attention_fp8), bool(m.pos_embedding), (images.data_ptr(), images._version, tuple(images.shape)),
             bool(cm.attention_fp8_long))
 

@@ -464,6 +464,10 @@ def _sweep_worker(rank, world, make_model_and_optimizer, criterion, data, condit
     threads = kw.pop("torch_threads", None)
     if threads:
         torch.set_num_threads(threads)
+    mode = kw.pop("float32_matmul", None)
+    if mode is not None:
+        from . import ops
+        ops.set_float32_matmul_precision(mode)
     if devices:
         dev = torch.device("cuda", devices[rank % len(devices)])
         torch.cuda.set_device(dev)
@@ -479,10 +483,15 @@ def launch_sweep(nprocs, make_model_and_optimizer, criterion, data, conditions, 
     ``shard_conditions`` share of ``conditions`` through :func:`run_sweep` -- the 8-way sharded
     C5 sweep with no collective.  ``make_model_and_optimizer`` and ``criterion``
     must be picklable (module-level).  Returns {rank: [((start, length), csv, source)]}.
-    ``cache_visual_prefix``: each worker builds and owns its visual prefix caches (``run_sweep``)."""
+    ``cache_visual_prefix``: each worker builds and owns its visual prefix caches (``run_sweep``).
+    The workers run in the caller's fp32 GEMM mode (``set_float32_matmul_precision``; ``VIT_F32_MATMUL`` is
+    inherited through the environment as well)."""
     import torch.multiprocessing as mp
+    from . import _lib, ops
     if cache_visual_prefix:
         kw = dict(kw, cache_visual_prefix=True)
+    if _lib._lib is not None:  # (a process that never loaded the library cannot have switched the mode)
+        kw = dict(kw, float32_matmul=ops.get_float32_matmul_precision())
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     devices = list(gpus) if gpus else []

@@ -12,6 +12,10 @@ spread ``(max - min) / median``, the ratio, and the on-against-off relative diff
 
 ``--eot-tail`` does the same for the text tower's EOT tail (``CLIP.set_eot_tail``); given together
 with ``--cls-tail`` the class-token tail stays on throughout and the EOT tail alone alternates.
+
+``--f32-attention highest|high`` sets the fp32 attention arithmetic of the whole run
+(``vit_amd.set_float32_attention_precision``); ``--f32-attention-ab`` alternates the two in one process
+the way ``--f32-ab`` alternates the GEMM mode, the GEMMs staying at ``--f32-matmul``.
 """
 import argparse
 import json
@@ -85,11 +89,13 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds, which="cls",
     y = torch.randn(batch, 66, device=dev) * 0.5 + 1.0
     if which == "f32":  # the fp32 GEMM mode ("high" = bf16x3) off and on, the class-token tail as cls_fixed says
         switch = lambda on: vit_amd.set_float32_matmul_precision("high" if on else "highest")
+    elif which == "f32attn":  # the fp32 attention mode off and on, the GEMM mode as --f32-matmul says
+        switch = lambda on: vit_amd.set_float32_attention_precision("high" if on else "highest")
     else:
         switch = m.clip_model.set_cls_tail if which == "cls" else m.clip_model.set_eot_tail
-    if which in ("eot", "f32"):
+    if which in ("eot", "f32", "f32attn"):
         m.clip_model.set_cls_tail(cls_fixed)
-    key = "f32_high" if which == "f32" else which + "_tail"
+    key = {"f32": "f32_high", "f32attn": "f32_attention_high"}.get(which, which + "_tail")
 
     def window(n):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -127,7 +133,7 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds, which="cls",
     return {"ms_per_step": {key + "_off": off, key + "_on": on}, key + "_speedup": round(off["median"] / on["median"], 4),
             "images_per_sec": {key + "_off": round(batch / off["median"] * 1e3, 2),
                                key + "_on": round(batch / on["median"] * 1e3, 2)},
-            "cls_tail_throughout": bool(which in ("eot", "f32") and cls_fixed),
+            "cls_tail_throughout": bool(which in ("eot", "f32", "f32attn") and cls_fixed),
             "prediction_rel_diff_on_vs_off": float((preds[True] - preds[False]).abs().max() / preds[False].abs().max()),
             "prediction_rms_rel_diff_on_vs_off": float(((preds[True] - preds[False]).pow(2).mean()
                                                         / preds[False].pow(2).mean()).sqrt()),
@@ -153,16 +159,26 @@ def main():
                     help="fp32 GEMM arithmetic of the whole run (vit_amd.set_float32_matmul_precision; high = bf16x3)")
     ap.add_argument("--f32-ab", action="store_true",
                     help="alternate --f32-matmul highest and high in one process (with --cls-tail: that tail on throughout)")
+    ap.add_argument("--f32-attention", choices=["highest", "high"], default=None,
+                    help="fp32 attention arithmetic of the whole run (vit_amd.set_float32_attention_precision; high = "
+                         "bf16x3 in the resident f32 kernels)")
+    ap.add_argument("--f32-attention-ab", action="store_true",
+                    help="alternate --f32-attention highest and high in one process, the GEMMs as --f32-matmul says "
+                         "(with --cls-tail: that tail on throughout)")
     a = ap.parse_args()
     import torch
     if a.f32_matmul:
         import vit_amd
         vit_amd.set_float32_matmul_precision(a.f32_matmul)
-    if a.cls_tail or a.eot_tail or a.f32_ab:
+    if a.f32_attention:
+        import vit_amd
+        vit_amd.set_float32_attention_precision(a.f32_attention)
+    if a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab:
         if a.rounds < 3:
             ap.error("--rounds must be at least 3: the spread is part of the record")
         r = cls_tail_leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup, a.adapter, a.rounds,
-                         "f32" if a.f32_ab else "eot" if a.eot_tail else "cls", a.cls_tail)
+                         "f32attn" if a.f32_attention_ab else "f32" if a.f32_ab else "eot" if a.eot_tail else "cls",
+                         a.cls_tail)
     else:
         leg = bench.c3_leg if a.adapter == "dora" else lora_leg
         r = leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup)
@@ -170,6 +186,8 @@ def main():
     r["adapter"] = a.adapter
     if a.f32_matmul:
         r["f32_matmul"] = a.f32_matmul
+    if a.f32_attention:
+        r["f32_attention"] = a.f32_attention
     print(json.dumps(r))
 
 

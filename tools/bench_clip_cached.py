@@ -34,6 +34,11 @@ stays on throughout and the EOT tail alone alternates.  Records: ``bench_clip_ca
 ``*_tail`` series are then the ``high`` passes, on prefix caches built in ``high``; ``--cls-tail`` keeps that tail
 on throughout): ``f32_high_speedup``, records ``bench_clip_cached_f32high[_clstail]_{dtype}.json``.
 
+``--f32-attention highest|high`` sets the fp32 attention arithmetic of the whole run
+(``vit_amd.set_float32_attention_precision``) and ``--f32-attention-ab`` alternates the two the way
+``--f32-ab`` alternates the GEMM mode, the GEMMs staying at ``--f32-matmul``: ``f32_attention_high_speedup``, records
+``bench_clip_cached[_f32high]_f32attnhigh[_clstail]_{dtype}.json``.
+
 ``--adapter lora`` puts the reference's LoRA pair (NEWP:339-404) where DoRA stands; its records are named
 ``bench_clip_cached_lora_{dtype}.json``.
 """
@@ -106,21 +111,24 @@ def model_leg(a, dtype_name):
         pred_diff = float((pc - pu).abs().max() / pu.abs().max())
 
     fixed = caches["train"].take(torch.arange(a.batch))
-    tails = (False, True) if (a.cls_tail or a.eot_tail or a.f32_ab) else (False,)
+    ab = a.f32_ab or a.f32_attention_ab  # an fp32 mode alternates
+    tails = (False, True) if (a.cls_tail or a.eot_tail or ab) else (False,)
     # the switch that alternates: the EOT tail if asked for (the class-token tail then stays as --cls-tail says)
     set_tail = m.clip_model.set_eot_tail if a.eot_tail else m.clip_model.set_cls_tail
     tail_key = "eot_tail" if a.eot_tail else "cls_tail"
-    if a.eot_tail or a.f32_ab:
+    if a.eot_tail or ab:
         m.clip_model.set_cls_tail(a.cls_tail)
-    if a.f32_ab:  # the fp32 GEMM mode alternates; each mode reads the prefix caches built in it
-        vit_amd.set_float32_matmul_precision("high")
+    if ab:  # the fp32 GEMM (or attention) mode alternates; each mode reads the prefix caches built in it
+        set_mode = (vit_amd.set_float32_attention_precision if a.f32_attention_ab
+                    else vit_amd.set_float32_matmul_precision)
+        set_mode("high")
         by_mode = {False: caches, True: S.prefix_caches_for(m, data, None, a.batch)}
-        vit_amd.set_float32_matmul_precision("highest")
-        tail_key = "f32_high"
+        set_mode("highest")
+        tail_key = "f32_attention_high" if a.f32_attention_ab else "f32_high"
 
         def set_tail(on):
             nonlocal caches
-            vit_amd.set_float32_matmul_precision("high" if on else "highest")
+            set_mode("high" if on else "highest")
             caches = by_mode[on]
     vname = lambda c, t: ("cached" if c else "uncached") + ("_tail" if t else "")
     tail_diff = None
@@ -219,10 +227,19 @@ def model_leg(a, dtype_name):
                 b = rec[k][base]["median"]
                 gain[base] = round(s["median"] / b if k.endswith("per_sec") else b / s["median"], 4)
             rec[k][tail_key + "_speedup"] = gain
+    if ab:  # the 48 images' RSA correlation in either mode, on the parameters as the timed steps left them
+        rho = {}
+        for t in tails:
+            set_tail(t)
+            rho["high" if t else "highest"] = float(S.behavioral_rsa(m, data["inference"], data["reference_rdm"])[0])
+        set_tail(False)
+        rec[tail_key + "_rsa_rho"] = rho
     if len(tails) > 1:
         rec[tail_key + "_prediction_rel_diff"] = tail_diff
         rec[tail_key + "_prediction_bound"] = 1e-3 if dtype_name == "f32" else 3e-2
-        rec["cls_tail_throughout"] = bool((a.eot_tail or a.f32_ab) and a.cls_tail)
+        rec["cls_tail_throughout"] = bool((a.eot_tail or ab) and a.cls_tail)
+    rec["f32_matmul"], rec["f32_attention"] = (vit_amd.get_float32_matmul_precision(),
+                                               "ab" if a.f32_attention_ab else vit_amd.get_float32_attention_precision())
     rec["train_step_images_per_sec"]["cached_without_gather"] = _summary(no_gather)
     return rec
 
@@ -293,8 +310,12 @@ def driver(a):
             cmd.append("--f32-ab")
         if a.f32_matmul:
             cmd += ["--f32-matmul", a.f32_matmul]
+        if a.f32_attention_ab:
+            cmd.append("--f32-attention-ab")
+        if a.f32_attention:
+            cmd += ["--f32-attention", a.f32_attention]
         print("leg", leg, flush=True)
-        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if (a.cls_tail or a.eot_tail or a.f32_ab) else 1)).returncode  # TimeoutExpired ends the run
+        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if (a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab) else 1)).returncode  # TimeoutExpired ends the run
         if rc != 0:
             print(f"leg {leg} failed with exit code {rc}: stopping", flush=True)
             return rc
@@ -328,20 +349,31 @@ def main():
                     help="fp32 GEMM arithmetic of the whole run (high = bf16x3)")
     ap.add_argument("--f32-ab", action="store_true",
                     help="alternate the fp32 GEMM modes highest and high (with --cls-tail: that tail on throughout)")
+    ap.add_argument("--f32-attention", choices=["highest", "high"], default=None,
+                    help="fp32 attention arithmetic of the whole run (high = bf16x3 in the resident f32 kernels)")
+    ap.add_argument("--f32-attention-ab", action="store_true",
+                    help="alternate the fp32 attention modes highest and high, the GEMMs as --f32-matmul says (with "
+                         "--cls-tail: that tail on throughout)")
     a = ap.parse_args()
     if a.rounds < 3:
         ap.error("--rounds must be at least 3: the spread is part of the record")
     if a.f32_ab and (a.eot_tail or a.f32_matmul):
         ap.error("--f32-ab alternates the fp32 GEMM mode alone")
+    if a.f32_attention_ab and (a.eot_tail or a.f32_ab or a.f32_attention):
+        ap.error("--f32-attention-ab alternates the fp32 attention mode alone")
     if a.leg is None:
         sys.exit(driver(a))
     if a.f32_matmul:
         import vit_amd
         vit_amd.set_float32_matmul_precision(a.f32_matmul)
+    if a.f32_attention:
+        import vit_amd
+        vit_amd.set_float32_attention_precision(a.f32_attention)
     rec = gather_leg(a) if a.leg == "gather" else model_leg(a, a.leg)
     os.makedirs(a.out, exist_ok=True)
     tag = (("" if a.adapter == "dora" else f"_{a.adapter}") + ("_eottail" if a.eot_tail else "")
-           + ("_f32high" if (a.f32_ab or a.f32_matmul == "high") else "") + ("_clstail" if a.cls_tail else ""))
+           + ("_f32high" if (a.f32_ab or a.f32_matmul == "high") else "")
+           + ("_f32attnhigh" if (a.f32_attention_ab or a.f32_attention == "high") else "") + ("_clstail" if a.cls_tail else ""))
     name = "gather_blocks.json" if a.leg == "gather" else f"bench_clip_cached{tag}_{a.leg}.json"
     with open(os.path.join(a.out, name), "w") as fh:
         json.dump(rec, fh, indent=1)

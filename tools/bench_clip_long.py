@@ -5,9 +5,12 @@ tokens on the streamed f32 kernels against the generic ones (vit_sdpa_long_confi
 
     python tools/bench_clip_long.py [--batch 16] [--steps 5] [--warmup 2] [--rounds 3] [--steps-generic 2]
                                     [--f32-matmul highest|high] [--f32-ab]
+                                    [--f32-attention highest|high] [--f32-attention-ab]
 
 ``--f32-matmul`` sets the fp32 GEMM arithmetic of the run (``high`` = bf16x3); ``--f32-ab``
-alternates ``highest`` and ``high`` instead, both on the streamed attention kernels.
+alternates ``highest`` and ``high`` instead, both on the streamed attention kernels.  ``--f32-attention`` and
+``--f32-attention-ab`` do the same with the fp32 attention mode: at 577 tokens only the text
+tower's 77-token attention takes the bf16x3 kernels, the visual tower's streamed f32 kernels stay exact.
 """
 import argparse
 import json
@@ -36,9 +39,16 @@ def main():
     ap.add_argument("--prompts", type=int, default=66)
     ap.add_argument("--f32-matmul", choices=["highest", "high"], default=None)
     ap.add_argument("--f32-ab", action="store_true")
+    ap.add_argument("--f32-attention", choices=["highest", "high"], default=None)
+    ap.add_argument("--f32-attention-ab", action="store_true")
     a = ap.parse_args()
+    if a.f32_ab and a.f32_attention_ab:
+        ap.error("one switch alternates at a time")
     if a.f32_matmul:
         vit_amd.set_float32_matmul_precision(a.f32_matmul)
+    if a.f32_attention:
+        vit_amd.set_float32_attention_precision(a.f32_attention)
+    set_mode = vit_amd.set_float32_attention_precision if a.f32_attention_ab else vit_amd.set_float32_matmul_precision
     dev = torch.device("cuda", 0)
     lib = L.lib()
     torch.manual_seed(0)
@@ -72,19 +82,20 @@ def main():
         assert torch.isfinite(loss)
         return a.batch * steps / dt, lib.vit_sdpa_long_f32_count(0) - c0
 
-    if a.f32_ab:
+    if a.f32_ab or a.f32_attention_ab:
         ips = {"highest": [], "high": []}
         try:
             for rnd in range(a.rounds):
                 for name in ips:
-                    vit_amd.set_float32_matmul_precision(name)
+                    set_mode(name)
                     ips[name].append(round(run(1, a.steps, a.warmup if rnd == 0 else 1)[0], 2))
         finally:
             lib.vit_sdpa_long_config(-1)
-            vit_amd.set_float32_matmul_precision("highest")
+            set_mode("highest")
         med = {k: statistics.median(v) for k, v in ips.items()}
         print(json.dumps({"metric": "images/sec CLIP-HBA ViT-L/14@336px + DoRA fp32 train step", "batch": a.batch,
                           "steps": a.steps, "rounds": a.rounds, "images_per_sec": ips, "median": med,
+                          "alternated": "f32_attention" if a.f32_attention_ab else "f32_matmul",
                           "spread": {k: round((max(v) - min(v)) / med[k], 4) for k, v in ips.items()},
                           "high_over_highest": round(med["high"] / med["highest"], 3)}), flush=True)
         return

@@ -19,7 +19,7 @@ for line in sys.stdin:
         pass
     if k == 'wavefront_size':
         if pat.search(cur.get('name','')):
-            print(cur.get('vgpr_count'), cur.get('agpr_count'), 'spill', cur.get('vgpr_spill_count'), 'priv', cur.get('private_segment_fixed_size'), cur.get('name','')[:110])
+            print(cur.get('vgpr_count'), cur.get('agpr_count'), 'spill', cur.get('vgpr_spill_count'), 'priv', cur.get('private_segment_fixed_size'), cur.get('name','')[:110], 'lds', cur.get('group_segment_fixed_size'))
         cur = {}
 " "${2:-.}"
 rm -rf $T

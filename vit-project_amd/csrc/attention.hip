@@ -17,11 +17,17 @@
 // cross-lane shuffles; P stays in registers and feeds the PV MFMA as its
 // B-operand (k-slot permutation pi), V^T comes from ds_read_b64_tr_b16.
 // f32 path (parity mode): scalar-FMA online softmax.
+// resident f32 path, "high" (vit_sdpa_f32_precision(1), opt-in): the bf16 path's algebra on hi / lo bf16 splits of the
+// f32 operands, three MFMA products a product (attn_*_f32x3; see the block in front of F32X3).
 // one-query path (attn_cls1_*, the CLIP visual tower's class-token tail): query row 0 of every image alone,
 // K / V straight from HBM to registers, no MFMA -- see the block in front of attn_cls1_fwd; attn_row1_fwd is the
 // same forward at a row per sequence, causal or not (the CLIP text tower's EOT tail).
+#include <stdlib.h>
+#include <string.h>
+
 #include <initializer_list>
 
+#include "bf16_split.hpp"
 #include "common.hpp"
 #include "reduce.hpp"
 
@@ -1608,6 +1614,321 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_f32mfma(const float* __restr
 }
 
 // ---------------------------------------------------------------------------
+// Resident f32 attention as three bf16 MFMA products ("high", vit_sdpa_f32_precision(1)): the
+// operand algebra of the resident bf16 kernels (attn_fwd_mfma, at_dq_step, at_dkv_step -- rowf / trf fragments,
+// the AtOffsets swizzle, 16-row tiles in 32-row pairs) fed from f32 global memory.  Every f32 value x is split
+// with the GEMM's helper (bf16_split.hpp) into hi = bf16_rne(x), lo = bf16_rne(x - hi), and every matrix product
+// runs as  acc += A_hi B_lo;  acc += A_lo B_hi;  acc += A_hi B_hi  on v_mfma_f32_16x16x32_bf16 (A, B: the MFMA's
+// operands; lo lo is dropped).
+//   head images : loaded as f32, split once while the LDS image is written -- a hi and a lo image per matrix in
+//                 the bf16 layout, 4 x ROWS x 128 B, the bytes of the two f32 images they replace
+//   row operands: the wave's own rows (q; q and dO; k and v) from global memory as f32, split once per tile
+//   P, dS       : split from the f32 accumulators into a hi and a lo pack (4 values per lane and tile)
+// The masking, the row max / sum of the unsplit p, exp2, delta = rowsum(dO O), 1 / l, lse, the scale factors and
+// the stores are f32 as in the f32 MFMA kernels above.  Dynamic LDS; two workgroups per CU while four images fit
+// twice (<= 80 KiB), one beyond -- the launch bound follows.
+// ---------------------------------------------------------------------------
+template <int NT>
+struct F32X3 {
+  static constexpr int NT2 = (NT + 1) / 2, ROWS = NT2 * 32, IMG = ROWS * 128;
+  static constexpr int LDS = 4 * IMG, LDS_DKV = 4 * IMG + 2 * ROWS * 4;
+  static constexpr int CU_LDS = 163840;
+  // waves per SIMD (8 waves per workgroup on 4 SIMDs): 4 = two workgroups per CU (128 VGPRs), 2 = one (256)
+  static constexpr int WPS = 2 * LDS <= CU_LDS ? 4 : 2, WPS_DKV = 2 * LDS_DKV <= CU_LDS ? 4 : 2;
+  static_assert(LDS_DKV <= CU_LDS, "one workgroup per CU");
+  static void attrs();
+};
+
+__device__ __forceinline__ f32x4 mfma16x3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl,
+                                          f32x4 c) {
+  c = mfma16(ah, bl, c);
+  c = mfma16(al, bh, c);
+  return mfma16(ah, bh, c);
+}
+// Rows [0, N) of two f32 head slices -> a hi and a lo bf16 image each (at_off layout, rows >= N zero).
+template <int ROWS>
+__device__ __forceinline__ void x3_load2(char* ahi, char* alo, const float* sa, int64_t lda, char* bhi, char* blo,
+                                         const float* sb, int64_t ldb, int N) {
+  for (int i = threadIdx.x; i < ROWS * 8; i += AT_THREADS) {
+    const int r = i >> 3, c = i & 7;
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, b0 = a0, b1 = a0;
+    if (r < N) {
+      a0 = *reinterpret_cast<const f32x4*>(sa + (int64_t)r * lda + c * 8);
+      a1 = *reinterpret_cast<const f32x4*>(sa + (int64_t)r * lda + c * 8 + 4);
+      b0 = *reinterpret_cast<const f32x4*>(sb + (int64_t)r * ldb + c * 8);
+      b1 = *reinterpret_cast<const f32x4*>(sb + (int64_t)r * ldb + c * 8 + 4);
+    }
+    bf16x8 h, l;
+    split8<1>(a0, a1, h, l);
+    *reinterpret_cast<bf16x8*>(ahi + at_off(r, c)) = h;
+    *reinterpret_cast<bf16x8*>(alo + at_off(r, c)) = l;
+    split8<1>(b0, b1, h, l);
+    *reinterpret_cast<bf16x8*>(bhi + at_off(r, c)) = h;
+    *reinterpret_cast<bf16x8*>(blo + at_off(r, c)) = l;
+  }
+}
+// The lane's row fragments (head dims kk * 32 + 8g .. + 8) of the f32 row at p, split; x: the f32 values.
+__device__ __forceinline__ void x3_row(const float* p, int g, bf16x8 (&hi)[2], bf16x8 (&lo)[2], f32x4 (&x)[4]) {
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    x[2 * kk] = *reinterpret_cast<const f32x4*>(p + kk * 32 + g * 8);
+    x[2 * kk + 1] = *reinterpret_cast<const f32x4*>(p + kk * 32 + g * 8 + 4);
+    split8<1>(x[2 * kk], x[2 * kk + 1], hi[kk], lo[kk]);
+  }
+}
+// x[dt] * mul = columns dt * 16 + 4g .. + 4 of the lane's row at p (the accumulator layout of the bf16 kernels)
+__device__ __forceinline__ void x3_store_row(float* p, const f32x4 (&x)[4], float mul, int g) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+    *reinterpret_cast<f32x4*>(p + dt * 16 + 4 * g) = f32x4{x[dt][0] * mul, x[dt][1] * mul, x[dt][2] * mul, x[dt][3] * mul};
+}
+
+template <int NT, bool CAUSAL>
+__global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_fwd_f32x3(const float* __restrict__ qkv,
+                                                                             int64_t ld_qkv, int D, int H, int N,
+                                                                             float scale, float* __restrict__ o,
+                                                                             int64_t ld_o, float* __restrict__ lse) {
+  constexpr int NT2 = F32X3<NT>::NT2, ROWS = F32X3<NT>::ROWS, IMG = F32X3<NT>::IMG;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Khi = smem;
+  char* Klo = smem + IMG;
+  char* Vhi = smem + 2 * IMG;
+  char* Vlo = smem + 3 * IMG;
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  x3_load2<ROWS>(Khi, Klo, base + D, ld_qkv, Vhi, Vlo, base + 2 * D, ld_qkv, N);
+  const AtOffsets off(lane);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  for (int qt = wave; qt < NT; qt += AT_WAVES) {
+    const int q = qt * 16 + (lane & 15);
+    bf16x8 qh[2], ql[2];
+    {
+      f32x4 x[4];
+      x3_row(base + (int64_t)min(q, N - 1) * ld_qkv, g, qh, ql, x);
+    }
+    f32x4 s[NT];
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt) {
+      s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+        s[kt] = mfma16x3(rowf(Khi, kt * 16, off.row[kk]), rowf(Klo, kt * 16, off.row[kk]), qh[kk], ql[kk], s[kt]);
+      if (kt % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // bound K-fragment hoisting (VGPRs)
+    }
+    // keys >= N exist only in the last tile
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if ((NT - 1) * 16 + 4 * g + r >= N) s[NT - 1][r] = -INFINITY;
+    if constexpr (CAUSAL) {
+#pragma unroll
+      for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (kt * 16 + 4 * g + r > q) s[kt][r] = -INFINITY;
+    }
+    float mr[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mr[r] = fmaxf(mr[r], s[kt][r]);
+    float m = fmaxf(fmaxf(mr[0], mr[1]), fmaxf(mr[2], mr[3]));
+    m = fmaxf(m, __shfl_xor(m, 16, 64));
+    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    const float mc = m * c2;
+    float lr[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { const float p = fexp2(fmaf(s[kt][r], c2, -mc)); s[kt][r] = p; lr[r] += p; }
+    float l = (lr[0] + lr[1]) + (lr[2] + lr[3]);
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    f32x4 oacc[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < NT2; ++ks) {
+      const f32x4 hi = (2 * ks + 1 < NT) ? s[2 * ks + 1 < NT ? 2 * ks + 1 : 0] : f32x4{0.f, 0.f, 0.f, 0.f};
+      bf16x8 ph, pl;
+      split8<1>(s[2 * ks], hi, ph, pl);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+        oacc[dt] = mfma16x3(trf(Vhi, ks * 32, off.tr[dt]), trf(Vlo, ks * 32, off.tr[dt]), ph, pl, oacc[dt]);
+      if (ks % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // bound V-fragment hoisting (VGPRs)
+    }
+    if (q < N) {
+      x3_store_row(o + ((int64_t)b * N + q) * ld_o + h * 64, oacc, 1.0f / l, g);
+      if (g == 0) lse[(int64_t)bh * N + q] = (mc + __log2f(l)) * LN2;
+    }
+  }
+}
+
+// dq half, one pair of key tiles: at_dq_step on split operands.
+__device__ __forceinline__ void x3_dq_step(const char* Khi, const char* Klo, const char* Vhi, const char* Vlo, int row0,
+                                           int N, bool edge, const AtOffsets& off, int g, const bf16x8 (&qh)[2],
+                                           const bf16x8 (&ql)[2], const bf16x8 (&oh)[2], const bf16x8 (&ol)[2], float c2,
+                                           float l2, float dl, int q, int causal, f32x4 (&dq)[4]) {
+  f32x4 ds[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
+    const int rw = row0 + u * 16;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      sacc = mfma16x3(rowf(Khi, rw, off.row[kk]), rowf(Klo, rw, off.row[kk]), qh[kk], ql[kk], sacc);
+      dpacc = mfma16x3(rowf(Vhi, rw, off.row[kk]), rowf(Vlo, rw, off.row[kk]), oh[kk], ol[kk], dpacc);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = rw + 4 * g + r;
+      float pv = fexp2(fmaf(sacc[r], c2, -l2));
+      if (edge && key >= N) pv = 0.f;
+      if (causal && key > q) pv = 0.f;
+      ds[u][r] = pv * (dpacc[r] - dl);
+    }
+    if (u == 0) __builtin_amdgcn_sched_barrier(0);  // bound fragment hoisting: both tiles' 16 fragments spill at 128 VGPRs
+  }
+  bf16x8 dsh, dsl;
+  split8<1>(ds[0], ds[1], dsh, dsl);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+    dq[dt] = mfma16x3(trf(Khi, row0, off.tr[dt]), trf(Klo, row0, off.tr[dt]), dsh, dsl, dq[dt]);
+}
+// dkv half, one pair of query tiles: at_dkv_step on split operands.
+__device__ __forceinline__ void x3_dkv_step(const char* Qhi, const char* Qlo, const char* Ohi, const char* Olo,
+                                            const float* lse2, const float* delta, int row0, const AtOffsets& off, int g,
+                                            const bf16x8 (&kh)[2], const bf16x8 (&kl)[2], const bf16x8 (&vh)[2],
+                                            const bf16x8 (&vl)[2], float c2, bool kvalid, int key, int causal,
+                                            f32x4 (&dk)[4], f32x4 (&dv)[4]) {
+  f32x4 p[2], ds[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
+    const int rw = row0 + u * 16;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      sacc = mfma16x3(rowf(Qhi, rw, off.row[kk]), rowf(Qlo, rw, off.row[kk]), kh[kk], kl[kk], sacc);
+      dpacc = mfma16x3(rowf(Ohi, rw, off.row[kk]), rowf(Olo, rw, off.row[kk]), vh[kk], vl[kk], dpacc);
+    }
+    const f32x4 l2 = *reinterpret_cast<const f32x4*>(lse2 + rw + 4 * g);
+    const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + rw + 4 * g);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float pv = kvalid ? fexp2(fmaf(sacc[r], c2, -l2[r])) : 0.f;
+      if (causal && key > rw + 4 * g + r) pv = 0.f;
+      p[u][r] = pv;
+      ds[u][r] = pv * (dpacc[r] - dl[r]);
+    }
+  }
+  bf16x8 ph, pl, dsh, dsl;
+  split8<1>(p[0], p[1], ph, pl);
+  split8<1>(ds[0], ds[1], dsh, dsl);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    dv[dt] = mfma16x3(trf(Ohi, row0, off.tr[dt]), trf(Olo, row0, off.tr[dt]), ph, pl, dv[dt]);
+    dk[dt] = mfma16x3(trf(Qhi, row0, off.tr[dt]), trf(Qlo, row0, off.tr[dt]), dsh, dsl, dk[dt]);
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_bwd_dq_f32x3(
+    const float* __restrict__ qkv, int64_t ld_qkv, int D, int H, int N, float scale, const float* __restrict__ o,
+    int64_t ld_o, const float* __restrict__ dout, int64_t ld_do, const float* __restrict__ lse,
+    float* __restrict__ delta_out, float* __restrict__ dqkv, int64_t ld_dqkv, int causal) {
+  constexpr int NT2 = F32X3<NT>::NT2, ROWS = F32X3<NT>::ROWS, IMG = F32X3<NT>::IMG;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Khi = smem;
+  char* Klo = smem + IMG;
+  char* Vhi = smem + 2 * IMG;
+  char* Vlo = smem + 3 * IMG;
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const float* dob = dout + (int64_t)b * N * ld_do + h * 64;
+  const float* ob = o + (int64_t)b * N * ld_o + h * 64;
+  x3_load2<ROWS>(Khi, Klo, base + D, ld_qkv, Vhi, Vlo, base + 2 * D, ld_qkv, N);
+  const AtOffsets off(lane);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  for (int qt = wave; qt < NT; qt += AT_WAVES) {
+    const int q = qt * 16 + (lane & 15), qc = min(q, N - 1);
+    bf16x8 qh[2], ql[2], oh[2], ol[2];
+    float dl = 0.f;
+    {
+      f32x4 x[4], df[4];
+      x3_row(base + (int64_t)qc * ld_qkv, g, qh, ql, x);
+      x3_row(dob + (int64_t)qc * ld_do, g, oh, ol, df);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {  // delta = rowsum(dO * O) on the unsplit f32 values
+        const f32x4 ov = *reinterpret_cast<const f32x4*>(ob + (int64_t)qc * ld_o + (j >> 1) * 32 + g * 8 + (j & 1) * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dl = fmaf(df[j][e], ov[e], dl);
+      }
+    }
+    dl += __shfl_xor(dl, 16, 64);
+    dl += __shfl_xor(dl, 32, 64);
+    if (q < N && g == 0) delta_out[(int64_t)bh * N + q] = dl;
+    const float l2 = lse[(int64_t)bh * N + qc] * LOG2E;
+    f32x4 dq[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int kp = 0; kp < NT2; ++kp)  // edge, wave-uniform: only the last pair holds padded keys
+      x3_dq_step(Khi, Klo, Vhi, Vlo, kp * 32, N, (kp + 1) * 32 > N, off, g, qh, ql, oh, ol, c2, l2, dl, q, causal, dq);
+    if (q < N) x3_store_row(dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64, dq, scale, g);
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS_DKV) void attn_bwd_dkv_f32x3(
+    const float* __restrict__ qkv, int64_t ld_qkv, int D, int H, int N, float scale, const float* __restrict__ dout,
+    int64_t ld_do, const float* __restrict__ lse, const float* __restrict__ delta_in, float* __restrict__ dqkv,
+    int64_t ld_dqkv, int causal) {
+  constexpr int NT2 = F32X3<NT>::NT2, ROWS = F32X3<NT>::ROWS, IMG = F32X3<NT>::IMG;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Qhi = smem;
+  char* Qlo = smem + IMG;
+  char* Ohi = smem + 2 * IMG;  // dO
+  char* Olo = smem + 3 * IMG;
+  float* lse2 = reinterpret_cast<float*>(smem + 4 * IMG);  // lse * log2(e) per query (+inf past N)
+  float* delta = lse2 + ROWS;
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  x3_load2<ROWS>(Qhi, Qlo, base, ld_qkv, Ohi, Olo, dout + (int64_t)b * N * ld_do + h * 64, ld_do, N);
+  for (int i = threadIdx.x; i < ROWS; i += AT_THREADS) {
+    lse2[i] = i < N ? lse[(int64_t)bh * N + i] * LOG2E : INFINITY;
+    delta[i] = i < N ? delta_in[(int64_t)bh * N + i] : 0.f;
+  }
+  const AtOffsets off(lane);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  for (int kt = wave; kt < NT; kt += AT_WAVES) {
+    const int key = kt * 16 + (lane & 15), kc = min(key, N - 1);
+    const bool kvalid = key < N;
+    bf16x8 kh[2], kl[2], vh[2], vl[2];
+    {
+      f32x4 x[4];
+      x3_row(base + (int64_t)kc * ld_qkv + D, g, kh, kl, x);
+      x3_row(base + (int64_t)kc * ld_qkv + 2 * D, g, vh, vl, x);
+    }
+    f32x4 dk[4], dv[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = dk[dt]; }
+#pragma unroll 1
+    for (int qp = 0; qp < NT2; ++qp)
+      x3_dkv_step(Qhi, Qlo, Ohi, Olo, lse2, delta, qp * 32, off, g, kh, kl, vh, vl, c2, kvalid, key, causal, dk, dv);
+    if (kvalid) {
+      float* row = dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64;
+      x3_store_row(row + D, dk, scale, g);
+      x3_store_row(row + 2 * D, dv, 1.f, g);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // generic (f32 compute, f32 or bf16 storage) path: 4 lanes per query / key,
 // each owning 16 of the 64 head dims; keys / queries streamed through LDS.
 // ---------------------------------------------------------------------------
@@ -2309,6 +2630,26 @@ struct F32Res {  // resident f32 kernels: two head images of NT * 16 rows (+ lse
   }
 };
 
+template <int NT>
+void F32X3<NT>::attrs() {
+  static bool attr = false;
+  if (attr) return;
+  raise_lds(attn_fwd_f32x3<NT, false>, LDS);
+  raise_lds(attn_fwd_f32x3<NT, true>, LDS);
+  raise_lds(attn_bwd_dq_f32x3<NT>, LDS);
+  raise_lds(attn_bwd_dkv_f32x3<NT>, LDS_DKV);
+  attr = true;
+}
+// fp32 arithmetic of the resident f32 kernels (vit_sdpa_f32_precision): 0 = v_mfma_f32_16x16x4_f32, 1 = bf16x3
+// (the attn_*_f32x3 kernels).  Process-wide, read at launch time; the initial value comes from VIT_F32_ATTENTION
+// (highest | high, default highest).  g_f32_split_count: vit_sdpa_fwd / vit_sdpa_bwd calls that took them.
+static int f32_attention_env() {
+  const char* s = getenv("VIT_F32_ATTENTION");
+  return s && !strcmp(s, "high") ? 1 : 0;
+}
+static int g_f32_split = f32_attention_env();
+static int g_f32_split_count = 0;
+
 // ---------------------------------------------------------------------------
 template <int NT>
 static int fwd_mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal, void* o,
@@ -2349,6 +2690,36 @@ static int bwd_f32mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int
                      ld_qkv, D, H, N, scale, (const float*)dout, ld_do, lse, (const float*)delta, (float*)dqkv, ld_dqkv,
                      causal);
   VIT_CHECK_LAUNCH();
+  return 0;
+}
+template <int NT>
+static int fwd_f32x3(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal, void* o,
+                     int64_t ld_o, float* lse, hipStream_t s) {
+  F32X3<NT>::attrs();
+  if (causal)
+    hipLaunchKernelGGL((attn_fwd_f32x3<NT, true>), dim3(B * H), dim3(AT_THREADS), F32X3<NT>::LDS, s, (const float*)qkv,
+                       ld_qkv, D, H, N, scale, (float*)o, ld_o, lse);
+  else
+    hipLaunchKernelGGL((attn_fwd_f32x3<NT, false>), dim3(B * H), dim3(AT_THREADS), F32X3<NT>::LDS, s, (const float*)qkv,
+                       ld_qkv, D, H, N, scale, (float*)o, ld_o, lse);
+  VIT_CHECK_LAUNCH();
+  ++g_f32_split_count;
+  return 0;
+}
+template <int NT>
+static int bwd_f32x3(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal,
+                     const void* o, int64_t ld_o, const void* dout, int64_t ld_do, const float* lse, float* delta,
+                     void* dqkv, int64_t ld_dqkv, hipStream_t s) {
+  F32X3<NT>::attrs();
+  hipLaunchKernelGGL((attn_bwd_dq_f32x3<NT>), dim3(B * H), dim3(AT_THREADS), F32X3<NT>::LDS, s, (const float*)qkv,
+                     ld_qkv, D, H, N, scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta, (float*)dqkv,
+                     ld_dqkv, causal);
+  VIT_CHECK_LAUNCH();
+  hipLaunchKernelGGL((attn_bwd_dkv_f32x3<NT>), dim3(B * H), dim3(AT_THREADS), F32X3<NT>::LDS_DKV, s, (const float*)qkv,
+                     ld_qkv, D, H, N, scale, (const float*)dout, ld_do, lse, (const float*)delta, (float*)dqkv, ld_dqkv,
+                     causal);
+  VIT_CHECK_LAUNCH();
+  ++g_f32_split_count;
   return 0;
 }
 // The generic backward: any token count and alignment, causal or not.
@@ -2659,6 +3030,21 @@ int vit_sdpa_long_f32_count(int reset) {
   return c;
 }
 
+// fp32 arithmetic of the resident f32 kernels (f32, N <= 288, aligned rows, causal or not): 0 = f32 MFMA,
+// 1 = bf16x3, -1 keeps; other values are ignored.  Returns the previous setting.  "At most bf16x3": the streamed
+// f32 kernels past 288 tokens, the generic and the one-query kernels and vit_sdpa_fwd_cls stay exact f32.
+int vit_sdpa_f32_precision(int mode) {
+  const int prev = g_f32_split;
+  if (mode == 0 || mode == 1) g_f32_split = mode;
+  return prev;
+}
+// Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the bf16x3 kernels; reset != 0 zeroes it.
+int vit_sdpa_f32_split_count(int reset) {
+  const int c = g_f32_split_count;
+  if (reset) g_f32_split_count = 0;
+  return c;
+}
+
 // F.scaled_dot_product_attention(q, k, v) (no dropout) for head_dim 64; causal = 1
 // masks key > query (OpenAI CLIP text tower attn_mask, additive -inf above the diagonal).
 // qkv: [B*N, ld_qkv] with q at column h*64, k at D + h*64, v at 2D + h*64.
@@ -2692,6 +3078,11 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
       }
       break;
     case AP_RESIDENT_F32:
+      if (g_f32_split) switch ((N + 15) / 16) {
+#define CASE(n) case n: return fwd_f32x3<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
+        NT_CASES(CASE)
+#undef CASE
+      }
       switch ((N + 15) / 16) {
 #define CASE(n) case n: return fwd_f32mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
         NT_CASES(CASE)
@@ -2968,6 +3359,14 @@ int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
       VIT_CHECK_LAUNCH();
       return 0;
     case AP_RESIDENT_F32:
+      if (g_f32_split) {
+        switch ((N + 15) / 16) {
+#define CASE(n) case n: rc = bwd_f32x3<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv, s); break;
+          NT_CASES(CASE)
+#undef CASE
+        }
+        break;
+      }
       switch ((N + 15) / 16) {
 #define CASE(n) case n: rc = bwd_f32mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv, s); break;
         NT_CASES(CASE)

@@ -25,6 +25,7 @@
 
 #include "gemm_lds.hpp"
 #include "gemm_epi.hpp"
+#include "bf16_split.hpp"
 
 // act / act' of one pre-activation `pr`, already rounded to the storage type (the value a stored-pre design
 // would have differentiated) -- the per-element core of every epilogue form.  EXACT: the erf form of the

@@ -96,32 +96,8 @@ __device__ __forceinline__ f32x4 frag(uint32_t img, int s, int h, int lane) {
   }
 }
 
-// SPLIT = 1: two f32 -> packed bf16 pair (RNE), and the 8 values of a lane's fragment (x0: k half 0, x1: k half
-// 1) -> hi / lo bf16x8 operands, element j = 4h + t
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float sub_f32(float a, float b) {  // one v_sub_f32, never SLP-packed
-  float r;
-  asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, bf16x8& hi, bf16x8& lo) {
-  const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-  u32x4_ H, L;
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const float a = x[2 * p], b = x[2 * p + 1];
-    H[p] = cvt_pk_bf16(a, b);
-    const float ah = __uint_as_float(H[p] << 16), bh = __uint_as_float(H[p] & 0xffff0000u);
-    L[p] = cvt_pk_bf16(sub_f32(a, ah), sub_f32(b, bh));
-  }
-  hi = __builtin_bit_cast(bf16x8, H);
-  lo = __builtin_bit_cast(bf16x8, L);
-}
+// SPLIT = 1: split8 (bf16_split.hpp) turns the 8 values of a lane's fragment (x0: k half 0, x1: k half 1) into
+// hi / lo bf16x8 operands, element j = 4h + t
 
 // acc += P(i0.., rb + kb*BK ..) Q(j0.., ...)^T over k-steps [kb, ke) of one tile (the LDS ring restarts
 // per call; a __syncthreads before the first issue protects a previous call's reads)

@@ -495,6 +495,8 @@ class CLIP(nn.Module):
         key = (text.data_ptr(), text._version, tuple(text.shape), k, self.compute_dtype, self.attention_fp8,
                self.attention_fp8_long, tuple((p.data_ptr(), p._version) for p in params),
                ops.get_float32_matmul_precision())
+        if ops.get_float32_attention_precision() != "highest":  # the default mode keeps the key it always had
+            key += ("attention-" + ops.get_float32_attention_precision(),)
         if self.cache_frozen_text and self._text_cache is not None and self._text_cache[0] == key:
             return self._text_cache[1], k
         S, Lq = text.shape

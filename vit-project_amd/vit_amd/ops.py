@@ -882,6 +882,34 @@ def get_float32_matmul_precision() -> str:
     return _F32_MATMUL[L.lib().vit_gemm_f32_precision(-1)]
 
 
+_F32_ATTENTION = ("highest", "high")  # vit_sdpa_f32_precision 0 / 1
+
+
+def set_float32_attention_precision(precision):
+    """The arithmetic of the resident fp32 attention kernels (f32 operands, up to 288 tokens, head_dim 64,
+    aligned rows, causal or not):
+
+    - ``"highest"`` (the default): ``v_mfma_f32_16x16x4_f32``, exact f32 products;
+    - ``"high"``: every matrix product of the forward (``QK^T``, ``PV``) and the backward (``S``, ``dP``, ``dQ``,
+      ``dK``, ``dV``) as three bf16 MFMA products of ``hi + lo`` operands with f32 accumulation, the rule of
+      :func:`set_float32_matmul_precision`.  The softmax, ``delta``, ``lse``, the scale factors and the stores
+      stay f32.  At most bf16x3: the streamed f32 kernels past 288 tokens, the generic and the one-query kernels
+      and the class-token-only forward stay exact f32.  An infinite operand gives NaN.
+
+    Independent of the GEMM switch: ``set_float32_matmul_precision("high")`` leaves attention exact, and this
+    leaves the GEMMs exact.  Process-wide and read when a kernel is launched; cached frozen-prefix tensors carry the
+    mode in their keys when it is ``"high"``.  ``VIT_F32_ATTENTION=high`` sets the initial value when the library
+    loads (spawned workers inherit it).  Host-only: works without a GPU."""
+    if precision not in _F32_ATTENTION:
+        raise ValueError(f'float32 attention precision must be "highest" or "high", got {precision!r}')
+    L.lib().vit_sdpa_f32_precision(_F32_ATTENTION.index(precision))
+
+
+def get_float32_attention_precision() -> str:
+    """``"highest"`` or ``"high"``: see :func:`set_float32_attention_precision`."""
+    return _F32_ATTENTION[L.lib().vit_sdpa_f32_precision(-1)]
+
+
 def gemm(P, p_layout, Q, q_layout, M, N, R, out=None, out_dtype=torch.float32, bias=None):
     """Raw C[i][j] = sum_r P(i,r) Q(j,r) (+bias[j]); layouts L.LAY_RC (r contiguous) / L.LAY_CR."""
     assert P.dtype == Q.dtype and P.stride(-1) == 1 and Q.stride(-1) == 1

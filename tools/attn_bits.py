@@ -6,9 +6,11 @@
 One JSON line per seeded case (inputs as tests/test_gpu_attention_long.py::_case, B = 2, H = 3): SHA-1 of o, lse,
 dqkv, delta_ws and dbias; for bf16 also of the [B][3D] bias partials that partial-only mode (dbias == NULL) leaves.
 The backward runs from the library's own o and lse.  Cases: the bf16 resident two-kernel backward (N > 224, and
-vit_sdpa_bwd_variant(2) below that), the f32 resident kernels, the streamed kernels of both dtypes, and the fused
-bf16 backward as a control.  First come the resident fp8 forward's o and lse (N = 77 causal, 197, 257, 320, both
-dtypes; ``--fp8-only`` stops after them).
+vit_sdpa_bwd_variant(2) below that), the f32 resident kernels, the streamed kernels of both dtypes, the fused
+bf16 backward as a control, and last the f32 resident kernels in the "high" mode (vit_sdpa_f32_precision(1), the
+bf16x3 kernels; N = 1, 17, 33, 77 causal, 257, 288: one tile, an edge inside a pair's second tile, an odd tile
+count, the mask, one workgroup per CU, every tile full).  First come the resident fp8 forward's o and lse (N = 77
+causal, 197, 257, 320, both dtypes; ``--fp8-only`` stops after them).
 """
 import hashlib
 import json
@@ -33,6 +35,8 @@ CASES = ([("bf16 resident two-kernel", BF16, n, False, -1) for n in (240, 257, 2
          [("f32 resident", F32, n, c, -1) for n, c in ((50, False), (77, True), (197, False), (257, False), (288, False))] +
          [("streamed", dt, n, False, -1) for dt in (BF16, F32) for n in (289, 320, 577)] +
          [("bf16 fused (control)", BF16, 197, False, -1)])
+# f32 resident under vit_sdpa_f32_precision(1): (N, causal)
+HIGH_CASES = ((1, False), (17, False), (33, False), (77, True), (257, False), (288, False))
 # the resident fp8 forward (o and lse only), both dtypes; --fp8-only runs these alone
 FP8_CASES = ((77, True), (197, False), (257, False), (320, False))
 
@@ -100,6 +104,17 @@ def main():
             lib.vit_sdpa_bwd_variant(-1)
         print(json.dumps({"kernels": kernels, "dtype": "bf16" if dtype == BF16 else "f32", "N": N, "causal": causal,
                           "bwd_variant": variant, **r}), flush=True)
+    for N, causal in HIGH_CASES:
+        lib.vit_sdpa_f32_precision(1)
+        try:
+            lib.vit_sdpa_f32_split_count(1)  # zero it
+            r = run(F32, N, causal)
+            took = lib.vit_sdpa_f32_split_count(1)
+        finally:
+            lib.vit_sdpa_f32_precision(0)
+        assert took == 2, ("the forward and the backward must both take the bf16x3 kernels", N, took)
+        print(json.dumps({"kernels": "f32 resident high", "dtype": "f32", "N": N, "causal": causal,
+                          "bwd_variant": -1, **r}), flush=True)
 
 
 if __name__ == "__main__":

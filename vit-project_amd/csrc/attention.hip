@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include <initializer_list>
+#include <type_traits>
 
 #include "bf16_split.hpp"
 #include "common.hpp"
@@ -108,6 +109,38 @@ __device__ __forceinline__ bf16x8 trf(const char* img, int row0, int off) {
   const char* b = img + row0 * 128 + off;
   return cat4(lds_read_tr(b), lds_read_tr(b + 16 * 128));
 }
+// Operand policies of the resident tile steps (at_dq_step, at_dkv_step): how a head image is named, what an MFMA
+// operand is, how an f32 accumulator pair becomes one, and how a product is issued.
+struct AtBf16 {  // bf16 operands, one product
+  static constexpr bool SPLIT = false;
+  using Img = const char*;
+  using Frag = bf16x8;
+  static __device__ __forceinline__ Frag row(Img m, int row0, int off) { return rowf(m, row0, off); }
+  static __device__ __forceinline__ Frag tr(Img m, int row0, int off) { return trf(m, row0, off); }
+  static __device__ __forceinline__ Frag pack(const f32x4& a, const f32x4& b) { return pack8(a, b); }
+  static __device__ __forceinline__ f32x4 mma(const Frag& a, const Frag& b, f32x4 c) { return mfma16(a, b, c); }
+};
+struct AtBf16x3 {  // f32 operands as hi / lo bf16 splits (bf16_split.hpp), three products: hi lo, lo hi, hi hi
+  static constexpr bool SPLIT = true;
+  struct Img { const char *hi, *lo; };
+  struct Frag { bf16x8 hi, lo; };
+  static __device__ __forceinline__ Frag row(Img m, int row0, int off) {
+    return {rowf(m.hi, row0, off), rowf(m.lo, row0, off)};
+  }
+  static __device__ __forceinline__ Frag tr(Img m, int row0, int off) {
+    return {trf(m.hi, row0, off), trf(m.lo, row0, off)};
+  }
+  static __device__ __forceinline__ Frag pack(const f32x4& a, const f32x4& b) {
+    Frag f;
+    split8<1>(a, b, f.hi, f.lo);
+    return f;
+  }
+  static __device__ __forceinline__ f32x4 mma(const Frag& a, const Frag& b, f32x4 c) {
+    c = mfma16(a.hi, b.lo, c);
+    c = mfma16(a.lo, b.hi, c);
+    return mfma16(a.hi, b.hi, c);
+  }
+};
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // Diagnostic phase stamps (tools/attn_stamps.py): a separate template instance, launched only
@@ -874,20 +907,24 @@ __device__ __forceinline__ void at_store_dkv(bf16* row, int D, const f32x4 (&dk)
     *reinterpret_cast<bf16x4*>(row + 2 * D + dt * 16 + 4 * g) = vv;
   }
 }
+// The two resident backward steps, stated once for both operand policies P (AtBf16: the bf16 kernels, resident and
+// streamed; AtBf16x3: the f32 "high" kernels).
 // dq half, one pair of key tiles (32 keys): S^T and dP^T of the lane's query against the K / V images,
 // p = exp2(c2 S - l2) (0 on keys >= N and, causal, on keys > q), dS = p (dP - dl), dQ += dS K.
 // edge: the caller's wave-uniform "this pair (chunk) may hold keys >= N".
-__device__ __forceinline__ void at_dq_step(const char* Kimg, const char* Vimg, int row0, int key0, int N, bool edge,
-                                           const AtOffsets& off, int g, const bf16x8 (&qf)[2], const bf16x8 (&of)[2],
-                                           float c2, float l2, float dl, int q, int causal, f32x4 (&dq)[4]) {
+template <typename P = AtBf16>
+__device__ __forceinline__ void at_dq_step(typename P::Img Kimg, typename P::Img Vimg, int row0, int key0, int N,
+                                           bool edge, const AtOffsets& off, int g, const typename P::Frag (&qf)[2],
+                                           const typename P::Frag (&of)[2], float c2, float l2, float dl, int q,
+                                           int causal, f32x4 (&dq)[4]) {
   f32x4 ds[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      sacc = mfma16(rowf(Kimg, row0 + u * 16, off.row[kk]), qf[kk], sacc);
-      dpacc = mfma16(rowf(Vimg, row0 + u * 16, off.row[kk]), of[kk], dpacc);
+      sacc = P::mma(P::row(Kimg, row0 + u * 16, off.row[kk]), qf[kk], sacc);
+      dpacc = P::mma(P::row(Vimg, row0 + u * 16, off.row[kk]), of[kk], dpacc);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -897,25 +934,28 @@ __device__ __forceinline__ void at_dq_step(const char* Kimg, const char* Vimg, i
       if (causal && key > q) pv = 0.f;
       ds[u][r] = pv * (dpacc[r] - dl);
     }
+    // split operands: bound fragment hoisting -- both tiles' 16 fragments spill at 128 VGPRs
+    if constexpr (P::SPLIT) if (u == 0) __builtin_amdgcn_sched_barrier(0);
   }
-  const bf16x8 dsf = pack8(ds[0], ds[1]);
+  const typename P::Frag dsf = P::pack(ds[0], ds[1]);
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma16(trf(Kimg, row0, off.tr[dt]), dsf, dq[dt]);
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = P::mma(P::tr(Kimg, row0, off.tr[dt]), dsf, dq[dt]);
 }
 // dkv half, one pair of query tiles (32 queries): S and dP of the lane's key against the Q / dO images,
 // row constants from the lse * log2(e) / delta strips (indexed like the image), dV += P^T dO, dK += dS^T Q.
-__device__ __forceinline__ void at_dkv_step(const char* Qimg, const char* Oimg, const float* lse2, const float* delta,
-                                            int row0, int q0, const AtOffsets& off, int g, const bf16x8 (&kf)[2],
-                                            const bf16x8 (&vf)[2], float c2, bool kvalid, int key, int causal,
-                                            f32x4 (&dk)[4], f32x4 (&dv)[4]) {
+template <typename P = AtBf16>
+__device__ __forceinline__ void at_dkv_step(typename P::Img Qimg, typename P::Img Oimg, const float* lse2,
+                                            const float* delta, int row0, int q0, const AtOffsets& off, int g,
+                                            const typename P::Frag (&kf)[2], const typename P::Frag (&vf)[2], float c2,
+                                            bool kvalid, int key, int causal, f32x4 (&dk)[4], f32x4 (&dv)[4]) {
   f32x4 p[2], ds[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      sacc = mfma16(rowf(Qimg, row0 + u * 16, off.row[kk]), kf[kk], sacc);
-      dpacc = mfma16(rowf(Oimg, row0 + u * 16, off.row[kk]), vf[kk], dpacc);
+      sacc = P::mma(P::row(Qimg, row0 + u * 16, off.row[kk]), kf[kk], sacc);
+      dpacc = P::mma(P::row(Oimg, row0 + u * 16, off.row[kk]), vf[kk], dpacc);
     }
     const f32x4 l2 = *reinterpret_cast<const f32x4*>(lse2 + row0 + u * 16 + 4 * g);
     const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + row0 + u * 16 + 4 * g);
@@ -927,11 +967,11 @@ __device__ __forceinline__ void at_dkv_step(const char* Qimg, const char* Oimg, 
       ds[u][r] = pv * (dpacc[r] - dl[r]);
     }
   }
-  const bf16x8 pf = pack8(p[0], p[1]), dsf = pack8(ds[0], ds[1]);
+  const typename P::Frag pf = P::pack(p[0], p[1]), dsf = P::pack(ds[0], ds[1]);
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
-    dv[dt] = mfma16(trf(Oimg, row0, off.tr[dt]), pf, dv[dt]);
-    dk[dt] = mfma16(trf(Qimg, row0, off.tr[dt]), dsf, dk[dt]);
+    dv[dt] = P::mma(P::tr(Oimg, row0, off.tr[dt]), pf, dv[dt]);
+    dk[dt] = P::mma(P::tr(Qimg, row0, off.tr[dt]), dsf, dk[dt]);
   }
 }
 
@@ -1619,7 +1659,9 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_f32mfma(const float* __restr
 // the AtOffsets swizzle, 16-row tiles in 32-row pairs) fed from f32 global memory.  Every f32 value x is split
 // with the GEMM's helper (bf16_split.hpp) into hi = bf16_rne(x), lo = bf16_rne(x - hi), and every matrix product
 // runs as  acc += A_hi B_lo;  acc += A_lo B_hi;  acc += A_hi B_hi  on v_mfma_f32_16x16x32_bf16 (A, B: the MFMA's
-// operands; lo lo is dropped).
+// operands; lo lo is dropped).  That is the operand policy AtBf16x3: the backward kernels call the bf16 kernels' own
+// at_dq_step / at_dkv_step with it, the forward restates attn_fwd_mfma's query-tile body on it (a shared body or
+// softmax block reschedules every attn_fwd_mfma instance).
 //   head images : loaded as f32, split once while the LDS image is written -- a hi and a lo image per matrix in
 //                 the bf16 layout, 4 x ROWS x 128 B, the bytes of the two f32 images they replace
 //   row operands: the wave's own rows (q; q and dO; k and v) from global memory as f32, split once per tile
@@ -1636,15 +1678,8 @@ struct F32X3 {
   // waves per SIMD (8 waves per workgroup on 4 SIMDs): 4 = two workgroups per CU (128 VGPRs), 2 = one (256)
   static constexpr int WPS = 2 * LDS <= CU_LDS ? 4 : 2, WPS_DKV = 2 * LDS_DKV <= CU_LDS ? 4 : 2;
   static_assert(LDS_DKV <= CU_LDS, "one workgroup per CU");
-  static void attrs();
 };
 
-__device__ __forceinline__ f32x4 mfma16x3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl,
-                                          f32x4 c) {
-  c = mfma16(ah, bl, c);
-  c = mfma16(al, bh, c);
-  return mfma16(ah, bh, c);
-}
 // Rows [0, N) of two f32 head slices -> a hi and a lo bf16 image each (at_off layout, rows >= N zero).
 template <int ROWS>
 __device__ __forceinline__ void x3_load2(char* ahi, char* alo, const float* sa, int64_t lda, char* bhi, char* blo,
@@ -1668,12 +1703,12 @@ __device__ __forceinline__ void x3_load2(char* ahi, char* alo, const float* sa, 
   }
 }
 // The lane's row fragments (head dims kk * 32 + 8g .. + 8) of the f32 row at p, split; x: the f32 values.
-__device__ __forceinline__ void x3_row(const float* p, int g, bf16x8 (&hi)[2], bf16x8 (&lo)[2], f32x4 (&x)[4]) {
+__device__ __forceinline__ void x3_row(const float* p, int g, AtBf16x3::Frag (&f)[2], f32x4 (&x)[4]) {
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
     x[2 * kk] = *reinterpret_cast<const f32x4*>(p + kk * 32 + g * 8);
     x[2 * kk + 1] = *reinterpret_cast<const f32x4*>(p + kk * 32 + g * 8 + 4);
-    split8<1>(x[2 * kk], x[2 * kk + 1], hi[kk], lo[kk]);
+    f[kk] = AtBf16x3::pack(x[2 * kk], x[2 * kk + 1]);
   }
 }
 // x[dt] * mul = columns dt * 16 + 4g .. + 4 of the lane's row at p (the accumulator layout of the bf16 kernels)
@@ -1688,12 +1723,11 @@ __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_fwd_f32x3(con
                                                                              int64_t ld_qkv, int D, int H, int N,
                                                                              float scale, float* __restrict__ o,
                                                                              int64_t ld_o, float* __restrict__ lse) {
+  using X = AtBf16x3;
   constexpr int NT2 = F32X3<NT>::NT2, ROWS = F32X3<NT>::ROWS, IMG = F32X3<NT>::IMG;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Khi = smem;
-  char* Klo = smem + IMG;
-  char* Vhi = smem + 2 * IMG;
-  char* Vlo = smem + 3 * IMG;
+  char *Khi = smem, *Klo = smem + IMG, *Vhi = smem + 2 * IMG, *Vlo = smem + 3 * IMG;
+  const X::Img Kimg = {Khi, Klo}, Vimg = {Vhi, Vlo};
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
   const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
@@ -1703,18 +1737,17 @@ __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_fwd_f32x3(con
   const float c2 = scale * LOG2E;
   for (int qt = wave; qt < NT; qt += AT_WAVES) {
     const int q = qt * 16 + (lane & 15);
-    bf16x8 qh[2], ql[2];
+    X::Frag qf[2];
     {
       f32x4 x[4];
-      x3_row(base + (int64_t)min(q, N - 1) * ld_qkv, g, qh, ql, x);
+      x3_row(base + (int64_t)min(q, N - 1) * ld_qkv, g, qf, x);
     }
     f32x4 s[NT];
 #pragma unroll
     for (int kt = 0; kt < NT; ++kt) {
       s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-        s[kt] = mfma16x3(rowf(Khi, kt * 16, off.row[kk]), rowf(Klo, kt * 16, off.row[kk]), qh[kk], ql[kk], s[kt]);
+      for (int kk = 0; kk < 2; ++kk) s[kt] = X::mma(X::row(Kimg, kt * 16, off.row[kk]), qf[kk], s[kt]);
       if (kt % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // bound K-fragment hoisting (VGPRs)
     }
     // keys >= N exist only in the last tile
@@ -1751,11 +1784,9 @@ __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_fwd_f32x3(con
 #pragma unroll
     for (int ks = 0; ks < NT2; ++ks) {
       const f32x4 hi = (2 * ks + 1 < NT) ? s[2 * ks + 1 < NT ? 2 * ks + 1 : 0] : f32x4{0.f, 0.f, 0.f, 0.f};
-      bf16x8 ph, pl;
-      split8<1>(s[2 * ks], hi, ph, pl);
+      const X::Frag pf = X::pack(s[2 * ks], hi);
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-        oacc[dt] = mfma16x3(trf(Vhi, ks * 32, off.tr[dt]), trf(Vlo, ks * 32, off.tr[dt]), ph, pl, oacc[dt]);
+      for (int dt = 0; dt < 4; ++dt) oacc[dt] = X::mma(X::tr(Vimg, ks * 32, off.tr[dt]), pf, oacc[dt]);
       if (ks % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // bound V-fragment hoisting (VGPRs)
     }
     if (q < N) {
@@ -1765,84 +1796,16 @@ __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_fwd_f32x3(con
   }
 }
 
-// dq half, one pair of key tiles: at_dq_step on split operands.
-__device__ __forceinline__ void x3_dq_step(const char* Khi, const char* Klo, const char* Vhi, const char* Vlo, int row0,
-                                           int N, bool edge, const AtOffsets& off, int g, const bf16x8 (&qh)[2],
-                                           const bf16x8 (&ql)[2], const bf16x8 (&oh)[2], const bf16x8 (&ol)[2], float c2,
-                                           float l2, float dl, int q, int causal, f32x4 (&dq)[4]) {
-  f32x4 ds[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
-    const int rw = row0 + u * 16;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      sacc = mfma16x3(rowf(Khi, rw, off.row[kk]), rowf(Klo, rw, off.row[kk]), qh[kk], ql[kk], sacc);
-      dpacc = mfma16x3(rowf(Vhi, rw, off.row[kk]), rowf(Vlo, rw, off.row[kk]), oh[kk], ol[kk], dpacc);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int key = rw + 4 * g + r;
-      float pv = fexp2(fmaf(sacc[r], c2, -l2));
-      if (edge && key >= N) pv = 0.f;
-      if (causal && key > q) pv = 0.f;
-      ds[u][r] = pv * (dpacc[r] - dl);
-    }
-    if (u == 0) __builtin_amdgcn_sched_barrier(0);  // bound fragment hoisting: both tiles' 16 fragments spill at 128 VGPRs
-  }
-  bf16x8 dsh, dsl;
-  split8<1>(ds[0], ds[1], dsh, dsl);
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-    dq[dt] = mfma16x3(trf(Khi, row0, off.tr[dt]), trf(Klo, row0, off.tr[dt]), dsh, dsl, dq[dt]);
-}
-// dkv half, one pair of query tiles: at_dkv_step on split operands.
-__device__ __forceinline__ void x3_dkv_step(const char* Qhi, const char* Qlo, const char* Ohi, const char* Olo,
-                                            const float* lse2, const float* delta, int row0, const AtOffsets& off, int g,
-                                            const bf16x8 (&kh)[2], const bf16x8 (&kl)[2], const bf16x8 (&vh)[2],
-                                            const bf16x8 (&vl)[2], float c2, bool kvalid, int key, int causal,
-                                            f32x4 (&dk)[4], f32x4 (&dv)[4]) {
-  f32x4 p[2], ds[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
-    const int rw = row0 + u * 16;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      sacc = mfma16x3(rowf(Qhi, rw, off.row[kk]), rowf(Qlo, rw, off.row[kk]), kh[kk], kl[kk], sacc);
-      dpacc = mfma16x3(rowf(Ohi, rw, off.row[kk]), rowf(Olo, rw, off.row[kk]), vh[kk], vl[kk], dpacc);
-    }
-    const f32x4 l2 = *reinterpret_cast<const f32x4*>(lse2 + rw + 4 * g);
-    const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + rw + 4 * g);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float pv = kvalid ? fexp2(fmaf(sacc[r], c2, -l2[r])) : 0.f;
-      if (causal && key > rw + 4 * g + r) pv = 0.f;
-      p[u][r] = pv;
-      ds[u][r] = pv * (dpacc[r] - dl[r]);
-    }
-  }
-  bf16x8 ph, pl, dsh, dsl;
-  split8<1>(p[0], p[1], ph, pl);
-  split8<1>(ds[0], ds[1], dsh, dsl);
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    dv[dt] = mfma16x3(trf(Ohi, row0, off.tr[dt]), trf(Olo, row0, off.tr[dt]), ph, pl, dv[dt]);
-    dk[dt] = mfma16x3(trf(Qhi, row0, off.tr[dt]), trf(Qlo, row0, off.tr[dt]), dsh, dsl, dk[dt]);
-  }
-}
-
 template <int NT>
 __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_bwd_dq_f32x3(
     const float* __restrict__ qkv, int64_t ld_qkv, int D, int H, int N, float scale, const float* __restrict__ o,
     int64_t ld_o, const float* __restrict__ dout, int64_t ld_do, const float* __restrict__ lse,
     float* __restrict__ delta_out, float* __restrict__ dqkv, int64_t ld_dqkv, int causal) {
+  using X = AtBf16x3;
   constexpr int NT2 = F32X3<NT>::NT2, ROWS = F32X3<NT>::ROWS, IMG = F32X3<NT>::IMG;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Khi = smem;
-  char* Klo = smem + IMG;
-  char* Vhi = smem + 2 * IMG;
-  char* Vlo = smem + 3 * IMG;
+  char *Khi = smem, *Klo = smem + IMG, *Vhi = smem + 2 * IMG, *Vlo = smem + 3 * IMG;
+  const X::Img Kimg = {Khi, Klo}, Vimg = {Vhi, Vlo};
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
   const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
@@ -1854,12 +1817,12 @@ __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_bwd_dq_f32x3(
   const float c2 = scale * LOG2E;
   for (int qt = wave; qt < NT; qt += AT_WAVES) {
     const int q = qt * 16 + (lane & 15), qc = min(q, N - 1);
-    bf16x8 qh[2], ql[2], oh[2], ol[2];
+    X::Frag qf[2], of[2];
     float dl = 0.f;
     {
       f32x4 x[4], df[4];
-      x3_row(base + (int64_t)qc * ld_qkv, g, qh, ql, x);
-      x3_row(dob + (int64_t)qc * ld_do, g, oh, ol, df);
+      x3_row(base + (int64_t)qc * ld_qkv, g, qf, x);
+      x3_row(dob + (int64_t)qc * ld_do, g, of, df);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {  // delta = rowsum(dO * O) on the unsplit f32 values
         const f32x4 ov = *reinterpret_cast<const f32x4*>(ob + (int64_t)qc * ld_o + (j >> 1) * 32 + g * 8 + (j & 1) * 4);
@@ -1876,7 +1839,7 @@ __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_bwd_dq_f32x3(
     for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
     for (int kp = 0; kp < NT2; ++kp)  // edge, wave-uniform: only the last pair holds padded keys
-      x3_dq_step(Khi, Klo, Vhi, Vlo, kp * 32, N, (kp + 1) * 32 > N, off, g, qh, ql, oh, ol, c2, l2, dl, q, causal, dq);
+      at_dq_step<X>(Kimg, Vimg, kp * 32, kp * 32, N, (kp + 1) * 32 > N, off, g, qf, of, c2, l2, dl, q, causal, dq);
     if (q < N) x3_store_row(dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64, dq, scale, g);
   }
 }
@@ -1886,12 +1849,11 @@ __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS_DKV) void attn_bwd_dkv_f
     const float* __restrict__ qkv, int64_t ld_qkv, int D, int H, int N, float scale, const float* __restrict__ dout,
     int64_t ld_do, const float* __restrict__ lse, const float* __restrict__ delta_in, float* __restrict__ dqkv,
     int64_t ld_dqkv, int causal) {
+  using X = AtBf16x3;
   constexpr int NT2 = F32X3<NT>::NT2, ROWS = F32X3<NT>::ROWS, IMG = F32X3<NT>::IMG;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Qhi = smem;
-  char* Qlo = smem + IMG;
-  char* Ohi = smem + 2 * IMG;  // dO
-  char* Olo = smem + 3 * IMG;
+  char *Qhi = smem, *Qlo = smem + IMG, *Ohi = smem + 2 * IMG, *Olo = smem + 3 * IMG;  // O: dO
+  const X::Img Qimg = {Qhi, Qlo}, Oimg = {Ohi, Olo};
   float* lse2 = reinterpret_cast<float*>(smem + 4 * IMG);  // lse * log2(e) per query (+inf past N)
   float* delta = lse2 + ROWS;
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
@@ -1908,18 +1870,18 @@ __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS_DKV) void attn_bwd_dkv_f
   for (int kt = wave; kt < NT; kt += AT_WAVES) {
     const int key = kt * 16 + (lane & 15), kc = min(key, N - 1);
     const bool kvalid = key < N;
-    bf16x8 kh[2], kl[2], vh[2], vl[2];
+    X::Frag kf[2], vf[2];
     {
       f32x4 x[4];
-      x3_row(base + (int64_t)kc * ld_qkv + D, g, kh, kl, x);
-      x3_row(base + (int64_t)kc * ld_qkv + 2 * D, g, vh, vl, x);
+      x3_row(base + (int64_t)kc * ld_qkv + D, g, kf, x);
+      x3_row(base + (int64_t)kc * ld_qkv + 2 * D, g, vf, x);
     }
     f32x4 dk[4], dv[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = dk[dt]; }
 #pragma unroll 1
     for (int qp = 0; qp < NT2; ++qp)
-      x3_dkv_step(Qhi, Qlo, Ohi, Olo, lse2, delta, qp * 32, off, g, kh, kl, vh, vl, c2, kvalid, key, causal, dk, dv);
+      at_dkv_step<X>(Qimg, Oimg, lse2, delta, qp * 32, qp * 32, off, g, kf, vf, c2, kvalid, key, causal, dk, dv);
     if (kvalid) {
       float* row = dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64;
       x3_store_row(row + D, dk, scale, g);
@@ -2582,7 +2544,7 @@ static bool attn_long_stream() {
   static const int v = [] { const char* e = getenv("VIT_ATTN_LONG"); return e && *e == '0' ? 0 : 1; }();
   return v != 0;
 }
-constexpr int AT_RESIDENT_MAX = 288;  // the resident kernels' token limit (NT_CASES)
+constexpr int AT_RESIDENT_MAX = 288;  // the resident kernels' token limit (by_tiles)
 // VIT_ATTN_F32_GENERIC=1: the scalar-FMA f32 kernels instead of the f32 MFMA ones (A/B runs); f32 only
 static bool attn_f32_generic() {
   static const int v = [] { const char* e = getenv("VIT_ATTN_F32_GENERIC"); return e && *e == '1' ? 1 : 0; }();
@@ -2617,27 +2579,34 @@ static void stream_f32_attrs() {
   raise_lds(attn_bwd_dkv_stream_f32, SF_LDS_DKV);
   attr = true;
 }
+// The two resident f32 kernel families behind one interface, for fwd_f32 / bwd_f32 below: SPLIT, THREADS, the
+// dynamic LDS sizes LDS / LDS_DKV and the kernels fwd(causal), dq(), dkv().
 template <int NT>
-struct F32Res {  // resident f32 kernels: two head images of NT * 16 rows (+ lse / delta strips in dkv)
+struct F32Res {  // f32 MFMA: two head images of NT * 16 rows (+ lse / delta strips in dkv)
+  static constexpr bool SPLIT = false;
+  static constexpr int THREADS = 512;
   static constexpr int IMG = NT * 16 * 64 * 4, LDS = 2 * IMG, LDS_DKV = 2 * IMG + 2 * NT * 16 * 4;
-  static void attrs() {
-    static bool attr = false;
-    if (attr) return;
-    raise_lds(attn_fwd_f32mfma<NT>, LDS);
-    raise_lds(attn_bwd_dq_f32mfma<NT>, LDS);
-    raise_lds(attn_bwd_dkv_f32mfma<NT>, LDS_DKV);
-    attr = true;
-  }
+  static auto fwd(int) { return attn_fwd_f32mfma<NT>; }  // the mask is a kernel argument
+  static auto dq() { return attn_bwd_dq_f32mfma<NT>; }
+  static auto dkv() { return attn_bwd_dkv_f32mfma<NT>; }
 };
-
 template <int NT>
-void F32X3<NT>::attrs() {
+struct F32X3Res : F32X3<NT> {  // bf16x3: F32X3's layout constants and the kernels defined behind them
+  static constexpr bool SPLIT = true;
+  static constexpr int THREADS = AT_THREADS;
+  // the mask is a template argument, as in fwd_mfma
+  static auto fwd(int causal) { return causal ? attn_fwd_f32x3<NT, true> : attn_fwd_f32x3<NT, false>; }
+  static auto dq() { return attn_bwd_dq_f32x3<NT>; }
+  static auto dkv() { return attn_bwd_dkv_f32x3<NT>; }
+};
+template <typename F>
+static void f32_attrs() {
   static bool attr = false;
   if (attr) return;
-  raise_lds(attn_fwd_f32x3<NT, false>, LDS);
-  raise_lds(attn_fwd_f32x3<NT, true>, LDS);
-  raise_lds(attn_bwd_dq_f32x3<NT>, LDS);
-  raise_lds(attn_bwd_dkv_f32x3<NT>, LDS_DKV);
+  raise_lds(F::fwd(0), F::LDS);
+  raise_lds(F::fwd(1), F::LDS);
+  raise_lds(F::dq(), F::LDS);
+  raise_lds(F::dkv(), F::LDS_DKV);
   attr = true;
 }
 // fp32 arithmetic of the resident f32 kernels (vit_sdpa_f32_precision): 0 = v_mfma_f32_16x16x4_f32, 1 = bf16x3
@@ -2668,58 +2637,34 @@ static int fwd_mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N,
   VIT_CHECK_LAUNCH();
   return 0;
 }
-template <int NT>
-static int fwd_f32mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal, void* o,
-                       int64_t ld_o, float* lse, hipStream_t s) {
-  F32Res<NT>::attrs();
-  hipLaunchKernelGGL((attn_fwd_f32mfma<NT>), dim3(B * H), dim3(512), F32Res<NT>::LDS, s, (const float*)qkv, ld_qkv, D,
-                     H, N, scale, (float*)o, ld_o, lse, causal);
-  VIT_CHECK_LAUNCH();
-  return 0;
-}
-template <int NT>
-static int bwd_f32mfma(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal,
-                       const void* o, int64_t ld_o, const void* dout, int64_t ld_do, const float* lse, float* delta,
-                       void* dqkv, int64_t ld_dqkv, hipStream_t s) {
-  F32Res<NT>::attrs();
-  hipLaunchKernelGGL((attn_bwd_dq_f32mfma<NT>), dim3(B * H), dim3(512), F32Res<NT>::LDS, s, (const float*)qkv, ld_qkv,
-                     D, H, N, scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta, (float*)dqkv, ld_dqkv,
-                     causal);
-  VIT_CHECK_LAUNCH();
-  hipLaunchKernelGGL((attn_bwd_dkv_f32mfma<NT>), dim3(B * H), dim3(512), F32Res<NT>::LDS_DKV, s, (const float*)qkv,
-                     ld_qkv, D, H, N, scale, (const float*)dout, ld_do, lse, (const float*)delta, (float*)dqkv, ld_dqkv,
-                     causal);
-  VIT_CHECK_LAUNCH();
-  return 0;
-}
-template <int NT>
-static int fwd_f32x3(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal, void* o,
-                     int64_t ld_o, float* lse, hipStream_t s) {
-  F32X3<NT>::attrs();
-  if (causal)
-    hipLaunchKernelGGL((attn_fwd_f32x3<NT, true>), dim3(B * H), dim3(AT_THREADS), F32X3<NT>::LDS, s, (const float*)qkv,
-                       ld_qkv, D, H, N, scale, (float*)o, ld_o, lse);
+// The resident f32 forward and backward of either family F (F32Res<NT> or F32X3Res<NT>; the callers choose by
+// g_f32_split).
+template <typename F>
+static int fwd_f32(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal, void* o,
+                   int64_t ld_o, float* lse, hipStream_t s) {
+  f32_attrs<F>();
+  if constexpr (F::SPLIT)
+    hipLaunchKernelGGL(F::fwd(causal), dim3(B * H), dim3(F::THREADS), F::LDS, s, (const float*)qkv, ld_qkv, D, H, N,
+                       scale, (float*)o, ld_o, lse);
   else
-    hipLaunchKernelGGL((attn_fwd_f32x3<NT, false>), dim3(B * H), dim3(AT_THREADS), F32X3<NT>::LDS, s, (const float*)qkv,
-                       ld_qkv, D, H, N, scale, (float*)o, ld_o, lse);
+    hipLaunchKernelGGL(F::fwd(causal), dim3(B * H), dim3(F::THREADS), F::LDS, s, (const float*)qkv, ld_qkv, D, H, N,
+                       scale, (float*)o, ld_o, lse, causal);
   VIT_CHECK_LAUNCH();
-  ++g_f32_split_count;
+  g_f32_split_count += F::SPLIT;
   return 0;
 }
-template <int NT>
-static int bwd_f32x3(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal,
-                     const void* o, int64_t ld_o, const void* dout, int64_t ld_do, const float* lse, float* delta,
-                     void* dqkv, int64_t ld_dqkv, hipStream_t s) {
-  F32X3<NT>::attrs();
-  hipLaunchKernelGGL((attn_bwd_dq_f32x3<NT>), dim3(B * H), dim3(AT_THREADS), F32X3<NT>::LDS, s, (const float*)qkv,
-                     ld_qkv, D, H, N, scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta, (float*)dqkv,
-                     ld_dqkv, causal);
+template <typename F>
+static int bwd_f32(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal, const void* o,
+                   int64_t ld_o, const void* dout, int64_t ld_do, const float* lse, float* delta, void* dqkv,
+                   int64_t ld_dqkv, hipStream_t s) {
+  f32_attrs<F>();
+  hipLaunchKernelGGL(F::dq(), dim3(B * H), dim3(F::THREADS), F::LDS, s, (const float*)qkv, ld_qkv, D, H, N, scale,
+                     (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta, (float*)dqkv, ld_dqkv, causal);
   VIT_CHECK_LAUNCH();
-  hipLaunchKernelGGL((attn_bwd_dkv_f32x3<NT>), dim3(B * H), dim3(AT_THREADS), F32X3<NT>::LDS_DKV, s, (const float*)qkv,
-                     ld_qkv, D, H, N, scale, (const float*)dout, ld_do, lse, (const float*)delta, (float*)dqkv, ld_dqkv,
-                     causal);
+  hipLaunchKernelGGL(F::dkv(), dim3(B * H), dim3(F::THREADS), F::LDS_DKV, s, (const float*)qkv, ld_qkv, D, H, N, scale,
+                     (const float*)dout, ld_do, lse, (const float*)delta, (float*)dqkv, ld_dqkv, causal);
   VIT_CHECK_LAUNCH();
-  ++g_f32_split_count;
+  g_f32_split_count += F::SPLIT;
   return 0;
 }
 // The generic backward: any token count and alignment, causal or not.
@@ -2989,7 +2934,28 @@ static bool cls1_args_ok(int dtype, int B, int H, int N, int head_dim, std::init
   return true;
 }
 
-#define NT_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18)
+// f(integral_constant<int, NT>) at NT = ceil(N / 16) = 1 .. 18, the resident kernels' tile counts
+template <typename F>
+static int by_tiles(int N, F&& f) {
+  switch ((N + 15) / 16) {
+#define CASE(n) case n: return f(std::integral_constant<int, n>{});
+    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13)
+    CASE(14) CASE(15) CASE(16) CASE(17) CASE(18)
+#undef CASE
+  }
+  return (int)hipErrorInvalidValue;
+}
+// f(T{}) with T = bf16 or float, after dtype
+template <typename F>
+static int by_dtype(int dtype, F&& f) {
+  return dtype == VIT_BF16 ? f(bf16{}) : f(float{});
+}
+// a call counter, read and zeroed on request: the body of every vit_sdpa_*_count export
+static int take_count(int& counter, int reset) {
+  const int c = counter;
+  if (reset) counter = 0;
+  return c;
+}
 
 extern "C" {
 
@@ -3018,17 +2984,9 @@ int vit_sdpa_long_config(int mode) {
 }
 // Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed bf16 kernels (one per call:
 // the backward's two kernels count once); reset != 0 zeroes it after reading.
-int vit_sdpa_long_count(int reset) {
-  const int c = g_long_count;
-  if (reset) g_long_count = 0;
-  return c;
-}
+int vit_sdpa_long_count(int reset) { return take_count(g_long_count, reset); }
 // The same count for the streamed f32 kernels.
-int vit_sdpa_long_f32_count(int reset) {
-  const int c = g_long_f32_count;
-  if (reset) g_long_f32_count = 0;
-  return c;
-}
+int vit_sdpa_long_f32_count(int reset) { return take_count(g_long_f32_count, reset); }
 
 // fp32 arithmetic of the resident f32 kernels (f32, N <= 288, aligned rows, causal or not): 0 = f32 MFMA,
 // 1 = bf16x3, -1 keeps; other values are ignored.  Returns the previous setting.  "At most bf16x3": the streamed
@@ -3039,11 +2997,7 @@ int vit_sdpa_f32_precision(int mode) {
   return prev;
 }
 // Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the bf16x3 kernels; reset != 0 zeroes it.
-int vit_sdpa_f32_split_count(int reset) {
-  const int c = g_f32_split_count;
-  if (reset) g_f32_split_count = 0;
-  return c;
-}
+int vit_sdpa_f32_split_count(int reset) { return take_count(g_f32_split_count, reset); }
 
 // F.scaled_dot_product_attention(q, k, v) (no dropout) for head_dim 64; causal = 1
 // masks key > query (OpenAI CLIP text tower attn_mask, additive -inf above the diagonal).
@@ -3071,35 +3025,25 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
       ++g_long_f32_count;
       return 0;
     case AP_RESIDENT_BF16:
-      switch ((N + 15) / 16) {
-#define CASE(n) case n: return fwd_mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
-        NT_CASES(CASE)
-#undef CASE
-      }
-      break;
+      return by_tiles(N, [&](auto nt) {
+        return fwd_mfma<nt()>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
+      });
     case AP_RESIDENT_F32:
-      if (g_f32_split) switch ((N + 15) / 16) {
-#define CASE(n) case n: return fwd_f32x3<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
-        NT_CASES(CASE)
-#undef CASE
-      }
-      switch ((N + 15) / 16) {
-#define CASE(n) case n: return fwd_f32mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
-        NT_CASES(CASE)
-#undef CASE
-      }
-      break;
+      return by_tiles(N, [&](auto nt) {
+        return g_f32_split ? fwd_f32<F32X3Res<nt()>>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s)
+                           : fwd_f32<F32Res<nt()>>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, lse, s);
+      });
     case AP_GENERIC:
       break;
   }
   if ((int64_t)B * H > 65535) return (int)hipErrorInvalidValue;  // the generic kernels put b*h on grid.y
-  dim3 grid((N + 63) / 64, B * H);
-  if (dtype == VIT_BF16)
-    hipLaunchKernelGGL(attn_fwd_generic<bf16>, grid, dim3(256), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale, (bf16*)o, ld_o, lse, causal);
-  else
-    hipLaunchKernelGGL(attn_fwd_generic<float>, grid, dim3(256), 0, s, (const float*)qkv, ld_qkv, D, H, N, scale, (float*)o, ld_o, lse, causal);
-  VIT_CHECK_LAUNCH();
-  return 0;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(attn_fwd_generic<T>, dim3((N + 63) / 64, B * H), dim3(256), 0, s, (const T*)qkv, ld_qkv, D, H, N,
+                       scale, (T*)o, ld_o, lse, causal);
+    VIT_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 // Query-limited forward: only query 0 of every (b, h) will be read.  bf16, N <= 288, aligned rows: the
@@ -3109,22 +3053,15 @@ int vit_sdpa_fwd_cls(int dtype, int B, int H, int N, int head_dim, const void* q
                      int64_t ld_o, float* lse, float scale, void* stream) {
   if (head_dim != 64 || N <= 0) return (int)hipErrorInvalidValue;
   if (N <= AT_RESIDENT_MAX && dtype == VIT_BF16 && (ld_qkv % 8 == 0) && (ld_o % 4 == 0) && lse && !g_attn_stamps) {
-    const int nt = (N + 15) / 16;
     ++g_cls_count;
-    switch (nt) {
-#define CASE(n) case n: return fwd_mfma_cls<n>(qkv, ld_qkv, H * 64, B, H, N, scale, o, ld_o, lse, (hipStream_t)stream);
-      NT_CASES(CASE)
-#undef CASE
-    }
+    return by_tiles(N, [&](auto nt) {
+      return fwd_mfma_cls<nt()>(qkv, ld_qkv, H * 64, B, H, N, scale, o, ld_o, lse, (hipStream_t)stream);
+    });
   }
   return vit_sdpa_fwd(dtype, B, H, N, head_dim, qkv, ld_qkv, o, ld_o, lse, scale, 0, stream);
 }
 // Host-side count of vit_sdpa_fwd_cls calls that took the query-limited kernel (reset != 0 zeroes it).
-int vit_sdpa_cls_count(int reset) {
-  const int n = g_cls_count;
-  if (reset) g_cls_count = 0;
-  return n;
-}
+int vit_sdpa_cls_count(int reset) { return take_count(g_cls_count, reset); }
 
 // One-query forward (attn_cls1_fwd): query row 0 of every image, all N keys and values; bf16 or f32, any N up to
 // 2048.  o_cls [B, D] with row b at b * ld_o (the dense o with ld_o = N * D is a valid argument), lse_cls [B * H]
@@ -3137,15 +3074,14 @@ int vit_sdpa_cls1_fwd(int dtype, int B, int H, int N, int head_dim, const void* 
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   const int D = H * 64;
-  if (dtype == VIT_BF16)
-    hipLaunchKernelGGL(attn_cls1_fwd<bf16>, dim3(B * H), dim3(C1_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N,
-                       scale, (bf16*)o_cls, ld_o, lse_cls);
-  else
-    hipLaunchKernelGGL(attn_cls1_fwd<float>, dim3(B * H), dim3(C1_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
-                       scale, (float*)o_cls, ld_o, lse_cls);
-  VIT_CHECK_LAUNCH();
-  ++g_cls1_count;
-  return 0;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(attn_cls1_fwd<T>, dim3(B * H), dim3(C1_THREADS), 0, s, (const T*)qkv, ld_qkv, D, H, N, scale,
+                       (T*)o_cls, ld_o, lse_cls);
+    VIT_CHECK_LAUNCH();
+    ++g_cls1_count;
+    return 0;
+  });
 }
 
 // One-query backward (attn_cls1_bwd) from the class rows' dO (do_cls [B, D], row b at b * ld_do), the forward's
@@ -3159,22 +3095,17 @@ int vit_sdpa_cls1_bwd(int dtype, int B, int H, int N, int head_dim, const void* 
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   const int D = H * 64;
-  if (dtype == VIT_BF16)
-    hipLaunchKernelGGL(attn_cls1_bwd<bf16>, dim3(B * H), dim3(C1_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N,
-                       scale, (const bf16*)o_cls, ld_o, (const bf16*)do_cls, ld_do, lse_cls, (bf16*)dqkv, ld_dqkv);
-  else
-    hipLaunchKernelGGL(attn_cls1_bwd<float>, dim3(B * H), dim3(C1_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
-                       scale, (const float*)o_cls, ld_o, (const float*)do_cls, ld_do, lse_cls, (float*)dqkv, ld_dqkv);
-  VIT_CHECK_LAUNCH();
-  ++g_cls1_count;
-  return 0;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(attn_cls1_bwd<T>, dim3(B * H), dim3(C1_THREADS), 0, s, (const T*)qkv, ld_qkv, D, H, N, scale,
+                       (const T*)o_cls, ld_o, (const T*)do_cls, ld_do, lse_cls, (T*)dqkv, ld_dqkv);
+    VIT_CHECK_LAUNCH();
+    ++g_cls1_count;
+    return 0;
+  });
 }
 // Host-side count of launches of either one-query kernel (reset != 0 zeroes it after reading).
-int vit_sdpa_cls1_count(int reset) {
-  const int n = g_cls1_count;
-  if (reset) g_cls1_count = 0;
-  return n;
-}
+int vit_sdpa_cls1_count(int reset) { return take_count(g_cls1_count, reset); }
 
 // One-query forward at a row per sequence (attn_row1_fwd): query row qrow[b] (int64 on the device, clamped to
 // [0, N - 1] in the kernel) against keys 0 .. qrow[b] (causal != 0) or all N keys; bf16 or f32, any N up to 2048.
@@ -3188,22 +3119,17 @@ int vit_sdpa_row1_fwd(int dtype, int B, int H, int N, int head_dim, const void* 
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   const int D = H * 64;
-  if (dtype == VIT_BF16)
-    hipLaunchKernelGGL(attn_row1_fwd<bf16>, dim3(B * H), dim3(C1_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N,
-                       qrow, causal != 0, scale, (bf16*)o_row, ld_o, lse_row);
-  else
-    hipLaunchKernelGGL(attn_row1_fwd<float>, dim3(B * H), dim3(C1_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
-                       qrow, causal != 0, scale, (float*)o_row, ld_o, lse_row);
-  VIT_CHECK_LAUNCH();
-  ++g_row1_count;
-  return 0;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(attn_row1_fwd<T>, dim3(B * H), dim3(C1_THREADS), 0, s, (const T*)qkv, ld_qkv, D, H, N, qrow,
+                       causal != 0, scale, (T*)o_row, ld_o, lse_row);
+    VIT_CHECK_LAUNCH();
+    ++g_row1_count;
+    return 0;
+  });
 }
 // Host-side count of attn_row1_fwd launches (reset != 0 zeroes it after reading).
-int vit_sdpa_row1_count(int reset) {
-  const int n = g_row1_count;
-  if (reset) g_row1_count = 0;
-  return n;
-}
+int vit_sdpa_row1_count(int reset) { return take_count(g_row1_count, reset); }
 
 // fp8 (block-scaled OCP e4m3) forward, head_dim 64, N <= 320: see attn_fwd_fp8.  qkv / o bf16
 // or f32 (dtype; quantised to e4m3 inside the kernel either way); lse f32 or null.
@@ -3212,21 +3138,20 @@ int vit_sdpa_fwd_fp8(int dtype, int B, int H, int N, int head_dim, const void* q
   hipStream_t s = (hipStream_t)stream;
   if (head_dim != 64 || N <= 0 || N > 320 || (ld_qkv % 8) || (ld_o % 4)) return (int)hipErrorInvalidValue;
   const int D = H * 64;
-  switch ((N + 63) / 64) {
-#define F8(n)                                                                                                   \
-  case n:                                                                                                       \
-    if (dtype == VIT_BF16)                                                                                      \
-      hipLaunchKernelGGL((attn_fwd_fp8<n, bf16>), dim3(B * H), dim3(F8_THREADS), 0, s, (const bf16*)qkv, ld_qkv, \
-                         D, H, N, scale, (bf16*)o, ld_o, lse, causal);                                          \
-    else                                                                                                        \
-      hipLaunchKernelGGL((attn_fwd_fp8<n, float>), dim3(B * H), dim3(F8_THREADS), 0, s, (const float*)qkv,      \
-                         ld_qkv, D, H, N, scale, (float*)o, ld_o, lse, causal);                                 \
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    switch ((N + 63) / 64) {
+#define F8(n)                                                                                                       \
+  case n:                                                                                                           \
+    hipLaunchKernelGGL((attn_fwd_fp8<n, T>), dim3(B * H), dim3(F8_THREADS), 0, s, (const T*)qkv, ld_qkv, D, H, N, scale, \
+                       (T*)o, ld_o, lse, causal);                                                                   \
     break;
-    F8(1) F8(2) F8(3) F8(4) F8(5)
+      F8(1) F8(2) F8(3) F8(4) F8(5)
 #undef F8
-  }
-  VIT_CHECK_LAUNCH();
-  return 0;
+    }
+    VIT_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 // The streamed form of vit_sdpa_fwd_fp8 (attn_fwd_fp8_stream): any N >= 1, the same refusals otherwise; up to
@@ -3239,22 +3164,17 @@ int vit_sdpa_fwd_fp8_stream(int dtype, int B, int H, int N, int head_dim, const 
   const int D = H * 64;
   const dim3 grid(B * H, (N + F8S_QB - 1) / F8S_QB);
   if (grid.y > 65535) return (int)hipErrorInvalidValue;
-  if (dtype == VIT_BF16)
-    hipLaunchKernelGGL(attn_fwd_fp8_stream<bf16>, grid, dim3(F8_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
-                       (bf16*)o, ld_o, lse, causal);
-  else
-    hipLaunchKernelGGL(attn_fwd_fp8_stream<float>, grid, dim3(F8_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
-                       scale, (float*)o, ld_o, lse, causal);
-  VIT_CHECK_LAUNCH();
-  ++g_fp8_stream_count;
-  return 0;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(attn_fwd_fp8_stream<T>, grid, dim3(F8_THREADS), 0, s, (const T*)qkv, ld_qkv, D, H, N, scale,
+                       (T*)o, ld_o, lse, causal);
+    VIT_CHECK_LAUNCH();
+    ++g_fp8_stream_count;
+    return 0;
+  });
 }
 // Host-side count of vit_sdpa_fwd_fp8_stream calls that launched (reset != 0 zeroes it after reading).
-int vit_sdpa_fp8_stream_count(int reset) {
-  const int c = g_fp8_stream_count;
-  if (reset) g_fp8_stream_count = 0;
-  return c;
-}
+int vit_sdpa_fp8_stream_count(int reset) { return take_count(g_fp8_stream_count, reset); }
 
 // The quantise-once pair (attn_fp8_quant_kv, attn_fwd_fp8_pre).  The workspace layout is private to this file:
 // callers size it with vit_sdpa_fp8_kv_bytes.
@@ -3281,14 +3201,13 @@ int vit_sdpa_fp8_quant_kv(int dtype, int B, int H, int N, int head_dim, const vo
   hipStream_t s = (hipStream_t)stream;
   const int D = H * 64;
   const dim3 grid(B * H, (N + F8S_CH - 1) / F8S_CH);
-  if (dtype == VIT_BF16)
-    hipLaunchKernelGGL(attn_fp8_quant_kv<bf16>, grid, dim3(F8_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N,
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(attn_fp8_quant_kv<T>, grid, dim3(F8_THREADS), 0, s, (const T*)qkv, ld_qkv, D, H, N,
                        (unsigned char*)ws);
-  else
-    hipLaunchKernelGGL(attn_fp8_quant_kv<float>, grid, dim3(F8_THREADS), 0, s, (const float*)qkv, ld_qkv, D, H, N,
-                       (unsigned char*)ws);
-  VIT_CHECK_LAUNCH();
-  return 0;
+    VIT_CHECK_LAUNCH();
+    return 0;
+  });
 }
 // The consumer: vit_sdpa_fwd_fp8_stream's o and lse, bit for bit, with K and V taken from ws alone (qkv is read
 // for Q).  Same refusals, and ws as in vit_sdpa_fp8_quant_kv.
@@ -3298,22 +3217,17 @@ int vit_sdpa_fwd_fp8_pre(int dtype, int B, int H, int N, int head_dim, const voi
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(B * H, (N + F8S_QB - 1) / F8S_QB);
-  if (dtype == VIT_BF16)
-    hipLaunchKernelGGL(attn_fwd_fp8_pre<bf16>, grid, dim3(F8_THREADS), 0, s, (const bf16*)qkv, ld_qkv, H, N,
-                       (const unsigned char*)ws, scale, (bf16*)o, ld_o, lse, causal);
-  else
-    hipLaunchKernelGGL(attn_fwd_fp8_pre<float>, grid, dim3(F8_THREADS), 0, s, (const float*)qkv, ld_qkv, H, N,
-                       (const unsigned char*)ws, scale, (float*)o, ld_o, lse, causal);
-  VIT_CHECK_LAUNCH();
-  ++g_fp8_pre_count;
-  return 0;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(attn_fwd_fp8_pre<T>, grid, dim3(F8_THREADS), 0, s, (const T*)qkv, ld_qkv, H, N,
+                       (const unsigned char*)ws, scale, (T*)o, ld_o, lse, causal);
+    VIT_CHECK_LAUNCH();
+    ++g_fp8_pre_count;
+    return 0;
+  });
 }
 // Host-side count of vit_sdpa_fwd_fp8_pre calls that launched (reset != 0 zeroes it after reading).
-int vit_sdpa_fp8_pre_count(int reset) {
-  const int c = g_fp8_pre_count;
-  if (reset) g_fp8_pre_count = 0;
-  return c;
-}
+int vit_sdpa_fp8_pre_count(int reset) { return take_count(g_fp8_pre_count, reset); }
 
 // SDPA backward: writes dq/dk/dv into dqkv (same column layout as qkv).
 // `delta_ws` (>= B*H*N floats) receives rowsum(dO*O) per (b, h, n).
@@ -3349,29 +3263,21 @@ int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
   int rc = (int)hipErrorInvalidValue;
   switch (path) {
     case AP_RESIDENT_BF16:
-      switch ((N + 15) / 16) {
-#define CASE(n) case n: rc = bwd_mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv, (dbias || part_only) ? partial : nullptr, s); break;
-        NT_CASES(CASE)
-#undef CASE
-      }
+      rc = by_tiles(N, [&](auto nt) {
+        return bwd_mfma<nt()>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv,
+                              (dbias || part_only) ? partial : nullptr, s);
+      });
       if (rc || !dbias) return rc;
       launch_colreduce(partial, B, 3 * D, dbias, 0, s, partial + (int64_t)B * 3 * D);
       VIT_CHECK_LAUNCH();
       return 0;
     case AP_RESIDENT_F32:
-      if (g_f32_split) {
-        switch ((N + 15) / 16) {
-#define CASE(n) case n: rc = bwd_f32x3<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv, s); break;
-          NT_CASES(CASE)
-#undef CASE
-        }
-        break;
-      }
-      switch ((N + 15) / 16) {
-#define CASE(n) case n: rc = bwd_f32mfma<n>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv, ld_dqkv, s); break;
-        NT_CASES(CASE)
-#undef CASE
-      }
+      rc = by_tiles(N, [&](auto nt) {
+        return g_f32_split ? bwd_f32<F32X3Res<nt()>>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse,
+                                                     delta_ws, dqkv, ld_dqkv, s)
+                           : bwd_f32<F32Res<nt()>>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse,
+                                                   delta_ws, dqkv, ld_dqkv, s);
+      });
       break;
     case AP_STREAM_BF16:
       hipLaunchKernelGGL(attn_bwd_dq_stream, sgrid, dim3(AT_THREADS), 0, s, (const bf16*)qkv, ld_qkv, D, H, N, scale,
@@ -3395,10 +3301,10 @@ int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
       rc = 0;
       break;
     case AP_GENERIC:
-      rc = dtype == VIT_BF16 ? bwd_generic<bf16>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse,
-                                                 delta_ws, dqkv, ld_dqkv, s)
-                             : bwd_generic<float>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse,
-                                                  delta_ws, dqkv, ld_dqkv, s);
+      rc = by_dtype(dtype, [&](auto t) {
+        return bwd_generic<decltype(t)>(qkv, ld_qkv, D, B, H, N, scale, causal, o, ld_o, dout, ld_do, lse, delta_ws, dqkv,
+                                        ld_dqkv, s);
+      });
       break;
   }
   if (rc) return rc;

@@ -378,7 +378,7 @@ int vit_sdpa_long_f32_count(int reset);
  * operands (the rule of vit_gemm_f32_precision), f32 accumulate; the softmax, delta, lse, the scale factors and
  * the stores stay f32.  -1 keeps; any other value is ignored.  Returns the previous setting (initially
  * VIT_F32_ATTENTION = highest | high, else 0).  Independent of vit_gemm_f32_precision.  "At most bf16x3": the
- * streamed f32 kernels past 288 tokens, the generic kernels, vit_sdpa_cls1_* / vit_sdpa_row1_fwd and
+ * streamed f32 kernels past 288 tokens (unless vit_sdpa_f32_long_precision(1) is set too), the generic kernels, vit_sdpa_cls1_* / vit_sdpa_row1_fwd and
  * vit_sdpa_fwd_cls are exact f32 in either mode.  +-inf in gives NaN out in mode 1 (the -inf of the masks is
  * applied after the products and is not affected).  Process-wide, read at launch time: a backward runs in the
  * mode current when it runs.  Additive to ABI 10.  Host-only, no GPU call. */
@@ -386,6 +386,17 @@ int vit_sdpa_f32_precision(int mode);
 /* Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the bf16x3 kernels (one per call; reset != 0
  * zeroes it after reading): a test's guard against a silent fallback. */
 int vit_sdpa_f32_split_count(int reset);
+/* fp32 arithmetic of the streamed f32 attention kernels (f32 operands, N > 288, head_dim 64, every row stride a
+ * multiple of 4, not causal): 0 = v_mfma_f32_16x16x4_f32, exact f32 products (default); 1 = the three bf16 MFMA
+ * products of vit_sdpa_f32_precision(1) on the streamed schedule, taken only while vit_sdpa_f32_precision is 1 as
+ * well -- that switch alone leaves streamed attention exact.  -1 keeps; any other value is ignored.  Returns the
+ * previous setting (initially 1 under VIT_F32_ATTENTION_LONG=1, else 0).  The generic kernels past 288 tokens
+ * (causal, misaligned rows, vit_sdpa_long_config(0), VIT_ATTN_F32_GENERIC=1) stay exact f32.  Process-wide, read at
+ * launch time.  Additive to ABI 10.  Host-only, no GPU call. */
+int vit_sdpa_f32_long_precision(int mode);
+/* Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed bf16x3 kernels (one per call; they
+ * count in vit_sdpa_long_f32_count as well and never in vit_sdpa_f32_split_count; reset != 0 zeroes it). */
+int vit_sdpa_long_f32_split_count(int reset);
 /* Tuning hook: the bf16 backward form for N <= 224 (-1 = from VIT_ATTN_BWD_SPLIT, 1 = whole-head fused
  * (the default), 2 = two kernels; 0, round 4's banded form, was removed in ABI 8: hipErrorInvalidValue).
  * The two forms agree to bf16 rounding (some f32 sums are ordered differently). */

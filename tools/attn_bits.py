@@ -9,7 +9,9 @@ The backward runs from the library's own o and lse.  Cases: the bf16 resident tw
 vit_sdpa_bwd_variant(2) below that), the f32 resident kernels, the streamed kernels of both dtypes, the fused
 bf16 backward as a control, and last the f32 resident kernels in the "high" mode (vit_sdpa_f32_precision(1), the
 bf16x3 kernels; N = 1, 17, 33, 77 causal, 257, 288: one tile, an edge inside a pair's second tile, an odd tile
-count, the mask, one workgroup per CU, every tile full).  First come the resident fp8 forward's o and lse (N = 77
+count, the mask, one workgroup per CU, every tile full) and the f32 streamed kernels in the high + long mode
+(vit_sdpa_f32_long_precision(1) as well, the streamed bf16x3 kernels; N = 289, 321, 577; skipped on a library that
+lacks the export, whose file then ends three lines earlier).  First come the resident fp8 forward's o and lse (N = 77
 causal, 197, 257, 320, both dtypes; ``--fp8-only`` stops after them).
 """
 import hashlib
@@ -37,6 +39,8 @@ CASES = ([("bf16 resident two-kernel", BF16, n, False, -1) for n in (240, 257, 2
          [("bf16 fused (control)", BF16, 197, False, -1)])
 # f32 resident under vit_sdpa_f32_precision(1): (N, causal)
 HIGH_CASES = ((1, False), (17, False), (33, False), (77, True), (257, False), (288, False))
+# f32 streamed under vit_sdpa_f32_precision(1) and vit_sdpa_f32_long_precision(1)
+HIGH_LONG_CASES = (289, 321, 577)
 # the resident fp8 forward (o and lse only), both dtypes; --fp8-only runs these alone
 FP8_CASES = ((77, True), (197, False), (257, False), (320, False))
 
@@ -114,6 +118,21 @@ def main():
             lib.vit_sdpa_f32_precision(0)
         assert took == 2, ("the forward and the backward must both take the bf16x3 kernels", N, took)
         print(json.dumps({"kernels": "f32 resident high", "dtype": "f32", "N": N, "causal": causal,
+                          "bwd_variant": -1, **r}), flush=True)
+    if "vit_sdpa_f32_long_precision" not in L.SIGNATURES:  # an older build
+        return
+    for N in HIGH_LONG_CASES:
+        lib.vit_sdpa_f32_precision(1)
+        lib.vit_sdpa_f32_long_precision(1)
+        try:
+            lib.vit_sdpa_long_f32_split_count(1)  # zero it
+            r = run(F32, N, False)
+            took = lib.vit_sdpa_long_f32_split_count(1)
+        finally:
+            lib.vit_sdpa_f32_precision(0)
+            lib.vit_sdpa_f32_long_precision(0)
+        assert took == 2, ("the forward and the backward must both take the streamed bf16x3 kernels", N, took)
+        print(json.dumps({"kernels": "f32 streamed high + long", "dtype": "f32", "N": N, "causal": False,
                           "bwd_variant": -1, **r}), flush=True)
 
 

@@ -5,12 +5,18 @@ for the cost of streaming per score.  The variants alternate over --rounds round
 variant's round-to-round spread are reported.
 
     python tools/bench_attn_long.py [--dtype bf16|f32] [--batch 64] [--heads 12] [--n 577] [--n-resident 257]
-                                    [--reps 20] [--fp8]
+                                    [--reps 20] [--fp8] [--pairs P]
 
 --fp8 (forward only): the streamed fp8 kernel against the streamed forward of --dtype at --n, and the resident fp8
 kernel against the streamed one at --n-resident (<= 320).  At both lengths also the pre-quantised form (DESIGN
 §4.20): the pre-pass alone, the consumer alone (on a workspace made beforehand) and the pair as ops.sdpa_fwd runs it
 past 320 tokens (workspace from the caching allocator in every call).
+
+--pairs P (--dtype f32, P >= 3): instead, the streamed f32 kernels at --n in both arithmetics -- "highest" (f32 MFMA)
+and "high" + long (bf16x3, ``ops.set_float32_attention_precision("high", long_sequences=True)``) --
+alternated over P pairs in this one process, as tools/bench_attn_f32.py alternates the resident kernels: per kernel
+and mode the median of P windows of --reps back-to-back calls, the spread (max - min) / median, the ratio of the
+medians and whether it counts (past twice the larger spread).  One JSON line.
 
 Prints one JSON line per (variant, round) and a final summary line.  --no-generic / --no-streamed skip a
 variant (a tree without the streamed kernels can still time its resident kernels with --n 0).
@@ -113,6 +119,47 @@ def main_fp8(a, dtype):
     print(json.dumps(out), flush=True)
 
 
+def main_pairs(a):
+    """--pairs: streamed f32 attention at --n, "highest" against "high" + long, alternated."""
+    from tools.bench_attn_f32 import summary, window
+    B, H, N = a.batch, a.heads, a.n
+    lib = L.lib()
+    lib.vit_sdpa_long_config(1)
+    c = case(B, H, N, torch.float32)
+    calls = {"fwd": lambda: ops.sdpa_fwd(c["qkv"], B, H, N, o=c["o"], lse=c["lse"]),
+             "bwd": lambda: ops.sdpa_bwd(c["qkv"], c["o"], c["do"], c["lse"], B, H, N, dqkv=c["dq"], dbias=c["dbias"])}
+    modes = ("highest", "high+long")
+    switch = lambda m: ops.set_float32_attention_precision(m.split("+")[0], long_sequences=m.endswith("+long"))
+    us = {k: {m: [] for m in modes} for k in calls}
+    try:
+        for m in modes:  # warm both modes, and check which kernels each takes
+            switch(m)
+            c0, s0 = lib.vit_sdpa_long_f32_split_count(0), lib.vit_sdpa_long_f32_count(0)
+            for fn in calls.values():
+                window(fn, 3)
+            took = (lib.vit_sdpa_long_f32_split_count(0) - c0, lib.vit_sdpa_long_f32_count(0) - s0)
+            assert took == ((6, 6) if m != "highest" else (0, 6)), (m, took)
+        for _ in range(a.pairs):
+            for m in modes:
+                switch(m)
+                for k, fn in calls.items():
+                    us[k][m].append(window(fn, a.reps))
+    finally:
+        ops.set_float32_attention_precision("highest")
+        lib.vit_sdpa_long_config(-1)
+    rec = {"B": B, "H": H, "N": N, "dtype": "f32", "pairs": a.pairs, "reps": a.reps, "bwd_with_dbias": True}
+    fl = 4.0 * B * H * N * N * 64
+    for k in calls:
+        s = {m: summary(us[k][m]) for m in modes}
+        ratio = s["highest"]["median_us"] / s["high+long"]["median_us"]
+        s["high_long_speedup"] = round(ratio, 3)
+        s["counts"] = bool(abs(ratio - 1) > 2 * max(s[m]["spread"] for m in modes))
+        s["high_long_tflops_of_the_f32_product"] = round((1.0 if k == "fwd" else 2.5) * fl
+                                                         / s["high+long"]["median_us"] / 1e6, 1)
+        rec[k] = s
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fp8", action="store_true", help="forward only: the streamed fp8 kernel against the streamed "
@@ -127,7 +174,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--no-generic", action="store_true")
     ap.add_argument("--no-streamed", action="store_true")
+    ap.add_argument("--pairs", type=int, default=0, help="--dtype f32: alternate the streamed kernels' highest and "
+                    "high + long arithmetic over this many pairs (at least 3) instead of the variants above")
     a = ap.parse_args()
+    if a.pairs:
+        if a.pairs < 3 or a.dtype != "f32" or a.fp8 or a.n <= 288:
+            ap.error("--pairs needs at least 3 pairs, --dtype f32, --n past 288 and no --fp8")
+        return main_pairs(a)
     lib = L.lib()
     dtype = torch.float32 if a.dtype == "f32" else torch.bfloat16
     if a.fp8:

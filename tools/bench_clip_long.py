@@ -5,12 +5,16 @@ tokens on the streamed f32 kernels against the generic ones (vit_sdpa_long_confi
 
     python tools/bench_clip_long.py [--batch 16] [--steps 5] [--warmup 2] [--rounds 3] [--steps-generic 2]
                                     [--f32-matmul highest|high] [--f32-ab]
-                                    [--f32-attention highest|high] [--f32-attention-ab]
+                                    [--f32-attention highest|high] [--f32-attention-ab] [--f32-attention-long]
 
 ``--f32-matmul`` sets the fp32 GEMM arithmetic of the run (``high`` = bf16x3); ``--f32-ab``
 alternates ``highest`` and ``high`` instead, both on the streamed attention kernels.  ``--f32-attention`` and
 ``--f32-attention-ab`` do the same with the fp32 attention mode: at 577 tokens only the text
-tower's 77-token attention takes the bf16x3 kernels, the visual tower's streamed f32 kernels stay exact.
+tower's 77-token attention takes the bf16x3 kernels, the visual tower's streamed f32 kernels stay exact --
+unless ``--f32-attention-long`` is given too: then ``high`` means
+``set_float32_attention_precision("high", long_sequences=True)`` and the visual tower's streamed attention takes
+the bf16x3 kernels as well.  With ``--f32-attention-ab`` the record then also holds ``pred_distance``, the largest
+difference between the two modes' predictions on the batch over the largest prediction, taken before the first step.
 """
 import argparse
 import json
@@ -41,14 +45,21 @@ def main():
     ap.add_argument("--f32-ab", action="store_true")
     ap.add_argument("--f32-attention", choices=["highest", "high"], default=None)
     ap.add_argument("--f32-attention-ab", action="store_true")
+    ap.add_argument("--f32-attention-long", action="store_true",
+                    help="with --f32-attention high or --f32-attention-ab: high also covers streamed attention")
     a = ap.parse_args()
     if a.f32_ab and a.f32_attention_ab:
         ap.error("one switch alternates at a time")
+    if a.f32_attention_long and not (a.f32_attention == "high" or a.f32_attention_ab):
+        ap.error("--f32-attention-long needs --f32-attention high or --f32-attention-ab")
+
+    def set_attention(mode):
+        vit_amd.set_float32_attention_precision(mode, long_sequences=a.f32_attention_long and mode == "high")
     if a.f32_matmul:
         vit_amd.set_float32_matmul_precision(a.f32_matmul)
     if a.f32_attention:
-        vit_amd.set_float32_attention_precision(a.f32_attention)
-    set_mode = vit_amd.set_float32_attention_precision if a.f32_attention_ab else vit_amd.set_float32_matmul_precision
+        set_attention(a.f32_attention)
+    set_mode = set_attention if a.f32_attention_ab else vit_amd.set_float32_matmul_precision
     dev = torch.device("cuda", 0)
     lib = L.lib()
     torch.manual_seed(0)
@@ -84,7 +95,20 @@ def main():
 
     if a.f32_ab or a.f32_attention_ab:
         ips = {"highest": [], "high": []}
+        extra = {}
         try:
+            if a.f32_attention_ab and a.f32_attention_long:
+                lib.vit_sdpa_long_config(1)
+                preds = {}
+                for name in ips:
+                    set_mode(name)
+                    c0 = lib.vit_sdpa_long_f32_split_count(0)
+                    with torch.no_grad():
+                        preds[name] = m(x).double()
+                    assert (lib.vit_sdpa_long_f32_split_count(0) > c0) == (name == "high"), name
+                extra["pred_distance"] = float((preds["high"] - preds["highest"]).abs().max()
+                                               / preds["highest"].abs().max())
+                extra["f32_attention_long"] = True
             for rnd in range(a.rounds):
                 for name in ips:
                     set_mode(name)
@@ -96,8 +120,9 @@ def main():
         print(json.dumps({"metric": "images/sec CLIP-HBA ViT-L/14@336px + DoRA fp32 train step", "batch": a.batch,
                           "steps": a.steps, "rounds": a.rounds, "images_per_sec": ips, "median": med,
                           "alternated": "f32_attention" if a.f32_attention_ab else "f32_matmul",
+                          "f32_matmul": "ab" if a.f32_ab else (a.f32_matmul or "highest"),
                           "spread": {k: round((max(v) - min(v)) / med[k], 4) for k, v in ips.items()},
-                          "high_over_highest": round(med["high"] / med["highest"], 3)}), flush=True)
+                          "high_over_highest": round(med["high"] / med["highest"], 3), **extra}), flush=True)
         return
     ips = {"streamed": [], "generic": []}
     try:

@@ -19,6 +19,8 @@
 // f32 path (parity mode): scalar-FMA online softmax.
 // resident f32 path, "high" (vit_sdpa_f32_precision(1), opt-in): the bf16 path's algebra on hi / lo bf16 splits of the
 // f32 operands, three MFMA products a product (attn_*_f32x3; see the block in front of F32X3).
+// streamed f32 path, "high" + long (vit_sdpa_f32_long_precision(1) as well, opt-in): the same split on the streamed
+// schedule (attn_*_stream_x3; see the block in front of SX_BUF).
 // one-query path (attn_cls1_*, the CLIP visual tower's class-token tail): query row 0 of every image alone,
 // K / V straight from HBM to registers, no MFMA -- see the block in front of attn_cls1_fwd; attn_row1_fwd is the
 // same forward at a row per sequence, causal or not (the CLIP text tower's EOT tail).
@@ -2515,6 +2517,235 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dkv_stream_f32(
   if (kvalid) f32_store_dkv(dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64 + 16 * g, D, dk, dv, scale);
 }
 
+// ---------------------------------------------------------------------------
+// Streamed f32 attention as three bf16 MFMA products ("high" + long, vit_sdpa_f32_long_precision(1)):
+// the operand policy AtBf16x3 of the resident "high" kernels on the streamed schedule above -- the loop of
+// attn_fwd_stream with st_softmax_chunk, at_dq_step / at_dkv_step per 32-row pair, x3_row for the wave's own rows.
+// A ring buffer holds a hi and a lo bf16 image (64 rows x 128 B, at_off layout) of each of the two streamed
+// matrices: 32 KiB a buffer, 64 KiB a ring, the bytes of the f32 ring (+ the lse * log2(e) / delta strip in dkv).
+// A thread fetches one 8-float piece of each matrix as f32, holds it across the chunk's MFMA work and splits it at
+// commit (x3_load2's rule, a chunk at a time: rows are clamped to N - 1 and pieces of rows >= N zeroed first).
+// Ragged ends, ownership and summation order are the streamed kernels': one owner per output element, no atomics,
+// bitwise repeatable.
+// ---------------------------------------------------------------------------
+constexpr int SX_BUF = 4 * ST_IMG;                   // bytes: A hi | A lo | B hi | B lo
+constexpr int SX_LDS = 2 * SX_BUF;                   // fwd, dq: K, V
+constexpr int SX_BUF_DKV = SX_BUF + 2 * ST_CH * 4;   // Q, dO | lse * log2(e) | delta
+constexpr int SX_LDS_DKV = 2 * SX_BUF_DKV;
+static_assert(SX_BUF_DKV % 16 == 0, "the second buffer's images stay 16-B aligned");
+
+struct SxPiece { f32x4 a[2], b[2]; };
+// this thread's 8-float piece of rows [j0, j0 + 64) of two f32 head slices (clamped to row N - 1)
+__device__ __forceinline__ SxPiece sx_fetch(const float* sa, int64_t lda, const float* sb, int64_t ldb, int j0, int N) {
+  const int row = min(j0 + (int)(threadIdx.x >> 3), N - 1), c = threadIdx.x & 7;
+  SxPiece p;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    p.a[u] = *reinterpret_cast<const f32x4*>(sa + (int64_t)row * lda + c * 8 + u * 4);
+    p.b[u] = *reinterpret_cast<const f32x4*>(sb + (int64_t)row * ldb + c * 8 + u * 4);
+  }
+  return p;
+}
+__device__ __forceinline__ void sx_commit(char* buf, SxPiece p, int j0, int N) {
+  const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
+  if (j0 + r >= N) {
+    p.a[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    p.a[1] = p.a[0]; p.b[0] = p.a[0]; p.b[1] = p.a[0];
+  }
+  bf16x8 h, l;
+  split8<1>(p.a[0], p.a[1], h, l);
+  *reinterpret_cast<bf16x8*>(buf + at_off(r, c)) = h;
+  *reinterpret_cast<bf16x8*>(buf + ST_IMG + at_off(r, c)) = l;
+  split8<1>(p.b[0], p.b[1], h, l);
+  *reinterpret_cast<bf16x8*>(buf + 2 * ST_IMG + at_off(r, c)) = h;
+  *reinterpret_cast<bf16x8*>(buf + 3 * ST_IMG + at_off(r, c)) = l;
+}
+// The streamed kernels' name for the policy: at_dq_step / at_dkv_step instantiated on it are functions of their own,
+// so the resident attn_bwd_*_f32x3 kernels keep the instruction streams they had before these kernels shared the
+// steps (tools/isa_digest.sh --compare).
+struct AtBf16x3St : AtBf16x3 {};
+// matrix mtx (0: A, 1: B) of a ring buffer
+__device__ __forceinline__ AtBf16x3::Img sx_img(const char* buf, int mtx) {
+  return {buf + 2 * mtx * ST_IMG, buf + (2 * mtx + 1) * ST_IMG};
+}
+
+__global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_stream_x3(const float* __restrict__ qkv, int64_t ld_qkv, int D,
+                                                                   int H, int N, float scale, float* __restrict__ o,
+                                                                   int64_t ld_o, float* __restrict__ lse) {
+  using X = AtBf16x3;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const int q = blockIdx.y * ST_QB + wave * 16 + (lane & 15);
+  X::Frag qf[2];
+  {
+    f32x4 x[4];
+    x3_row(base + (int64_t)min(q, N - 1) * ld_qkv, g, qf, x);
+  }
+  const AtOffsets off(lane);
+  const int nc = (N + ST_CH - 1) / ST_CH;
+  SxPiece pc = sx_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, 0, N);
+  sx_commit(smem, pc, 0, N);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  float m = -INFINITY, l = 0.f;  // running max (raw scores, all 4 lanes of a query agree); this lane's part of the sum
+  f32x4 oacc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const char* buf = smem + (c & 1) * SX_BUF;
+    const X::Img Kimg = sx_img(buf, 0), Vimg = sx_img(buf, 1);
+    const int j0 = c * ST_CH;
+    const bool more = c + 1 < nc;
+    if (more) pc = sx_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0 + ST_CH, N);
+    f32x4 s[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) s[kt] = X::mma(X::row(Kimg, kt * 16, off.row[kk]), qf[kk], s[kt]);
+      if (kt % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // bound K-fragment hoisting (VGPRs)
+    }
+    st_softmax_chunk(s, j0, N, g, c2, m, l, oacc);  // on the f32 scores; the row sum is of the unsplit p
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const X::Frag pf = X::pack(s[2 * ks], s[2 * ks + 1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) oacc[dt] = X::mma(X::tr(Vimg, ks * 32, off.tr[dt]), pf, oacc[dt]);
+    }
+    if (more) sx_commit(smem + ((c + 1) & 1) * SX_BUF, pc, j0 + ST_CH, N);
+    __syncthreads();
+  }
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (q < N) {
+    x3_store_row(o + ((int64_t)b * N + q) * ld_o + h * 64, oacc, 1.0f / l, g);
+    if (g == 0) lse[(int64_t)bh * N + q] = (m * c2 + __log2f(l)) * LN2;
+  }
+}
+
+// query-parallel half of the streamed "high" backward: delta = rowsum(dO * O) on the unsplit f32 values (as in
+// attn_bwd_dq_f32x3) and dQ (at_dq_step<AtBf16x3> per 32-key pair of a chunk)
+__global__ __launch_bounds__(AT_THREADS, 4) void attn_bwd_dq_stream_x3(
+    const float* __restrict__ qkv, int64_t ld_qkv, int D, int H, int N, float scale, const float* __restrict__ o,
+    int64_t ld_o, const float* __restrict__ dout, int64_t ld_do, const float* __restrict__ lse,
+    float* __restrict__ delta_out, float* __restrict__ dqkv, int64_t ld_dqkv) {
+  using X = AtBf16x3;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const int q = blockIdx.y * ST_QB + wave * 16 + (lane & 15), qc = min(q, N - 1);
+  X::Frag qf[2], of[2];
+  float dl = 0.f;
+  {
+    const float* dorow = dout + ((int64_t)b * N + qc) * ld_do + h * 64;
+    const float* orow = o + ((int64_t)b * N + qc) * ld_o + h * 64;
+    f32x4 x[4], df[4];
+    x3_row(base + (int64_t)qc * ld_qkv, g, qf, x);
+    x3_row(dorow, g, of, df);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const f32x4 ov = *reinterpret_cast<const f32x4*>(orow + (j >> 1) * 32 + g * 8 + (j & 1) * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dl = fmaf(df[j][e], ov[e], dl);
+    }
+  }
+  dl += __shfl_xor(dl, 16, 64);
+  dl += __shfl_xor(dl, 32, 64);
+  if (q < N && g == 0) delta_out[(int64_t)bh * N + q] = dl;
+  const float l2 = lse[(int64_t)bh * N + qc] * LOG2E;
+  const AtOffsets off(lane);
+  const int nc = (N + ST_CH - 1) / ST_CH;
+  SxPiece pc = sx_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, 0, N);
+  sx_commit(smem, pc, 0, N);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  f32x4 dq[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const char* buf = smem + (c & 1) * SX_BUF;
+    const X::Img Kimg = sx_img(buf, 0), Vimg = sx_img(buf, 1);
+    const int j0 = c * ST_CH;
+    const bool more = c + 1 < nc;
+    if (more) pc = sx_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0 + ST_CH, N);
+    const bool edge = j0 + ST_CH > N;  // wave-uniform: only the last chunk holds keys >= N
+#pragma unroll 1
+    for (int kp = 0; kp < 2; ++kp)
+      at_dq_step<AtBf16x3St>(Kimg, Vimg, kp * 32, j0 + kp * 32, N, edge, off, g, qf, of, c2, l2, dl, q, 0, dq);
+    if (more) sx_commit(smem + ((c + 1) & 1) * SX_BUF, pc, j0 + ST_CH, N);
+    __syncthreads();
+  }
+  if (q < N) x3_store_row(dqkv + ((int64_t)b * N + q) * ld_dqkv + h * 64, dq, scale, g);
+}
+
+// key-parallel half: dK, dV of the workgroup's 128 keys (K, V rows split in registers) over streamed Q / dO chunks.
+// kf, vf (hi and lo), dk and dv are 64 live registers before the chunk's own operands: the 256-register budget, as
+// attn_bwd_dkv_stream_f32.
+__global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_dkv_stream_x3(
+    const float* __restrict__ qkv, int64_t ld_qkv, int D, int H, int N, float scale, const float* __restrict__ dout,
+    int64_t ld_do, const float* __restrict__ lse, const float* __restrict__ delta_in, float* __restrict__ dqkv,
+    int64_t ld_dqkv) {
+  using X = AtBf16x3;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
+  const float* dob = dout + (int64_t)b * N * ld_do + h * 64;
+  const int key = blockIdx.y * ST_QB + wave * 16 + (lane & 15), kc = min(key, N - 1);
+  const bool kvalid = key < N;
+  X::Frag kf[2], vf[2];
+  {
+    f32x4 x[4];
+    x3_row(base + (int64_t)kc * ld_qkv + D, g, kf, x);
+    x3_row(base + (int64_t)kc * ld_qkv + 2 * D, g, vf, x);
+  }
+  const float* lse_bh = lse + (int64_t)bh * N;
+  const float* delta_bh = delta_in + (int64_t)bh * N;
+  const AtOffsets off(lane);
+  const int nc = (N + ST_CH - 1) / ST_CH;
+  SxPiece pc = sx_fetch(base, ld_qkv, dob, ld_do, 0, N);
+  float sv = st_stat_fetch(lse_bh, delta_bh, 0, N);
+  sx_commit(smem, pc, 0, N);
+  st_stat_commit(smem + SX_BUF, sv);
+  __syncthreads();
+  const float c2 = scale * LOG2E;
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = dk[dt]; }
+#pragma unroll 1
+  for (int c = 0; c < nc; ++c) {
+    const char* buf = smem + (c & 1) * SX_BUF_DKV;
+    const X::Img Qimg = sx_img(buf, 0), Oimg = sx_img(buf, 1);  // O: dO
+    const float* lse2 = reinterpret_cast<const float*>(buf + SX_BUF);
+    const float* delta = lse2 + ST_CH;
+    const int j0 = c * ST_CH;
+    const bool more = c + 1 < nc;
+    if (more) {
+      pc = sx_fetch(base, ld_qkv, dob, ld_do, j0 + ST_CH, N);
+      sv = st_stat_fetch(lse_bh, delta_bh, j0 + ST_CH, N);
+    }
+#pragma unroll 1
+    for (int qp = 0; qp < 2; ++qp)
+      at_dkv_step<AtBf16x3St>(Qimg, Oimg, lse2, delta, qp * 32, j0 + qp * 32, off, g, kf, vf, c2, kvalid, key, 0, dk, dv);
+    if (more) {
+      char* nb = smem + ((c + 1) & 1) * SX_BUF_DKV;
+      sx_commit(nb, pc, j0 + ST_CH, N);
+      st_stat_commit(nb + SX_BUF, sv);
+    }
+    __syncthreads();
+  }
+  if (kvalid) {
+    float* row = dqkv + ((int64_t)b * N + key) * ld_dqkv + h * 64;
+    x3_store_row(row + D, dk, scale, g);
+    x3_store_row(row + 2 * D, dv, 1.f, g);
+  }
+}
+
 // qkv-bias gradient partials past 288 tokens: part[b][c] = sum over the image's N rows of dqkv[.][c], one
 // thread per column, rows in a fixed order (8 interleaved chains) -- the [B][3D] layout the resident
 // kernels leave.  It reads dqkv once, a few percent of the bytes the two backward kernels move.
@@ -2579,6 +2810,14 @@ static void stream_f32_attrs() {
   raise_lds(attn_bwd_dkv_stream_f32, SF_LDS_DKV);
   attr = true;
 }
+static void stream_x3_attrs() {
+  static bool attr = false;
+  if (attr) return;
+  raise_lds(attn_fwd_stream_x3, SX_LDS);
+  raise_lds(attn_bwd_dq_stream_x3, SX_LDS);
+  raise_lds(attn_bwd_dkv_stream_x3, SX_LDS_DKV);
+  attr = true;
+}
 // The two resident f32 kernel families behind one interface, for fwd_f32 / bwd_f32 below: SPLIT, THREADS, the
 // dynamic LDS sizes LDS / LDS_DKV and the kernels fwd(causal), dq(), dkv().
 template <int NT>
@@ -2618,6 +2857,16 @@ static int f32_attention_env() {
 }
 static int g_f32_split = f32_attention_env();
 static int g_f32_split_count = 0;
+// The same choice for the streamed f32 kernels past 288 tokens (vit_sdpa_f32_long_precision): 1 = bf16x3 (the
+// attn_*_stream_x3 kernels), honoured only while g_f32_split is 1 too.  Initial value from VIT_F32_ATTENTION_LONG=1.
+// g_long_f32_split_count: vit_sdpa_fwd / vit_sdpa_bwd calls that took them (g_long_f32_count counts those too).
+static int f32_attention_long_env() {
+  const char* s = getenv("VIT_F32_ATTENTION_LONG");
+  return s && !strcmp(s, "1") ? 1 : 0;
+}
+static int g_f32_long = f32_attention_long_env();
+static int g_long_f32_split_count = 0;
+static bool stream_f32_split() { return g_f32_split && g_f32_long; }
 
 // ---------------------------------------------------------------------------
 template <int NT>
@@ -2989,8 +3238,9 @@ int vit_sdpa_long_count(int reset) { return take_count(g_long_count, reset); }
 int vit_sdpa_long_f32_count(int reset) { return take_count(g_long_f32_count, reset); }
 
 // fp32 arithmetic of the resident f32 kernels (f32, N <= 288, aligned rows, causal or not): 0 = f32 MFMA,
-// 1 = bf16x3, -1 keeps; other values are ignored.  Returns the previous setting.  "At most bf16x3": the streamed
-// f32 kernels past 288 tokens, the generic and the one-query kernels and vit_sdpa_fwd_cls stay exact f32.
+// 1 = bf16x3, -1 keeps; other values are ignored.  Returns the previous setting.  "At most bf16x3": the generic and
+// the one-query kernels and vit_sdpa_fwd_cls stay exact f32, and so do the streamed f32 kernels past 288 tokens
+// unless vit_sdpa_f32_long_precision(1) is set as well.
 int vit_sdpa_f32_precision(int mode) {
   const int prev = g_f32_split;
   if (mode == 0 || mode == 1) g_f32_split = mode;
@@ -2998,6 +3248,18 @@ int vit_sdpa_f32_precision(int mode) {
 }
 // Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the bf16x3 kernels; reset != 0 zeroes it.
 int vit_sdpa_f32_split_count(int reset) { return take_count(g_f32_split_count, reset); }
+// fp32 arithmetic of the streamed f32 kernels (f32, N > 288, aligned rows, not causal): 0 = f32 MFMA (exact, the
+// default), 1 = bf16x3 while vit_sdpa_f32_precision is 1 as well, -1 keeps; other values are ignored.  Returns the
+// previous setting.  The generic kernels past 288 tokens (causal, misaligned, vit_sdpa_long_config(0),
+// VIT_ATTN_F32_GENERIC=1) stay exact f32.
+int vit_sdpa_f32_long_precision(int mode) {
+  const int prev = g_f32_long;
+  if (mode == 0 || mode == 1) g_f32_long = mode;
+  return prev;
+}
+// Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed bf16x3 kernels (they count in
+// vit_sdpa_long_f32_count too, never in vit_sdpa_f32_split_count); reset != 0 zeroes it.
+int vit_sdpa_long_f32_split_count(int reset) { return take_count(g_long_f32_split_count, reset); }
 
 // F.scaled_dot_product_attention(q, k, v) (no dropout) for head_dim 64; causal = 1
 // masks key > query (OpenAI CLIP text tower attn_mask, additive -inf above the diagonal).
@@ -3018,6 +3280,15 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
       ++g_long_count;
       return 0;
     case AP_STREAM_F32:
+      if (stream_f32_split()) {
+        stream_x3_attrs();
+        hipLaunchKernelGGL(attn_fwd_stream_x3, sgrid, dim3(AT_THREADS), SX_LDS, s, (const float*)qkv, ld_qkv, D, H, N,
+                           scale, (float*)o, ld_o, lse);
+        VIT_CHECK_LAUNCH();
+        ++g_long_f32_count;
+        ++g_long_f32_split_count;
+        return 0;
+      }
       stream_f32_attrs();
       hipLaunchKernelGGL(attn_fwd_stream_f32, sgrid, dim3(AT_THREADS), SF_LDS, s, (const float*)qkv, ld_qkv, D, H, N,
                          scale, (float*)o, ld_o, lse);
@@ -3290,6 +3561,19 @@ int vit_sdpa_bwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
       rc = 0;
       break;
     case AP_STREAM_F32:
+      if (stream_f32_split()) {
+        stream_x3_attrs();
+        hipLaunchKernelGGL(attn_bwd_dq_stream_x3, sgrid, dim3(AT_THREADS), SX_LDS, s, (const float*)qkv, ld_qkv, D, H, N,
+                           scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta_ws, (float*)dqkv, ld_dqkv);
+        VIT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(attn_bwd_dkv_stream_x3, sgrid, dim3(AT_THREADS), SX_LDS_DKV, s, (const float*)qkv, ld_qkv, D,
+                           H, N, scale, (const float*)dout, ld_do, lse, (const float*)delta_ws, (float*)dqkv, ld_dqkv);
+        VIT_CHECK_LAUNCH();
+        ++g_long_f32_count;
+        ++g_long_f32_split_count;
+        rc = 0;
+        break;
+      }
       stream_f32_attrs();
       hipLaunchKernelGGL(attn_bwd_dq_stream_f32, sgrid, dim3(AT_THREADS), SF_LDS, s, (const float*)qkv, ld_qkv, D, H, N,
                          scale, (const float*)o, ld_o, (const float*)dout, ld_do, lse, delta_ws, (float*)dqkv, ld_dqkv);

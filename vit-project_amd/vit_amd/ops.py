@@ -885,29 +885,49 @@ def get_float32_matmul_precision() -> str:
 _F32_ATTENTION = ("highest", "high")  # vit_sdpa_f32_precision 0 / 1
 
 
-def set_float32_attention_precision(precision):
-    """The arithmetic of the resident fp32 attention kernels (f32 operands, up to 288 tokens, head_dim 64,
-    aligned rows, causal or not):
+def set_float32_attention_precision(precision, long_sequences=False):
+    """The arithmetic of the fp32 attention kernels (f32 operands, head_dim 64, aligned rows): the resident ones
+    (up to 288 tokens, causal or not) and, with ``long_sequences=True``, the streamed ones past 288
+    tokens (not causal):
 
     - ``"highest"`` (the default): ``v_mfma_f32_16x16x4_f32``, exact f32 products;
     - ``"high"``: every matrix product of the forward (``QK^T``, ``PV``) and the backward (``S``, ``dP``, ``dQ``,
       ``dK``, ``dV``) as three bf16 MFMA products of ``hi + lo`` operands with f32 accumulation, the rule of
       :func:`set_float32_matmul_precision`.  The softmax, ``delta``, ``lse``, the scale factors and the stores
-      stay f32.  At most bf16x3: the streamed f32 kernels past 288 tokens, the generic and the one-query kernels
-      and the class-token-only forward stay exact f32.  An infinite operand gives NaN.
+      stay f32.  At most bf16x3: the generic and the one-query kernels and the class-token-only forward stay exact
+      f32, and so do the streamed f32 kernels past 288 tokens unless ``long_sequences=True``.  An infinite operand
+      gives NaN.
+
+    ``long_sequences=True`` (with ``"high"`` only; with ``"highest"`` it raises ``ValueError`` and changes
+    nothing) also runs streamed f32 attention -- 577 tokens for CLIP ViT-L/14@336px -- as three bf16 products, after
+    ``set_attention_fp8(True, long_sequences=True)``.  Both switches are set on every call, so a call without the
+    keyword switches the long form off; :func:`get_float32_attention_long` reads it.
 
     Independent of the GEMM switch: ``set_float32_matmul_precision("high")`` leaves attention exact, and this
     leaves the GEMMs exact.  Process-wide and read when a kernel is launched; cached frozen-prefix tensors carry the
     mode in their keys when it is ``"high"``.  ``VIT_F32_ATTENTION=high`` sets the initial value when the library
-    loads (spawned workers inherit it).  Host-only: works without a GPU."""
+    loads and ``VIT_F32_ATTENTION_LONG=1`` that of the long form (spawned workers inherit them).  Host-only: works
+    without a GPU."""
     if precision not in _F32_ATTENTION:
         raise ValueError(f'float32 attention precision must be "highest" or "high", got {precision!r}')
+    if long_sequences and precision != "high":
+        raise ValueError('long_sequences=True runs streamed fp32 attention as three bf16 products: it needs '
+                         'precision "high"')
     L.lib().vit_sdpa_f32_precision(_F32_ATTENTION.index(precision))
+    L.lib().vit_sdpa_f32_long_precision(1 if long_sequences else 0)
 
 
 def get_float32_attention_precision() -> str:
     """``"highest"`` or ``"high"``: see :func:`set_float32_attention_precision`."""
     return _F32_ATTENTION[L.lib().vit_sdpa_f32_precision(-1)]
+
+
+def get_float32_attention_long() -> bool:
+    """Whether streamed fp32 attention past 288 tokens runs as three bf16 products: both switches of
+    :func:`set_float32_attention_precision` are on.  (``VIT_F32_ATTENTION_LONG=1`` without ``VIT_F32_ATTENTION=high``
+    leaves the C switch set and this ``False``: the kernels stay exact.)"""
+    lib = L.lib()
+    return bool(lib.vit_sdpa_f32_precision(-1) == 1 and lib.vit_sdpa_f32_long_precision(-1) == 1)
 
 
 def gemm(P, p_layout, Q, q_layout, M, N, R, out=None, out_dtype=torch.float32, bias=None):

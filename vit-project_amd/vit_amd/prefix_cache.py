@@ -13,7 +13,8 @@ parameters, the cut, the compute dtype, the fp8-attention switch, ``pos_embeddin
 ``set_float32_matmul_precision("high")`` the compute-dtype element is the pair ``(compute_dtype, "high")``: rows
 built in one fp32 GEMM mode are rebuilt in the other, never read, and the key's length, its last element and
 its default-mode value stay what they were; under ``set_float32_attention_precision("high")`` it is the triple
-``(compute_dtype, gemm mode, "attention-high")``, for the same reason.  The cache holds references to those tensors, so an address in the key
+``(compute_dtype, gemm mode, "attention-high")``, for the same reason, and with ``long_sequences=True``
+(streamed fp32 attention as three bf16 products) ``(compute_dtype, gemm mode, "attention-high-long")``.  The cache holds references to those tensors, so an address in the key
 cannot come back as another tensor while the cache lives.  ``valid_for`` recomputes the key; a stale
 cache is rebuilt by ``ensure`` (the sweep calls it before every condition), never read.
 """
@@ -55,11 +56,12 @@ def _frozen_tensors(cm, first):
 def compute_key(cm):
     """The arithmetic the cached rows were computed in: the compute dtype, paired with the fp32 GEMM mode when
     that is not the default ``"highest"`` (``ops.set_float32_matmul_precision``), and with both modes when the
-    fp32 attention mode is not (``ops.set_float32_attention_precision``): ``(dtype, gemm mode, "attention-high")``."""
+    fp32 attention mode is not (``ops.set_float32_attention_precision``): ``(dtype, gemm mode, "attention-high")``,
+    or ``"attention-high-long"`` when its ``long_sequences`` switch is on as well."""
     mode = ops.get_float32_matmul_precision()
     attn = ops.get_float32_attention_precision()
     if attn != "highest":
-        return (cm.compute_dtype, mode, "attention-" + attn)
+        return (cm.compute_dtype, mode, "attention-" + attn + ("-long" if ops.get_float32_attention_long() else ""))
     return cm.compute_dtype if mode == "highest" else (cm.compute_dtype, mode)
 
 

@@ -469,9 +469,10 @@ def _sweep_worker(rank, world, make_model_and_optimizer, criterion, data, condit
         from . import ops
         ops.set_float32_matmul_precision(mode)
     mode = kw.pop("float32_attention", None)
+    long_sequences = kw.pop("float32_attention_long", False)
     if mode is not None:
         from . import ops
-        ops.set_float32_attention_precision(mode)
+        ops.set_float32_attention_precision(mode, long_sequences=long_sequences)
     if devices:
         dev = torch.device("cuda", devices[rank % len(devices)])
         torch.cuda.set_device(dev)
@@ -489,15 +490,16 @@ def launch_sweep(nprocs, make_model_and_optimizer, criterion, data, conditions, 
     must be picklable (module-level).  Returns {rank: [((start, length), csv, source)]}.
     ``cache_visual_prefix``: each worker builds and owns its visual prefix caches (``run_sweep``).
     The workers run in the caller's fp32 GEMM mode (``set_float32_matmul_precision``; ``VIT_F32_MATMUL`` is
-    inherited through the environment as well) and fp32 attention mode (``set_float32_attention_precision``;
-    ``VIT_F32_ATTENTION``)."""
+    inherited through the environment as well) and fp32 attention mode (``set_float32_attention_precision``,
+    its ``long_sequences`` switch included; ``VIT_F32_ATTENTION``, ``VIT_F32_ATTENTION_LONG``)."""
     import torch.multiprocessing as mp
     from . import _lib, ops
     if cache_visual_prefix:
         kw = dict(kw, cache_visual_prefix=True)
     if _lib._lib is not None:  # (a process that never loaded the library cannot have switched the mode)
         kw = dict(kw, float32_matmul=ops.get_float32_matmul_precision(),
-                  float32_attention=ops.get_float32_attention_precision())
+                  float32_attention=ops.get_float32_attention_precision(),
+                  float32_attention_long=ops.get_float32_attention_long())
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     devices = list(gpus) if gpus else []

@@ -431,7 +431,10 @@ int vit_sgd_chunk_bytes(void);
 /* DoRALayer.weight (NEWP:447-463): W[out,in] = (m * (D + (B@A)s) / (||.||_col + 1e-8))^T,
  * and its backward (dm, dA, dB) for AdamW (NEWP:1000-1001).  noise (nullable, [in,out] like D):
  * DoRALayer.forward's train-mode dropout of delta_D (NEWP:465-481), (B@A)s * noise with
- * noise = keep-mask / (1 - p); the backward masks the delta_D gradient the same way. */
+ * noise = keep-mask / (1 - p); the backward masks the delta_D gradient the same way.
+ * All three entry points return hipErrorInvalidValue, before anything is queued, for in <= 0,
+ * out <= 0, r outside 1..64 (LoRA's range) or a null operand; only noise, the forward's nu and
+ * slabs may be null. */
 int vit_dora_weight_fwd(int in, int out, int r, const float* m, const float* A, const float* B, const float* D,
                         float scaling, const float* noise, float* W, float* nu, float* DnT_ws, float* colsq_ws,
                         void* stream);

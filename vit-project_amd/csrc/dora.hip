@@ -136,11 +136,14 @@ extern "C" {
 
 // W [out, in] (f32) from DoRA parameters; DnT_ws >= out*in floats (kept for the
 // backward), colsq_ws >= ceil(in/64)*out floats, nu [out] saved for backward.
+// hipErrorInvalidValue before anything is queued for in <= 0, out <= 0, r outside 1..64 or a null
+// operand other than noise and nu (here and in both backward entry points: noise, slabs).
 int vit_dora_weight_fwd(int in, int out, int r, const float* m, const float* A, const float* Bm, const float* D,
                         float scaling, const float* noise, float* W, float* nu, float* DnT_ws, float* colsq_ws,
                         void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (r > 64 || in <= 0 || out <= 0) return (int)hipErrorInvalidValue;
+  if (r < 1 || r > 64 || in <= 0 || out <= 0) return (int)hipErrorInvalidValue;
+  if (!m || !A || !Bm || !D || !W || !DnT_ws || !colsq_ws) return (int)hipErrorInvalidValue;
   int ty = (in + DT - 1) / DT;
   hipLaunchKernelGGL(dora_tile_kernel, dim3((out + DT - 1) / DT, ty), dim3(256), 0, s, in, out, r, A, Bm, D, scaling,
                      noise, DnT_ws, colsq_ws);
@@ -159,6 +162,8 @@ int vit_dora_weight_bwd_ws(int in, int out, int r, const float* m, const float* 
                            const float* DnT, float scaling, const float* nu, float* dm, float* dA, float* dB,
                            float* sdDnT_ws, float* slabs, int64_t slab_floats, const float* noise, void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  if (r < 1 || r > 64 || in <= 0 || out <= 0) return (int)hipErrorInvalidValue;
+  if (!m || !A || !Bm || !gW || !DnT || !nu || !dm || !dA || !dB || !sdDnT_ws) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(dora_bwd_row_kernel, dim3((out + 3) / 4), dim3(256), 0, s, in, out, gW, DnT, m, nu, scaling,
                      noise, dm, sdDnT_ws);
   VIT_CHECK_LAUNCH();

@@ -21,6 +21,23 @@ from . import _lib as L
 from . import ops
 from ._lib import call, ptr
 
+MAX_R = 64
+
+
+def _check(m, A, Bm, D, noise):
+    if D.dim() != 2 or A.dim() != 2 or Bm.dim() != 2:
+        raise ValueError(f"dora_weight: D {tuple(D.shape)}, A {tuple(A.shape)} and B {tuple(Bm.shape)} must be 2-D")
+    fin, fout = D.shape
+    r = A.shape[0]
+    if not 1 <= r <= MAX_R:
+        raise ValueError(f"dora_weight: rank {r} outside 1..{MAX_R}")
+    if fin < 1 or fout < 1:
+        raise ValueError(f"dora_weight: empty D {tuple(D.shape)}")
+    if tuple(A.shape) != (r, fout) or tuple(Bm.shape) != (fin, r) or tuple(m.shape) != (fout,):
+        raise ValueError(f"dora_weight: A {tuple(A.shape)} / B {tuple(Bm.shape)} / m {tuple(m.shape)} do not fit "
+                         f"D [{fin}, {fout}] (in, out), r = {r}: A [r, out], B [in, r], m [out]")
+    if noise is not None and tuple(noise.shape) != (fin, fout):
+        raise ValueError(f"dora_weight: noise {tuple(noise.shape)} is not D's [{fin}, {fout}]")
 
 
 class _DoraWeightFn(torch.autograd.Function):
@@ -47,6 +64,8 @@ class _DoraWeightFn(torch.autograd.Function):
         fout, fin = DnT.shape
         r = A.shape[0]
         dev = DnT.device
+        if tuple(gW.shape) != (fout, fin):
+            raise ValueError(f"dora_weight backward: gW {tuple(gW.shape)} is not W's [{fout}, {fin}]")
         gW = gW.contiguous().float()
         dm = torch.empty_like(m)
         dA = torch.empty_like(A)
@@ -82,7 +101,9 @@ class _LinearF32Fn(torch.autograd.Function):
 
 def dora_weight(m, A, Bm, D, scaling, noise=None):
     """W [out, in] = ((D + (B@A)*s [* noise]) / (||.||_col + 1e-8) * m)^T  (NEWP:447-463; with the
-    dropout noise of DoRALayer.forward, NEWP:467-468)."""
+    dropout noise of DoRALayer.forward, NEWP:467-468).  D [in, out], A [r, out], B [in, r], m [out], noise None
+    or [in, out], 1 <= r <= 64: ``ValueError`` before anything is queued otherwise."""
+    _check(m, A, Bm, D, noise)
     L.require_gpu(D)
     return _DoraWeightFn.apply(m, A, Bm, D, scaling, noise)
 

@@ -114,6 +114,22 @@ int vit_gemm_f32_precision(int mode);
 int vit_gemm_f32_count(int reset);
 int vit_gemm_f32_split_count(int reset);
 
+/* Pre-split weight images for mode 1 (additive to ABI 10).  In mode 1 both operands are split into hi / lo bf16 in
+ * registers, by every wave in every k-step; a frozen weight's split can be done once.  The image of an f32 matrix
+ * A [rows][red] has A's size and a row pitch of red * 4 bytes: each 128-byte block of 32 reduction values holds
+ * four 16-byte hi chunks, then four lo chunks, and hi chunk g holds as its bf16 element j = 0..7 the hi of
+ * k = 16 (j >> 2) + 4 g + (j & 3); lo chunk g the lo values in the same order.  That is the operand pack the
+ * kernel forms in registers, so a GEMM that reads the image issues the same MFMAs on the same bits: its result is
+ * mode 1's bit for bit.
+ * vit_gemm_f32_weight_image writes the image of W [N][K] (row stride ldw; transpose == 0: N rows x K cells, the
+ * forward's operand) or of W^T (transpose != 0: K rows x N cells, the input gradient's operand).  The reduction
+ * extent (K, or N transposed) must be a multiple of 32, W and img 16-byte aligned, ldw a multiple of 4 and >= K;
+ * otherwise hipErrorInvalidValue with nothing launched.  img holds N * K * 4 bytes and may not overlap W. */
+int vit_gemm_f32_weight_image(int N, int K, const float* W, int64_t ldw, int transpose, void* img, void* stream);
+/* Launches of the f32 MFMA path that read a weight image since the last reset (they also count in
+ * vit_gemm_f32_count and vit_gemm_f32_split_count). */
+int vit_gemm_f32_presplit_count(int reset);
+
 /* Host-only query (no GPU call): rows per launch the bf16 MFMA path uses for a row-contiguous
  * operand of M rows x ld elements (its staging offsets are 32-bit: larger operands are split
  * into row chunks, a multiple of 256 rows each); M when one launch fits, 0 if none does. */
@@ -127,6 +143,12 @@ int vit_gemm_rc_chunk_rows(int M, int64_t ld);
 int vit_linear_fwd(int dtype, int out_dtype, int epi, int M, int N, int K, const void* X, int64_t ldx,
                    const void* W, const float* bias, void* Y, int64_t ldy, const void* resid,
                    void* act_out, void* stream);
+/* The same, with Wimg = the image of W (vit_gemm_f32_weight_image(N, K, W, K, 0, ..) of W's current values).  When
+ * the mode is 1, Wimg is not NULL, dtype is f32 and the call takes the f32 MFMA path, the image alone is read and W
+ * is never dereferenced; the result is vit_linear_fwd's bit for bit.  In every other case this is vit_linear_fwd. */
+int vit_linear_fwd_wimg(int dtype, int out_dtype, int epi, int M, int N, int K, const void* X, int64_t ldx,
+                        const void* W, const float* bias, void* Y, int64_t ldy, const void* resid,
+                        void* act_out, const void* Wimg, void* stream);
 
 /* F.linear input gradient dX = dY W (+ GELU' epilogue) -- autograd of VIT:142.  dbias (optional) =
  * column sums of dX (bias gradient of the Linear that produced dX's forward value, e.g. fc1.bias from
@@ -139,6 +161,11 @@ int vit_linear_fwd(int dtype, int out_dtype, int epi, int M, int N, int K, const
 int vit_linear_dgrad(int dtype, int out_dtype, int epi, int M, int N, int K, const void* dY, int64_t lddy,
                      const void* W, void* dX, int64_t lddx, const void* pre, float* dbias, float* partial,
                      int64_t partial_floats, int defer_reduce, void* stream);
+/* The same, with Wimg = the image of W^T (vit_gemm_f32_weight_image(N, K, W, K, 1, ..)), read in place of W under
+ * the rule of vit_linear_fwd_wimg; dX and the fused column sums are vit_linear_dgrad's bit for bit. */
+int vit_linear_dgrad_wimg(int dtype, int out_dtype, int epi, int M, int N, int K, const void* dY, int64_t lddy,
+                          const void* W, void* dX, int64_t lddx, const void* pre, float* dbias, float* partial,
+                          int64_t partial_floats, int defer_reduce, const void* Wimg, void* stream);
 /* defer_reduce = 1: dbias is not written; `partial` keeps its [ceil(M/64)][K] column-sum
  * partials for the caller to reduce with vit_colreduce (e.g. on another stream, off the
  * input-gradient chain). */

@@ -1,12 +1,17 @@
 """fp32 MFMA GEMM timing at config C3's shapes (CLIP ViT-L/14 visual tower, B=64: M = 64 x 257 rows),
 with and without the stream's stream-K workspace (f32m::gemm_sk_kernel vs one tile per workgroup).
 
-    python tools/bench_f32.py [--batch 64] [--reps 20] [--precision highest|high] [--pairs N] [--json out.jsonl]
+    python tools/bench_f32.py [--batch 64] [--reps 20] [--precision highest|high] [--presplit] [--pairs N]
+                              [--json out.jsonl]
 
 ``--precision`` sets the fp32 GEMM arithmetic (vit_amd.set_float32_matmul_precision; "high" = bf16x3, DESIGN
 §4.22).  ``--pairs N`` times every case N times in "highest" and "high", alternating, in this one process, and
 prints per case the median of each, their ratio and the spread (max - min over median) of each side.  TFLOP/s
 count 2 M N R in both modes.  ``sum`` is a float64 checksum of the case's output (to compare two builds).
+``--presplit`` gives every case the pre-split image of its weight: alone it times "high" reading the
+images; with ``--pairs N`` the two sides are in-loop "high" and pre-split "high" (``high`` / ``presplit``), and each
+case's two outputs are compared bit for bit.  It also times the image pass itself (both forms, three shapes) as GB/s
+of the 8 bytes per element it moves.
 """
 import argparse
 import json
@@ -43,8 +48,9 @@ def main():
     ap.add_argument("--json", default="")
     ap.add_argument("--precision", choices=["highest", "high"], default="highest")
     ap.add_argument("--pairs", type=int, default=0)
+    ap.add_argument("--presplit", action="store_true")
     a = ap.parse_args()
-    ops.set_float32_matmul_precision(a.precision)
+    ops.set_float32_matmul_precision("high" if a.presplit else a.precision)
     dev = torch.device("cuda", 0)
     M, D = a.batch * 257, 1024
     g = torch.Generator(device=dev).manual_seed(0)
@@ -57,18 +63,62 @@ def main():
     dy1 = torch.randn(M, D, device=dev, generator=g)
     pre = torch.empty(M, 4 * D, device=dev)
     act = torch.empty_like(pre)
+    # the weights' images (forward) and their transposes' (input gradient); `img` switches the cases between them
+    wi = {n: ops.weight_image_raw(t) for n, t in w.items()} if a.presplit else {}
+    wt = {n: ops.weight_image_raw(w[n], transposed=True) for n in ("fc1", "fc2")} if a.presplit else {}
+    img = {"on": a.presplit}
+    I = lambda d, n: d[n] if img["on"] else None
     cases = {
-        "fwd qkv (bias)": (lambda: ops.linear_fwd(x, w["qkv"], b["qkv"]), 2 * M * 3 * D * D),
-        "fwd proj (bias)": (lambda: ops.linear_fwd(x, w["proj"], b["proj"]), 2 * M * D * D),
+        "fwd qkv (bias)": (lambda: ops.linear_fwd(x, w["qkv"], b["qkv"], wimg=I(wi, "qkv")), 2 * M * 3 * D * D),
+        "fwd proj (bias)": (lambda: ops.linear_fwd(x, w["proj"], b["proj"], wimg=I(wi, "proj")), 2 * M * D * D),
         "fwd fc1 (bias + QuickGELU pair)": (lambda: ops.linear_fwd(x, w["fc1"], b["fc1"], epi=L.EPI_BIAS_QGELU,
-                                                                   out=pre, act_out=act), 2 * M * 4 * D * D),
-        "fwd fc2 (bias)": (lambda: ops.linear_fwd(h, w["fc2"], b["fc2"]), 2 * M * 4 * D * D),
-        "dgrad fc2 -> dh": (lambda: ops.linear_dgrad(dy1, w["fc2"], out_dtype=torch.float32), 2 * M * 4 * D * D),
-        "dgrad fc1 -> dx": (lambda: ops.linear_dgrad(dy4, w["fc1"], out_dtype=torch.float32), 2 * M * 4 * D * D),
+                                                                   out=pre, act_out=act, wimg=I(wi, "fc1")),
+                                            2 * M * 4 * D * D),
+        "fwd fc2 (bias)": (lambda: ops.linear_fwd(h, w["fc2"], b["fc2"], wimg=I(wi, "fc2")), 2 * M * 4 * D * D),
+        "dgrad fc2 -> dh": (lambda: ops.linear_dgrad(dy1, w["fc2"], out_dtype=torch.float32, wimg=I(wt, "fc2")),
+                            2 * M * 4 * D * D),
+        "dgrad fc1 -> dx": (lambda: ops.linear_dgrad(dy4, w["fc1"], out_dtype=torch.float32, wimg=I(wt, "fc1")),
+                            2 * M * 4 * D * D),
     }
     st = L.stream_ptr(dev)
     out = []
-    if a.pairs:
+    if a.presplit:
+        for N, K in ((1024, 1024), (4096, 1024), (1024, 4096)):
+            src = torch.randn(N, K, device=dev, generator=g)
+            for tr in (False, True):
+                dst = torch.empty((K, N) if tr else (N, K), device=dev)
+                t = timeit(lambda: ops.weight_image_raw(src, tr, out=dst), a.reps)
+                row = {"case": f"image pass [{N},{K}]" + (" transposed" if tr else ""), "us": round(t * 1e6, 1),
+                       "gbs": round(8 * N * K / t / 1e9, 1)}
+                print(json.dumps(row), flush=True)
+                out.append(row)
+    if a.pairs and a.presplit:
+        ops._SK.pop(st, None)
+        ops._streamk(dev)
+        lib = L.lib()
+        for name, (fn, flop) in cases.items():
+            t, outs = {"high": [], "presplit": []}, {}
+            for _ in range(a.pairs):
+                for side in ("high", "presplit"):
+                    img["on"] = side == "presplit"
+                    c0 = lib.vit_gemm_f32_presplit_count(0)
+                    t[side].append(timeit(fn, a.reps))
+                    assert (lib.vit_gemm_f32_presplit_count(0) > c0) == img["on"], (name, side)
+                    r = fn()
+                    outs[side] = (r[0] if isinstance(r, tuple) else r).clone()
+            med = {m: sorted(v)[len(v) // 2] for m, v in t.items()}
+            row = {"case": name, "M": M, "gflop": round(flop / 1e9, 2), "pairs": a.pairs,
+                   "bit_equal": bool(torch.equal(outs["high"].view(torch.int32), outs["presplit"].view(torch.int32)))}
+            for m in t:
+                row[m + "_us"] = round(med[m] * 1e6, 1)
+                row[m + "_tf"] = round(flop / med[m] / 1e12, 1)
+                row[m + "_spread"] = round((max(t[m]) - min(t[m])) / med[m], 4)
+            row["speedup"] = round(med["high"] / med["presplit"], 3)
+            print(json.dumps(row), flush=True)
+            out.append(row)
+        cases = {}
+        ops.set_float32_matmul_precision("highest")
+    elif a.pairs:
         ops._SK.pop(st, None)
         ops._streamk(dev)
         for name, (fn, flop) in cases.items():
@@ -89,7 +139,8 @@ def main():
             out.append(row)
         cases = {}
     for name, (fn, flop) in cases.items():
-        row = {"case": name, "M": M, "gflop": round(flop / 1e9, 2), "precision": a.precision}
+        row = {"case": name, "M": M, "gflop": round(flop / 1e9, 2),
+               "precision": "high, pre-split" if a.presplit else a.precision}
         r = fn()
         row["sum"] = float((r[0] if isinstance(r, tuple) else r).double().sum())
         for mode in ("plain", "streamk"):

@@ -1333,21 +1333,33 @@ static int f32_precision_env() {
   return s && strcmp(s, "high") == 0 ? 1 : 0;
 }
 static int g_f32_split = f32_precision_env();
-static int g_f32_count = 0, g_f32_split_count = 0;
+static int g_f32_count = 0, g_f32_split_count = 0, g_f32_presplit_count = 0;
+
+// SPLIT = 2: Q is the pre-split image of a weight (f32w, RC x RC only)
+template <int PL, int QL, int EPI, typename TO, int SPLIT> static auto f32_plain_kernel() {
+  if constexpr (SPLIT == 2) return &f32w::gemm_kernel<PL, QL, EPI, TO, float, 2>;
+  else return &f32m::gemm_kernel<PL, QL, EPI, TO, float, SPLIT>;
+}
+template <int PL, int QL, int EPI, typename TO, int SPLIT> static auto f32_sk_kernel() {
+  if constexpr (SPLIT == 2) return &f32w::gemm_sk_kernel<PL, QL, EPI, TO, float, 2>;
+  else return &f32m::gemm_sk_kernel<PL, QL, EPI, TO, float, SPLIT>;
+}
 
 template <int PL, int QL, int EPI, typename TO, int SPLIT>
 static int launch_f32_mode(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
                            const Epi& e, hipStream_t s) {
+  static_assert(SPLIT != 2 || (PL == LAY_RC && QL == LAY_RC), "a weight image is read row-contiguous");
+  const auto plain = f32_plain_kernel<PL, QL, EPI, TO, SPLIT>();
+  const auto sk = f32_sk_kernel<PL, QL, EPI, TO, SPLIT>();
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)f32m::gemm_kernel<PL, QL, EPI, TO, float, SPLIT>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, f32m::LDS);
-    (void)hipFuncSetAttribute((const void*)f32m::gemm_sk_kernel<PL, QL, EPI, TO, float, SPLIT>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, f32m::LDS + 16);
+    (void)hipFuncSetAttribute((const void*)plain, hipFuncAttributeMaxDynamicSharedMemorySize, f32m::LDS);
+    (void)hipFuncSetAttribute((const void*)sk, hipFuncAttributeMaxDynamicSharedMemorySize, f32m::LDS + 16);
     attr = true;
   }
   ++g_f32_count;
-  g_f32_split_count += SPLIT;
+  g_f32_split_count += SPLIT != 0;
+  g_f32_presplit_count += SPLIT == 2;
   const int64_t tiles = (int64_t)((M + f32m::BM - 1) / f32m::BM) * ((N + f32m::BN - 1) / f32m::BN);
   const int G = 2 * num_cus();  // two workgroups per CU
   if (split <= 1 && R % f32m::BK == 0 && tiles >= G && ragged_waste(tiles, G) > 0.03) {
@@ -1357,9 +1369,8 @@ static int launch_f32_mode(const void* P, int64_t ldp, const void* Q, int64_t ld
       // tile by k-steps from the start was 2-7 % slower on the tall forwards, round 3; that form and the
       // VIT_GEMM_STREAMK A/B switch were removed in round 5)
       const int dp_rounds = (int)(tiles / G) - 1;
-      hipLaunchKernelGGL((f32m::gemm_sk_kernel<PL, QL, EPI, TO, float, SPLIT>), dim3(G), dim3(f32m::THREADS),
-                         f32m::LDS + 16, s, (const float*)P, ldp, (const float*)Q, ldq, M, N, R, dp_rounds, e,
-                         w->part, w->cnt);
+      hipLaunchKernelGGL(sk, dim3(G), dim3(f32m::THREADS), f32m::LDS + 16, s, (const float*)P, ldp,
+                         (const float*)Q, ldq, M, N, R, dp_rounds, e, w->part, w->cnt);
       VIT_CHECK_LAUNCH();
       return 0;
     }
@@ -1367,10 +1378,19 @@ static int launch_f32_mode(const void* P, int64_t ldp, const void* Q, int64_t ld
   const int r_chunk = r_chunk_for(R, split, f32m::BK);
   const int nz = (R + r_chunk - 1) / r_chunk;
   dim3 grid(((M + f32m::BM - 1) / f32m::BM) * ((N + f32m::BN - 1) / f32m::BN) * nz);
-  hipLaunchKernelGGL((f32m::gemm_kernel<PL, QL, EPI, TO, float, SPLIT>), grid, dim3(f32m::THREADS), f32m::LDS, s,
-                     (const float*)P, ldp, (const float*)Q, ldq, M, N, R, r_chunk, e);
+  hipLaunchKernelGGL(plain, grid, dim3(f32m::THREADS), f32m::LDS, s, (const float*)P, ldp, (const float*)Q, ldq,
+                     M, N, R, r_chunk, e);
   VIT_CHECK_LAUNCH();
   return 0;
+}
+
+// the GEMM classes that read a weight image when one is given: the f32 forward with its epilogues and the
+// input gradient with its (P = X or dY, RC; Q = the image of W or of W^T, RC with row pitch R)
+template <int EPI> constexpr bool wimg_combo(int ql) {
+  if (ql == LAY_RC)
+    return EPI == EPI_STORE || EPI == EPI_RESID || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU ||
+           EPI == EPI_BIAS_GELU_FWD || EPI == EPI_BIAS_QGELU_FWD;
+  return EPI == EPI_STORE || EPI == EPI_GELU_BWD || EPI == EPI_QGELU_BWD;
 }
 
 // the one place every f32 MFMA-path GEMM goes through: forward (every epilogue), input and weight gradient,
@@ -1419,7 +1439,7 @@ template <int PL, int QL, int EPI, typename TO> constexpr bool fast_combo() {
 template <int EPI>
 static int gemm_dispatch(int dtype, int out_dtype, int pl, int ql, int M, int N, int R,
                          const void* P, int64_t ldp, const void* Q, int64_t ldq, int split,
-                         const Epi& e, hipStream_t s, bool allow_fast) {
+                         const Epi& e, hipStream_t s, bool allow_fast, const void* qimg = nullptr) {
   if constexpr (epi_act_only(EPI)) {  // the act-only forms exist for the RC x RC forward alone
     if (pl != LAY_RC || ql != LAY_RC || split > 1) return (int)hipErrorInvalidValue;
   }
@@ -1465,6 +1485,12 @@ static int gemm_dispatch(int dtype, int out_dtype, int pl, int ql, int M, int N,
   }
   if (allow_fast && out_dtype == VIT_F32 && fast_f32_ok(dtype, pl, ql, M, N, R, P, Q, ldp, ldq) && epi_ok &&
       f32_grid_ok(M, N, split)) {
+    // a pre-split image of the weight (vit_linear_fwd_wimg / vit_linear_dgrad_wimg) stands in for Q in "high":
+    // W, or W^T for the input gradient, as RC rows of R cells.  Q is not read then.
+    if constexpr (wimg_combo<EPI>(LAY_RC) || wimg_combo<EPI>(LAY_CR)) {
+      if (qimg && g_f32_split && split <= 1 && pl == LAY_RC && wimg_combo<EPI>(ql) && aligned16(qimg))
+        return launch_f32_mode<LAY_RC, LAY_RC, EPI, float, 2>(P, ldp, qimg, R, M, N, R, 1, e, s);
+    }
     if (pl == LAY_RC && ql == LAY_RC) return launch_f32<LAY_RC, LAY_RC, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
     if constexpr (!epi_act_only(EPI)) {  // (act-only: forward layout only, checked above)
       if (pl == LAY_RC && ql == LAY_CR) return launch_f32<LAY_RC, LAY_CR, EPI, float>(P, ldp, Q, ldq, M, N, R, split, e, s);
@@ -1484,18 +1510,18 @@ static int gemm_dispatch(int dtype, int out_dtype, int pl, int ql, int M, int N,
 
 static int gemm_any(int epi, int dtype, int out_dtype, int pl, int ql, int M, int N, int R,
                     const void* P, int64_t ldp, const void* Q, int64_t ldq, int split, const Epi& e,
-                    hipStream_t s, bool allow_fast = true) {
+                    hipStream_t s, bool allow_fast = true, const void* qimg = nullptr) {
   switch (epi) {
-    case EPI_STORE: return gemm_dispatch<EPI_STORE>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
-    case EPI_BIAS_GELU: return gemm_dispatch<EPI_BIAS_GELU>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
-    case EPI_BIAS_QGELU: return gemm_dispatch<EPI_BIAS_QGELU>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
-    case EPI_RESID: return gemm_dispatch<EPI_RESID>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
-    case EPI_GELU_BWD: return gemm_dispatch<EPI_GELU_BWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
-    case EPI_QGELU_BWD: return gemm_dispatch<EPI_QGELU_BWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
-    case EPI_ACC: return gemm_dispatch<EPI_ACC>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
-    case EPI_PATCH: return gemm_dispatch<EPI_PATCH>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
-    case EPI_BIAS_GELU_FWD: return gemm_dispatch<EPI_BIAS_GELU_FWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
-    case EPI_BIAS_QGELU_FWD: return gemm_dispatch<EPI_BIAS_QGELU_FWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast);
+    case EPI_STORE: return gemm_dispatch<EPI_STORE>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
+    case EPI_BIAS_GELU: return gemm_dispatch<EPI_BIAS_GELU>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
+    case EPI_BIAS_QGELU: return gemm_dispatch<EPI_BIAS_QGELU>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
+    case EPI_RESID: return gemm_dispatch<EPI_RESID>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
+    case EPI_GELU_BWD: return gemm_dispatch<EPI_GELU_BWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
+    case EPI_QGELU_BWD: return gemm_dispatch<EPI_QGELU_BWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
+    case EPI_ACC: return gemm_dispatch<EPI_ACC>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
+    case EPI_PATCH: return gemm_dispatch<EPI_PATCH>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
+    case EPI_BIAS_GELU_FWD: return gemm_dispatch<EPI_BIAS_GELU_FWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
+    case EPI_BIAS_QGELU_FWD: return gemm_dispatch<EPI_BIAS_QGELU_FWD>(dtype, out_dtype, pl, ql, M, N, R, P, ldp, Q, ldq, split, e, s, allow_fast, qimg);
   }
   return (int)hipErrorInvalidValue;
 }
@@ -1549,6 +1575,31 @@ int vit_gemm_f32_precision(int mode) {
 // Host-side launch counts since the last reset: every launch of the f32 MFMA path / those in mode 1.
 int vit_gemm_f32_count(int reset) { const int c = g_f32_count; if (reset) g_f32_count = 0; return c; }
 int vit_gemm_f32_split_count(int reset) { const int c = g_f32_split_count; if (reset) g_f32_split_count = 0; return c; }
+// ... and those that read a pre-split weight image (they count in both of the above as well)
+int vit_gemm_f32_presplit_count(int reset) { const int c = g_f32_presplit_count; if (reset) g_f32_presplit_count = 0; return c; }
+
+// The pre-split image of an f32 weight for the "high" GEMMs (gemm_f32.inc, SPLIT = 2), W [N][K] with
+// row stride ldw: transpose == 0 gives the image of W (N rows x K cells of 4 bytes, contiguous: the forward's Q),
+// transpose != 0 that of W^T (K rows x N cells: the input gradient's Q, reduced over N).  The reduction extent
+// (K, or N transposed) must be a multiple of 32, W and img 16-byte aligned and ldw a multiple of 4 (>= K);
+// anything else returns hipErrorInvalidValue and launches nothing.  img may not overlap W.
+int vit_gemm_f32_weight_image(int N, int K, const float* W, int64_t ldw, int transpose, void* img, void* stream) {
+  const int red = transpose ? N : K, rows = transpose ? K : N;
+  if (N <= 0 || K <= 0 || red % 32 || W == nullptr || img == nullptr || !aligned16(W) || !aligned16(img) || ldw % 4 ||
+      ldw < K)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  if (transpose) {
+    hipLaunchKernelGGL(f32w::weight_image_t_kernel, dim3((N + 63) / 64, (K + 31) / 32), dim3(256), 0, s, W, ldw, N, K,
+                       (char*)img);
+  } else {
+    const int64_t lanes = (int64_t)rows * (red / 32) * 4;
+    hipLaunchKernelGGL(f32w::weight_image_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, W, ldw, rows,
+                       red, (char*)img);
+  }
+  VIT_CHECK_LAUNCH();
+  return 0;
+}
 
 // Raw dispatcher (exported for tests/benchmarks of individual layouts).
 int vit_gemm(int dtype, int out_dtype, int p_layout, int q_layout, int epi, int M, int N, int R,
@@ -1595,12 +1646,21 @@ int vit_gemm_splitk(int p_layout, int q_layout, int M, int N, int R, const float
 //   epi = EPI_STORE (Y out_dtype), EPI_BIAS_GELU / EPI_BIAS_QGELU (Y = act'(pre), act_out = act(pre)),
 //   EPI_RESID (Y f32 = resid + X W^T + b; Y may alias resid),
 //   EPI_BIAS_GELU_FWD / EPI_BIAS_QGELU_FWD (Y = act(pre), the pair's act_out bits; act_out ignored, may be NULL).
+// vit_linear_fwd_wimg: the same with Wimg = vit_gemm_f32_weight_image(N, K, W, K, 0) of the current W.  When the
+// call takes the f32 MFMA path in "high" (vit_gemm_f32_precision(1)) and Wimg is not NULL, the image alone is read
+// (W is never dereferenced) and the result is vit_linear_fwd's bit for bit; in every other case it is vit_linear_fwd.
+int vit_linear_fwd_wimg(int dtype, int out_dtype, int epi, int M, int N, int K, const void* X, int64_t ldx,
+                        const void* W, const float* bias, void* Y, int64_t ldy, const void* resid,
+                        void* act_out, const void* Wimg, void* stream) {
+  Epi e = make_epi();
+  e.C = Y; e.ldc = ldy; e.bias = bias; e.aux = resid; e.ld_aux = ldy; e.aux_out = act_out;
+  return gemm_any(epi, dtype, out_dtype, LAY_RC, LAY_RC, M, N, K, X, ldx, W, K, 1, e, (hipStream_t)stream, true,
+                  dtype == VIT_F32 ? Wimg : nullptr);
+}
 int vit_linear_fwd(int dtype, int out_dtype, int epi, int M, int N, int K, const void* X, int64_t ldx,
                    const void* W, const float* bias, void* Y, int64_t ldy, const void* resid,
                    void* act_out, void* stream) {
-  Epi e = make_epi();
-  e.C = Y; e.ldc = ldy; e.bias = bias; e.aux = resid; e.ld_aux = ldy; e.aux_out = act_out;
-  return gemm_any(epi, dtype, out_dtype, LAY_RC, LAY_RC, M, N, K, X, ldx, W, K, 1, e, (hipStream_t)stream);
+  return vit_linear_fwd_wimg(dtype, out_dtype, epi, M, N, K, X, ldx, W, bias, Y, ldy, resid, act_out, nullptr, stream);
 }
 
 // Linear input gradient: dX[M,K] = dY[M,N] W[N,K]  (epi EPI_STORE or *_GELU_BWD: times the
@@ -1613,9 +1673,11 @@ int vit_linear_dgrad_partial_floats(int M, int K) {
   return (int)((int64_t)rows * K + colreduce_scratch_floats(rows, K));
 }
 
-int vit_linear_dgrad(int dtype, int out_dtype, int epi, int M, int N, int K, const void* dY, int64_t lddy,
-                     const void* W, void* dX, int64_t lddx, const void* pre, float* dbias, float* partial,
-                     int64_t partial_floats, int defer_reduce, void* stream) {
+// vit_linear_dgrad_wimg: Wimg = vit_gemm_f32_weight_image(N, K, W, K, 1), the image of W^T; read in place of W
+// under the rule of vit_linear_fwd_wimg.
+int vit_linear_dgrad_wimg(int dtype, int out_dtype, int epi, int M, int N, int K, const void* dY, int64_t lddy,
+                          const void* W, void* dX, int64_t lddx, const void* pre, float* dbias, float* partial,
+                          int64_t partial_floats, int defer_reduce, const void* Wimg, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Epi e = make_epi();
   e.C = dX; e.ldc = lddx; e.aux = pre; e.ld_aux = lddx;
@@ -1629,7 +1691,8 @@ int vit_linear_dgrad(int dtype, int out_dtype, int epi, int M, int N, int K, con
   const bool fast = any_fast_ok(dtype, LAY_RC, LAY_CR, M, K, N, dY, W, lddy, K) && epi_fast_ok(epi, dtype, out_dtype, e) &&
                     (dtype == VIT_BF16 || (out_dtype == VIT_F32 && f32_grid_ok(M, K, 1)));
   if (!fast) e.csum = nullptr;
-  int rc = gemm_any(epi, dtype, out_dtype, LAY_RC, LAY_CR, M, K, N, dY, lddy, W, K, 1, e, s);
+  int rc = gemm_any(epi, dtype, out_dtype, LAY_RC, LAY_CR, M, K, N, dY, lddy, W, K, 1, e, s, true,
+                    dtype == VIT_F32 ? Wimg : nullptr);
   if (rc || !dbias || M <= 0) return rc;
   if (!fast) {  // generic path: column sums of the stored output
     if (out_dtype == VIT_BF16)
@@ -1644,6 +1707,13 @@ int vit_linear_dgrad(int dtype, int out_dtype, int epi, int M, int N, int K, con
   launch_colreduce(partial, rows, K, dbias, 0, s, partial + (int64_t)rows * K);
   VIT_CHECK_LAUNCH();
   return 0;
+}
+
+int vit_linear_dgrad(int dtype, int out_dtype, int epi, int M, int N, int K, const void* dY, int64_t lddy,
+                     const void* W, void* dX, int64_t lddx, const void* pre, float* dbias, float* partial,
+                     int64_t partial_floats, int defer_reduce, void* stream) {
+  return vit_linear_dgrad_wimg(dtype, out_dtype, epi, M, N, K, dY, lddy, W, dX, lddx, pre, dbias, partial,
+                               partial_floats, defer_reduce, nullptr, stream);
 }
 
 // Column reduction out[N] (+)= sum_z part[z][N] (second stage of fused bias gradients);

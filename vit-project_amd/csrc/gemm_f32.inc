@@ -35,6 +35,15 @@
 // bf16 range gives hi = +-inf, lo = -+inf; either way the element is NaN where the f32 form gives +-inf.
 // The setting is "at most bf16x3": GEMMs that do not take this path run the generic scalar-FMA kernel
 // and are exact f32 in either mode.
+//
+// SPLIT = 2 (namespace f32w below, DESIGN 4.25): SPLIT = 1 with Q read from a pre-split image of a weight,
+// built once per weight version by f32w::weight_image_kernel.  A row's 128-byte k-block holds four hi chunks,
+// then four lo chunks; hi chunk g holds the bf16 hi of k = 16 (j >> 2) + 4 g + (j & 3) as element j = 0..7 --
+// what split8 packs from the two fragment reads (h = 0, 1) of lane group g -- and lo chunk g the lo values in
+// the same order.  The image has the f32 matrix's row pitch and size, stage<LAY_RC> copies it unchanged, and
+// the reads frag<LAY_RC>(.., h = 0) / (.., h = 1) (chunks g and 4 + g) ARE Q's hi / lo packs: no VALU work
+// for Q, P split as in SPLIT = 1, the same three MFMAs on the same operand bits in the same order, so the
+// result is SPLIT = 1's bit for bit.
 namespace f32m {
 
 constexpr int BM = 128, BN = 128, BK = 32, THREADS = 256, WAVES = 4, S = 2;
@@ -118,7 +127,32 @@ __device__ __forceinline__ void mainloop(const float* __restrict__ P, int64_t ld
     big::lds_barrier();
     const bool more = kt + 1 < ke;
     const uint32_t cur = big::lds_addr(smem + (kt % S) * STAGE);
-    if constexpr (SPLIT) {
+    if constexpr (SPLIT == 2) {
+      static_assert(QL == LAY_RC, "the pre-split image is row-contiguous");
+      // Q is a pre-split image: its h = 0 / h = 1 reads are the hi / lo packs.  Issue and read order as below.
+      f32x4 pf[2][AI], qf[2][AJ];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (more) issue(kt + 1, h + 1);
+#pragma unroll
+        for (int b = 0; b < AJ; ++b) qf[h][b] = frag<QL, BN>(cur + PIMG, wj * AJ + b, h, lane);
+#pragma unroll
+        for (int a = 0; a < AI; ++a) pf[h][a] = frag<PL, BM>(cur, wi * AI + a, h, lane);
+      }
+      big::lgkm_wait0();
+#pragma unroll
+      for (int a = 0; a < AI; ++a) {
+        bf16x8 ph, pl;
+        split8(pf[0][a], pf[1][a], ph, pl);
+#pragma unroll
+        for (int b = 0; b < AJ; ++b) {
+          const bf16x8 qh = __builtin_bit_cast(bf16x8, qf[0][b]), ql = __builtin_bit_cast(bf16x8, qf[1][b]);
+          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ql, ph, acc[a][b], 0, 0, 0);  // P_hi Q_lo
+          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qh, pl, acc[a][b], 0, 0, 0);  // P_lo Q_hi
+          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qh, ph, acc[a][b], 0, 0, 0);  // P_hi Q_hi
+        }
+      }
+    } else if constexpr (SPLIT) {
       // both halves' fragments before any MFMA; the next stage's P pieces before the first half's reads,
       // its Q pieces before the second's (the same split issue)
       f32x4 pf[2][AI], qf[2][AJ];
@@ -178,123 +212,65 @@ __device__ __forceinline__ void epilogue(const Epi& e, const f32x4 (&acc)[AI][AJ
   VIT_EPI_FRAG(AI, AJ, i0 + wi * 64, j0 + wj * 64, )
 }
 
-template <int PL, int QL, int EPI, typename TO, typename TA, int SPLIT>
-__global__ __launch_bounds__(THREADS, 2) void gemm_kernel(const float* __restrict__ P, int64_t ldp,
-                                                          const float* __restrict__ Q, int64_t ldq, int M, int N,
-                                                          int R, int r_chunk, Epi e) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tiles_j = (N + BN - 1) / BN;
-  const int tiles = ((M + BM - 1) / BM) * tiles_j;
-  const int w = big::xcd_remap(blockIdx.x, gridDim.x);
-  const int z = w / tiles, t = w - z * tiles;
-  const int ti = t / tiles_j, tj = t - ti * tiles_j;
-  const int i0 = ti * BM, j0 = tj * BN;
-  const int rb = z * r_chunk;
-  const int re = min(R, rb + r_chunk);
-  const int nk = (re - rb) / BK;
-  f32x4 acc[AI][AJ];
-#pragma unroll
-  for (int a = 0; a < AI; ++a)
-#pragma unroll
-    for (int b = 0; b < AJ; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  mainloop<PL, QL, SPLIT>(P, ldp, Q, ldq, M, N, i0, j0, rb, 0, nk, acc, smem, wave, lane);
-  epilogue<EPI, TO, TA>(e, acc, M, N, i0, j0, z, wave, lane);
-}
-
-// Stream-K form (one split, R % BK == 0) for tile counts that leave a ragged last round (C3's
-// 64 x 257 = 16 448 rows are 128.5 row tiles: 1032 / 3096 / 4128 tiles on 512 workgroup slots).
-// G persistent workgroups first run `dp_rounds` tile-aligned rounds (tile r*G + w: every workgroup
-// starts its tile at k = 0 together with the workgroups that share its operand blocks, so they hit in
-// L2 as a plain launch does), then share the remaining tiles x nk k-steps equally.  That remainder is
-// at least G tiles, so each workgroup holds at least nk k-steps and a tile is cut at most once, at the
-// start of workgroup b (boundary b): its piece 0 (k < cut, from workgroup b-1) and piece 1 (from b)
-// are published as f32 fragment images in part[b][piece]; the workgroup that draws the boundary's
-// second ticket adds them in piece order (agent-scope release / acquire, cdna_hip_programming.md §5
-// "In-launch split-K reduction") and runs the tile's epilogue.  Sums in a fixed order: the result does
-// not depend on arrival order.  (Sharing all k-steps from the start measured 2-7 % slower on the tall
-// forwards: co-resident workgroups sat at different k offsets of the blocks they share.)
-template <int PL, int QL, int EPI, typename TO, typename TA, int SPLIT>
-__global__ __launch_bounds__(THREADS, 2) void gemm_sk_kernel(const float* __restrict__ P, int64_t ldp,
-                                                             const float* __restrict__ Q, int64_t ldq, int M, int N,
-                                                             int R, int dp_rounds, Epi e,
-                                                             float* __restrict__ part, int* __restrict__ cnt) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tiles_j = (N + BN - 1) / BN;
-  const int tiles = ((M + BM - 1) / BM) * tiles_j;
-  const int nk = R / BK;
-  const int G = gridDim.x, w = big::xcd_remap(blockIdx.x, G);
-  for (int r = 0; r < dp_rounds; ++r) {  // tile-aligned rounds
-    const int t = r * G + w;
-    const int ti = t / tiles_j, tj = t - ti * tiles_j;
-    f32x4 acc[AI][AJ];
-#pragma unroll
-    for (int a = 0; a < AI; ++a)
-#pragma unroll
-      for (int b = 0; b < AJ; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    __syncthreads();  // the previous tile's LDS reads are done before the ring restarts
-    mainloop<PL, QL, SPLIT>(P, ldp, Q, ldq, M, N, ti * BM, tj * BN, 0, 0, nk, acc, smem, wave, lane);
-    epilogue<EPI, TO, TA>(e, acc, M, N, ti * BM, tj * BN, 0, wave, lane);
-  }
-  const int tbase = dp_rounds * G;
-  const int64_t W = (int64_t)(tiles - tbase) * nk;
-  const int64_t s0 = (int64_t)w * W / G, s1 = (int64_t)(w + 1) * W / G;
-  constexpr int PIECE = BM * BN;  // floats of one fragment image
-  int* flag = reinterpret_cast<int*>(smem + LDS);  // one int past the ring (dynamic LDS holds it)
-  for (int64_t s = s0; s < s1;) {
-    const int tl = (int)(s / nk), k0 = (int)(s - (int64_t)tl * nk);
-    const int t = tbase + tl;
-    const int k1 = (int)min((int64_t)nk, k0 + (s1 - s));
-    const int ti = t / tiles_j, tj = t - ti * tiles_j;
-    const int i0 = ti * BM, j0 = tj * BN;
-    f32x4 acc[AI][AJ];
-#pragma unroll
-    for (int a = 0; a < AI; ++a)
-#pragma unroll
-      for (int b = 0; b < AJ; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    __syncthreads();  // the previous segment's LDS reads are done before the ring restarts
-    mainloop<PL, QL, SPLIT>(P, ldp, Q, ldq, M, N, i0, j0, 0, k0, k1, acc, smem, wave, lane);
-    s += k1 - k0;
-    if (k0 == 0 && k1 == nk) {
-      epilogue<EPI, TO, TA>(e, acc, M, N, i0, j0, 0, wave, lane);
-      continue;
-    }
-    // a cut tile: piece 0 ends at the start of workgroup w + 1, piece 1 starts at the start of w
-    const int b = k0 == 0 ? w + 1 : w, piece = k0 == 0 ? 0 : 1;
-    float* mine = part + ((int64_t)b * 2 + piece) * PIECE + tid * 4;
-#pragma unroll
-    for (int a = 0; a < AI; ++a)
-#pragma unroll
-      for (int c = 0; c < AJ; ++c)
-        *reinterpret_cast<f32x4*>(mine + (a * AJ + c) * THREADS * 4) = acc[a][c];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      *flag = __hip_atomic_fetch_add(cnt + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (*flag != 1) continue;  // the other piece finishes the tile
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(cnt + b, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const float* other = part + ((int64_t)b * 2 + (1 - piece)) * PIECE + tid * 4;
-#pragma unroll
-    for (int a = 0; a < AI; ++a)
-#pragma unroll
-      for (int c = 0; c < AJ; ++c) {
-        const f32x4 o = *reinterpret_cast<const f32x4*>(other + (a * AJ + c) * THREADS * 4);
-        acc[a][c] = piece == 0 ? acc[a][c] + o : o + acc[a][c];  // piece 0 + piece 1
-      }
-    epilogue<EPI, TO, TA>(e, acc, M, N, i0, j0, 0, wave, lane);
-  }
-}
+#include "gemm_f32_kernels.inc"
 
 }  // namespace f32m
+
+// The kernels that read a pre-split weight image as Q (instantiated with PL = QL = LAY_RC, SPLIT = 2 only), and the
+// pass that writes one.  A namespace of their own: the f32m kernels are the SPLIT = 0 / 1 pairs and nothing else.
+namespace f32w {
+
+using namespace f32m;
+
+#include "gemm_f32_kernels.inc"
+
+// img (rows x red cells of 4 bytes, contiguous) = the pre-split image of A, where A = W [rows][red] (row stride
+// ldw) or, TRANSPOSE, A = W^T of W [red][rows].  red % 32 == 0.  One lane per (row, 32-deep k-block, lane group
+// g): the two f32x4 the GEMM's lane group g would read (k = 4g.. and 16 + 4g..) through split8 into hi chunk g
+// and lo chunk g.  Memory-bound, run once per weight version.
+__global__ __launch_bounds__(256) void weight_image_kernel(const float* __restrict__ W, int64_t ldw, int rows,
+                                                           int red, char* __restrict__ img) {
+  const int kbs = red / 32;
+  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int g = (int)(id & 3);
+  const int64_t blk = id >> 2;
+  if (blk >= (int64_t)rows * kbs) return;
+  const int row = (int)(blk / kbs), kb = (int)(blk - (int64_t)row * kbs);
+  const float* src = W + (int64_t)row * ldw + kb * 32 + 4 * g;
+  const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 16);
+  bf16x8 hi, lo;
+  split8(x0, x1, hi, lo);
+  char* dst = img + ((int64_t)row * red + kb * 32) * 4 + 16 * g;
+  *reinterpret_cast<bf16x8*>(dst) = hi;
+  *reinterpret_cast<bf16x8*>(dst + 64) = lo;
+}
+
+// the transposed form through an LDS tile of 64 reduction rows (n) x 32 image rows (k): 128-byte row pieces
+// in, 256-byte image-row pieces out
+__global__ __launch_bounds__(256) void weight_image_t_kernel(const float* __restrict__ W, int64_t ldw, int red,
+                                                             int rows, char* __restrict__ img) {
+  __shared__ float tile[64][33];
+  const int tid = threadIdx.x;
+  const int n0 = blockIdx.x * 64, k0 = blockIdx.y * 32;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int n = (tid >> 5) + 8 * u, k = tid & 31;
+    tile[n][k] = (n0 + n < red && k0 + k < rows) ? W[(int64_t)(n0 + n) * ldw + k0 + k] : 0.f;
+  }
+  __syncthreads();
+  const int k = tid >> 3, nb = (tid >> 2) & 1, g = tid & 3;
+  if (k0 + k >= rows || n0 + nb * 32 >= red) return;  // red % 32 == 0: a k-block is whole or absent
+  f32x4 x0, x1;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    x0[t] = tile[nb * 32 + 4 * g + t][k];
+    x1[t] = tile[nb * 32 + 16 + 4 * g + t][k];
+  }
+  bf16x8 hi, lo;
+  split8(x0, x1, hi, lo);
+  char* dst = img + ((int64_t)(k0 + k) * red + n0 + nb * 32) * 4 + 16 * g;
+  *reinterpret_cast<bf16x8*>(dst) = hi;
+  *reinterpret_cast<bf16x8*>(dst + 64) = lo;
+}
+
+}  // namespace f32w

@@ -11,6 +11,7 @@ from .optim import FusedSGD, FusedAdamW, CosineAnnealingLRWithWarmup
 from .dora import DoRALayer, dora_weight
 from .lora import LoRALayer, lora_weight
 from .ops import set_float32_matmul_precision, get_float32_matmul_precision
+from .ops import get_float32_matmul_presplit, weight_image_bytes
 from .ops import set_float32_attention_precision, get_float32_attention_precision, get_float32_attention_long
 from . import rsa
 from . import clip
@@ -29,7 +30,8 @@ __all__ = ["VisionTransformer", "create_model", "cross_entropy", "set_wgrad_over
            "set_cls_tail", "block_forward_only", "evaluate", "EvalMeter", "validate", "resample_abs_pos_embed", "adapt_state_dict",
            "prefix_cache", "VisualPrefixCache", "LoRALayer", "lora_weight", "apply_lora_to_ViT", "unfreeze_lora_layers",
            "set_float32_matmul_precision", "get_float32_matmul_precision", "set_float32_attention_precision",
-           "get_float32_attention_precision", "get_float32_attention_long"]
+           "get_float32_attention_precision", "get_float32_attention_long", "get_float32_matmul_presplit",
+           "weight_image_bytes"]
 
 
 def load_library(path=None):

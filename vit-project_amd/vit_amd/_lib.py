@@ -36,6 +36,10 @@ SIGNATURES = {
     "vit_gemm_f32_precision": [i32],
     "vit_gemm_f32_count": [i32],
     "vit_gemm_f32_split_count": [i32],
+    "vit_gemm_f32_presplit_count": [i32],
+    "vit_gemm_f32_weight_image": [i32, i32, vp, i64, i32, vp, vp],
+    "vit_linear_fwd_wimg": [i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp],
+    "vit_linear_dgrad_wimg": [i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, vp, vp],
     "vit_gemm_rc_chunk_rows": [i32, i64],
     "vit_gemm": [i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, vp],
     "vit_linear_fwd": [i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, vp],

@@ -143,14 +143,18 @@ class _Side:
 
 
 class _Shadowed:
-    """Registry of bf16 shadows for GEMM weights."""
+    """Registry of bf16 shadows for GEMM weights, and of the fp32 weights that may hold pre-split images
+    (``ops.weight_image``)."""
 
     def __init__(self):
         self.pairs = []  # (param, shadow)
+        self.f32 = []    # fp32 GEMM weights: images are built on first use by the GEMMs' callers
 
     def add(self, p: nn.Parameter, dtype):
         if dtype == torch.float32:
             p._vit_shadow = None
+            ops.register_weight_image(p)
+            self.f32.append(p)
             return
         sh = torch.empty(p.shape, dtype=dtype, device=p.device)
         p._vit_shadow = sh
@@ -158,6 +162,8 @@ class _Shadowed:
         self.pairs.append(p)
 
     def refresh(self):
+        if self.f32 and not ops.get_float32_matmul_presplit():
+            ops.drop_weight_images(self.f32)
         for p in self.pairs:
             if p._vit_shadow.device != p.device or p._vit_shadow.shape != p.shape:
                 p._vit_shadow = torch.empty(p.shape, dtype=p._vit_shadow.dtype, device=p.device)
@@ -320,6 +326,8 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
     act = torch.empty(Mt, F, dtype=T, device=dev)
     dact = None if fwd_only else torch.empty(Mt, F, dtype=T, device=dev)
     Wqkv, Wproj, W1, W2 = _wt(qkvw, T), _wt(projw, T), _wt(fc1w, T), _wt(fc2w, T)
+    # pre-split images of the fp32 weights (None unless set_float32_matmul_precision("high", presplit_weights=True))
+    Iqkv, Iproj, I1, I2 = (ops.weight_image(p, T) for p in (qkvw, projw, fc1w, fc2w))
     causal = bool(cfg.get("causal", False))
     attn_fp8 = bool(cfg.get("attn_fp8", False))  # forward-only blocks (frozen prefix, no-grad passes)
     attn_fp8_long = bool(cfg.get("attn_fp8_long", False))  # past 320 tokens: the streamed fp8 kernel
@@ -349,8 +357,8 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
 
     def fc1(sl):
         if fwd_only:
-            return lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=act[sl])
-        return lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=dact[sl], act_out=act[sl])
+            return lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=act[sl], wimg=I1)
+        return lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=dact[sl], act_out=act[sl], wimg=I1)
 
     def ln1(sl):
         if pend is not None:
@@ -363,14 +371,14 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
         sl = slice(b0 * N, b1 * N)
         steps = [
             ln1(sl),
-            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
                                  fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre),
-            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), out=pb[sl]),
+            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), out=pb[sl], wimg=Iproj),
             lambda: ops.add_layer_norm_fwd(x2[sl], pb[sl], xm[sl], n2w.detach(), n2b.detach(), eps, out=h2[sl],
                                            mean=m2[sl], rstd=r2[sl]),
             fc1(sl),
-            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), out=yb[sl]),
+            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), out=yb[sl], wimg=I2),
         ]
         if cfg.get("resid_last"):
             steps.append(lambda: ops.add_layer_norm_fwd(xm[sl], yb[sl], xo[sl]))
@@ -382,7 +390,7 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
         sl, cs = slice(b0 * N, b1 * N), slice(b0, b1)
         steps = [
             ln1(sl),
-            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv),
         ]
         if rt:  # the query at each sequence's live row alone, into the compact o; then that row of the stream
             steps += [
@@ -397,22 +405,22 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
             steps.append(lambda: ops.sdpa_fwd_cls(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N]))
         if rs is not None:
             steps += [
-                lambda: ops.linear_fwd(o_cls[cs], Wproj, projb.detach(), out=pb[cs]),
+                lambda: ops.linear_fwd(o_cls[cs], Wproj, projb.detach(), out=pb[cs], wimg=Iproj),
                 lambda: ops.add_layer_norm_fwd(x_cls[cs], pb[cs], xm[cs], n2w.detach(), n2b.detach(), eps,
                                                out=h2[cs], mean=m2[cs], rstd=r2[cs]),
                 fc1(cs),
-                lambda: ops.linear_fwd(act[cs], W2, fc2b.detach(), out=yb[cs]),
+                lambda: ops.linear_fwd(act[cs], W2, fc2b.detach(), out=yb[cs], wimg=I2),
                 lambda: ops.add_layer_norm_fwd(xm[cs], yb[cs], xo[cs]),
             ]
         else:
             if not rt:
                 steps.append(lambda: ops.pad_cols(x_cls[cs], D, out=xc[cs]))
             steps += [
-                lambda: ops.linear_fwd(o_cls[cs], Wproj, projb.detach(), epi=L.EPI_RESID, resid=xc[cs], out=xm[cs]),
+                lambda: ops.linear_fwd(o_cls[cs], Wproj, projb.detach(), epi=L.EPI_RESID, resid=xc[cs], out=xm[cs], wimg=Iproj),
                 lambda: ops.layer_norm_fwd(xm[cs], n2w.detach(), n2b.detach(), eps, T, out=h2[cs], mean=m2[cs],
                                            rstd=r2[cs]),
                 fc1(cs),
-                lambda: ops.linear_fwd(act[cs], W2, fc2b.detach(), epi=L.EPI_RESID, resid=xm[cs], out=xo[cs]),
+                lambda: ops.linear_fwd(act[cs], W2, fc2b.detach(), epi=L.EPI_RESID, resid=xm[cs], out=xo[cs], wimg=I2),
             ]
         return steps
 
@@ -427,14 +435,14 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
         return [
             lambda: ops.layer_norm_fwd(x2[sl], n1w.detach(), n1b.detach(), eps, T, out=h1[sl], mean=m1[sl],
                                        rstd=r1[sl]),
-            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl]),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
                                  fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre),
-            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), epi=L.EPI_RESID, resid=x2[sl], out=xm[sl]),
+            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), epi=L.EPI_RESID, resid=x2[sl], out=xm[sl], wimg=Iproj),
             lambda: ops.layer_norm_fwd(xm[sl], n2w.detach(), n2b.detach(), eps, T, out=h2[sl], mean=m2[sl],
                                        rstd=r2[sl]),
             fc1(sl),
-            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), epi=L.EPI_RESID, resid=xm[sl], out=xo[sl]),
+            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), epi=L.EPI_RESID, resid=xm[sl], out=xo[sl], wimg=I2),
         ]
 
     def run(steps):
@@ -697,13 +705,13 @@ class _BlockFn(torch.autograd.Function):
         dx = None
         if need_mlp_in:
             dpre = ops.linear_dgrad(dxo_c, W2, out_dtype=T, epi=gelu_bwd, pre=dact, dbias=g[10], reduce_on=rb,
-                                    part_rows=dg_rows)
+                                    part_rows=dg_rows, wimg=ops.weight_image(fc2w, T, transposed=True))
             if pair_mlp:
                 side.run(lambda: ops.linear_wgrad_pair((dxo_c, act, g[11]), (dpre, h2, g[9]), rbw, split=sp_mlp))
             elif ng[9]:
                 side.run(lambda: ops.linear_wgrad(dpre, h2, out=g[9], reduce_on=rbw))
         if any(ng[0:9]):
-            dh2 = ops.linear_dgrad(dpre, W1, out_dtype=T)
+            dh2 = ops.linear_dgrad(dpre, W1, out_dtype=T, wimg=ops.weight_image(fc1w, T, transposed=True))
             dxm = torch.empty(Mt, D, dtype=torch.float32, device=dev)
             dxm_c = dxm if T == torch.float32 else torch.empty(Mt, D, dtype=T, device=dev)
             ops.layer_norm_bwd(xm, D, dh2, n2w.detach(), m2, r2, dxm, D, Mt, dres=dxo, ldres=D,
@@ -721,7 +729,7 @@ class _BlockFn(torch.autograd.Function):
             if ng[5] and not pair_attn:
                 side.run(lambda: ops.linear_wgrad(dxm_c, o_w, out=g[5], split=sp_attn, tail=tail, reduce_on=rbw))
             if need_attn:
-                do = ops.linear_dgrad(dxm_c, Wproj, out_dtype=T)
+                do = ops.linear_dgrad(dxm_c, Wproj, out_dtype=T, wimg=ops.weight_image(projw, T, transposed=True))
                 if a1:  # the class rows of dO, P rows apart, straight to the one-query backward
                     dqkv = ops.sdpa_cls1_bwd(qkv, o, do.view(B, P * D)[:, :D], lse, B, H, N)
                 else:
@@ -733,7 +741,7 @@ class _BlockFn(torch.autograd.Function):
                 elif ng[3]:
                     side.run(lambda: ops.linear_wgrad(dqkv, h1, out=g[3], split=sp_attn, tail=tail, reduce_on=rbw))
             if need_h1:
-                dh1 = ops.linear_dgrad(dqkv, Wqkv, out_dtype=T)
+                dh1 = ops.linear_dgrad(dqkv, Wqkv, out_dtype=T, wimg=ops.weight_image(qkvw, T, transposed=True))
                 dx = torch.empty(M, D, dtype=torch.float32, device=dev)
                 if compact_np:
                     dx_c = torch.empty(B * compact_np, D, dtype=T, device=dev)

@@ -78,10 +78,12 @@ def register_capture_stream(stream, device=None):
     _streamk(stream.device if device is None else device, stream)
 
 
-def linear_fwd(x2d, w, bias=None, epi=L.EPI_STORE, out=None, out_dtype=None, resid=None, act_out=None):
+def linear_fwd(x2d, w, bias=None, epi=L.EPI_STORE, out=None, out_dtype=None, resid=None, act_out=None, wimg=None):
     """y = epi(x @ w^T + bias).  x2d [M,K] (row stride x2d.stride(0)), w [N,K] contiguous.
     EPI_BIAS_GELU / EPI_BIAS_QGELU return (act'(pre), act(pre)) with pre = x @ w^T + bias;
-    EPI_BIAS_GELU_FWD / EPI_BIAS_QGELU_FWD (no backward follows) return act(pre) alone, the same bits."""
+    EPI_BIAS_GELU_FWD / EPI_BIAS_QGELU_FWD (no backward follows) return act(pre) alone, the same bits.
+    ``wimg``: the pre-split image of ``w`` (:func:`weight_image`), read in its place by the fp32 "high" MFMA
+    kernels -- the same bits."""
     L.require_gpu(x2d)
     M, K = x2d.shape
     N = w.shape[0]
@@ -101,8 +103,13 @@ def linear_fwd(x2d, w, bias=None, epi=L.EPI_STORE, out=None, out_dtype=None, res
         assert resid.stride(0) == out.stride(0)
     if x2d.dtype == torch.float32:
         _streamk(x2d.device)
-    call("vit_linear_fwd", L.dt(x2d), L.dt(out), epi, M, N, K, ptr(x2d), x2d.stride(0), ptr(w), ptr(bias),
-         ptr(out), out.stride(0), ptr(resid), ptr(act_out), _s(x2d))
+    args = (L.dt(x2d), L.dt(out), epi, M, N, K, ptr(x2d), x2d.stride(0), ptr(w), ptr(bias), ptr(out), out.stride(0),
+            ptr(resid), ptr(act_out))
+    if wimg is not None:
+        assert wimg.numel() == N * K and wimg.dtype == torch.float32 and wimg.device == w.device
+        call("vit_linear_fwd_wimg", *args, ptr(wimg), _s(x2d))
+    else:
+        call("vit_linear_fwd", *args, _s(x2d))
     return (out, act_out) if epi in (L.EPI_BIAS_GELU, L.EPI_BIAS_QGELU) else out
 
 
@@ -162,14 +169,16 @@ def spread_partials(part2d, pr):
 
 
 def linear_dgrad(dy2d, w, out_dtype=torch.float32, epi=L.EPI_STORE, pre=None, out=None, dbias=None, reduce_on=None,
-                 part_rows=None):
+                 part_rows=None, wimg=None):
     """dx = dy @ w  (dy [M,N], w [N,K]); with EPI_GELU_BWD / EPI_QGELU_BWD times ``pre`` [M,K] =
     the act'(pre) the forward's BIAS_GELU epilogue saved;
     dbias [K] (optional) receives the column sums of dx (fused into the GEMM epilogue).
     ``reduce_on`` (an object with ``.run(fn)``, e.g. the model's side stream): the final
     reduction of those column sums is issued through it instead of inline.
     ``part_rows`` (a PartRows, with a ColBatch): the partial rows are laid out as a dense launch's before
-    they are reduced (:func:`spread_partials`)."""
+    they are reduced (:func:`spread_partials`).
+    ``wimg``: the pre-split image of ``w^T`` (:func:`weight_image` with ``transposed=True``), read in place of
+    ``w`` by the fp32 "high" MFMA kernels -- the same bits."""
     M, N = dy2d.shape
     K = w.shape[1]
     assert w.shape[0] == N and w.dtype == dy2d.dtype and dy2d.stride(1) == 1
@@ -187,8 +196,13 @@ def linear_dgrad(dy2d, w, out_dtype=torch.float32, epi=L.EPI_STORE, pre=None, ou
                 else workspace("dgrad_bias", nfl * 4, dy2d.device))
     if dy2d.dtype == torch.float32:
         _streamk(dy2d.device)
-    call("vit_linear_dgrad", L.dt(dy2d), L.dt(out), epi, M, N, K, ptr(dy2d), dy2d.stride(0), ptr(w), ptr(out),
-         out.stride(0), ptr(pre), ptr(dbias), ptr(part), nfl, int(defer), _s(dy2d))
+    args = (L.dt(dy2d), L.dt(out), epi, M, N, K, ptr(dy2d), dy2d.stride(0), ptr(w), ptr(out), out.stride(0), ptr(pre),
+            ptr(dbias), ptr(part), nfl, int(defer))
+    if wimg is not None:
+        assert wimg.numel() == N * K and wimg.dtype == torch.float32 and wimg.device == w.device
+        call("vit_linear_dgrad_wimg", *args, ptr(wimg), _s(dy2d))
+    else:
+        call("vit_linear_dgrad", *args, _s(dy2d))
     if defer:
         rows = (M + DGRAD_SUM_ROWS - 1) // DGRAD_SUM_ROWS
         if isinstance(reduce_on, ColBatch):
@@ -852,7 +866,7 @@ def mse_bwd(pred, target, grad_loss=None):
 _F32_MATMUL = ("highest", "high")  # vit_gemm_f32_precision 0 / 1
 
 
-def set_float32_matmul_precision(precision):
+def set_float32_matmul_precision(precision, presplit_weights=False):
     """The arithmetic of the fp32 MFMA GEMMs (``compute_dtype=torch.float32``), after
     ``torch.set_float32_matmul_precision``:
 
@@ -868,18 +882,106 @@ def set_float32_matmul_precision(precision):
     when it runs, not the one its forward ran in; cached frozen-prefix tensors carry the mode in their keys and
     are rebuilt after a switch.  The environment variable ``VIT_F32_MATMUL=high`` sets the initial value when
     the library loads (spawned workers inherit it).  bf16 models, attention, LayerNorm and everything else
-    are untouched.  Host-only: works without a GPU."""
+    are untouched.  Host-only: works without a GPU.
+
+    ``presplit_weights=True`` (with ``"high"`` only; with ``"highest"`` it raises ``ValueError`` and changes
+    nothing) keeps, for every registered fp32 GEMM weight parameter, a pre-split ``hi`` / ``lo``
+    image in the layout the kernels' fragment reads expect (:func:`weight_image`), built on first use and rebuilt
+    when the parameter's version, address, shape or device changes.  The forward and input-gradient GEMMs then
+    read the image and split only their activation operand: the same MFMAs on the same bits, so results, and
+    every cache key, are those of ``"high"``.  It costs 4 bytes per covered weight element, twice that for
+    weights whose input gradient runs (about 1.2 GB for the ViT-L/14 visual tower): :func:`weight_image_bytes`.
+    Computed weights (DoRA / LoRA ``out_proj.weight``), weight gradients and the patch embedding keep the
+    in-loop split.  Both switches are set on every call, so a call without the keyword switches pre-splitting
+    off (the images are freed at the model's next forward); :func:`get_float32_matmul_presplit` reads it and
+    ``VIT_F32_MATMUL_PRESPLIT=1`` beside ``VIT_F32_MATMUL=high`` sets the initial value."""
     if precision == "medium":
         raise ValueError('float32 matmul precision "medium" (operands rounded to one bfloat16) is not a mode of '
                          'the fp32 path: build the model with compute_dtype=torch.bfloat16')
     if precision not in _F32_MATMUL:
         raise ValueError(f'float32 matmul precision must be "highest" or "high", got {precision!r}')
+    if presplit_weights and precision != "high":
+        raise ValueError('presplit_weights=True keeps hi / lo images of the weights for the three bf16 products: it '
+                         'needs precision "high"')
     L.lib().vit_gemm_f32_precision(_F32_MATMUL.index(precision))
+    _F32_PRESPLIT[0] = bool(presplit_weights)
 
 
 def get_float32_matmul_precision() -> str:
     """``"highest"`` or ``"high"``: see :func:`set_float32_matmul_precision`."""
     return _F32_MATMUL[L.lib().vit_gemm_f32_precision(-1)]
+
+
+_F32_PRESPLIT = [os.environ.get("VIT_F32_MATMUL_PRESPLIT", "") == "1"]
+
+
+def get_float32_matmul_presplit() -> bool:
+    """Whether the fp32 "high" GEMMs read pre-split weight images: both switches of
+    :func:`set_float32_matmul_precision` are on.  (``VIT_F32_MATMUL_PRESPLIT=1`` without ``VIT_F32_MATMUL=high``
+    leaves this ``False``.)"""
+    return bool(_F32_PRESPLIT[0] and L.lib().vit_gemm_f32_precision(-1) == 1)
+
+
+def weight_image_raw(w, transposed=False, out=None):
+    """The pre-split image of an f32 matrix ``w`` [N, K] (row stride ``w.stride(0)``) for the fp32 "high" GEMMs
+    (vit_gemm_f32_weight_image): a contiguous f32-typed tensor of ``w``'s size holding, per 128-byte block of 32
+    reduction values, four 16-byte ``hi`` chunks then four ``lo`` chunks of bf16.  ``transposed``: the image of
+    ``w^T`` ([K, N] cells), the input gradient's operand."""
+    L.require_gpu(w)
+    N, K = w.shape
+    assert w.dtype == torch.float32 and w.stride(1) == 1
+    if out is None:
+        out = torch.empty((K, N) if transposed else (N, K), dtype=torch.float32, device=w.device)
+    call("vit_gemm_f32_weight_image", N, K, ptr(w), w.stride(0), int(transposed), ptr(out), _s(w))
+    return out
+
+
+def register_weight_image(p):
+    """Mark a parameter as an fp32 GEMM weight that may hold pre-split images (the models' ``_ensure_shadows``)."""
+    p._vit_wimg_ok = True
+
+
+def drop_weight_images(params):
+    for p in params:
+        for name in ("_vit_wimg", "_vit_wimg_t"):
+            if getattr(p, name, None) is not None:
+                setattr(p, name, None)
+                setattr(p, name + "_version", None)
+
+
+def weight_image(p, dtype=torch.float32, transposed=False):
+    """The current pre-split image of a registered fp32 weight parameter (``p._vit_wimg`` / ``p._vit_wimg_t`` with
+    the version it was built from in ``..._version``), or None when pre-splitting is off, ``p`` is not a registered
+    parameter (computed weights: the in-loop split), or its shape does not qualify.  Built on first use, rebuilt
+    when ``p._version``, its address, shape or device changed.  Under graph capture a stale image is not rebuilt:
+    the GEMM takes the in-loop split, the same bits."""
+    if not _F32_PRESPLIT[0] or dtype != torch.float32 or not getattr(p, "_vit_wimg_ok", False):
+        return None
+    if not get_float32_matmul_presplit() or not p.is_cuda or p.dtype != torch.float32 or p.dim() != 2:
+        return None
+    name = "_vit_wimg_t" if transposed else "_vit_wimg"
+    N, K = p.shape
+    if (N if transposed else K) % 32 or not p.is_contiguous() or p.data_ptr() % 16:
+        return None
+    ver = (p._version, p.data_ptr(), tuple(p.shape), p.device)
+    img = getattr(p, name, None)
+    if img is not None and getattr(p, name + "_version", None) == ver:
+        return img
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    # a fresh tensor, not the old image rewritten: the old one goes back to the allocator, which hands it out
+    # again only behind the GEMMs already queued on this stream
+    img = weight_image_raw(p.detach(), transposed)
+    setattr(p, name, img)
+    setattr(p, name + "_version", ver)
+    return img
+
+
+def weight_image_bytes(module_or_params) -> int:
+    """Bytes held by the pre-split weight images of a module's (or an iterable of) parameters."""
+    ps = module_or_params.parameters() if hasattr(module_or_params, "parameters") else module_or_params
+    return sum(img.numel() * 4 for p in ps for img in (getattr(p, "_vit_wimg", None), getattr(p, "_vit_wimg_t", None))
+               if img is not None)
 
 
 _F32_ATTENTION = ("highest", "high")  # vit_sdpa_f32_precision 0 / 1

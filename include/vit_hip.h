@@ -130,6 +130,38 @@ int vit_gemm_f32_weight_image(int N, int K, const float* W, int64_t ldw, int tra
  * vit_gemm_f32_count and vit_gemm_f32_split_count). */
 int vit_gemm_f32_presplit_count(int reset);
 
+/* Pre-split activation images for mode 1 (additive to ABI 10).  With a weight image the activation is
+ * the one operand still split in every k-step.  In a forward-only chain an activation is read by one GEMM and
+ * nothing else, so the kernel that produces it can write its image instead: the same bytes, the same row pitch.
+ * VIT_DTYPE_F32_SPLIT names such a buffer: f32-sized, holding the image (rule above) of the f32 matrix with that
+ * row pitch, row by row -- what vit_gemm_f32_weight_image(rows, K, X, ldx, 0, ..) writes for a contiguous one.
+ *   - dtype_y of vit_layer_norm_fwd (f32 x) and vit_add_layer_norm_fwd: y is written as the image of the f32 y;
+ *     mean, rstd and xs are unchanged.  Vector kernels only: D % 256 == 0 with the alignment they ask for (ldy % 4,
+ *     y 16-byte aligned); anything else is hipErrorInvalidValue with nothing launched.
+ *   - out_dtype of vit_linear_fwd_wimg with VIT_EPI_STORE, VIT_EPI_BIAS_GELU_FWD or VIT_EPI_BIAS_QGELU_FWD: Y is
+ *     written as the image of the f32 Y of the same call.  Needs N % 32 == 0.
+ *   - dtype of vit_linear_fwd_wimg (X is an image; K % 32 == 0) with those three epilogues or VIT_EPI_RESID: the
+ *     result is the f32-X call's bit for bit.  W must still be given the way that call gets it (it is not read).
+ * In both linear forms act_out must be NULL (none of those epilogues writes one).  The LayerNorm entries take the code when
+ * vit_layer_norm_fwd_image_ok says so (host-only: add = 0 / 1 for vit_layer_norm_fwd / vit_add_layer_norm_fwd, D, the
+ * OR of every row stride and the OR of every address of the call): D % 256 == 0 up to 2048 -- but not 1280 or 1792
+ * for vit_layer_norm_fwd, whose f32 form runs the element-wise kernel there -- strides % 4 == 0, 16-byte alignment.
+ * A linear call that names the code in either place runs only on the pre-split MFMA kernels: when Wimg is NULL, the
+ * mode is not 1, or the same call with f32 X and Y would not take the f32 MFMA path (vit_linear_fwd_f32_mfma below,
+ * and 16-byte aligned Y, bias, resid with ldy % 4 == 0), it returns hipErrorInvalidValue with nothing launched.
+ * Image bytes are never read as floats there (vit_linear_fwd, which has no Wimg, refuses the code too).  The three
+ * entry points above are the only ones that know the code: pass it to no other.
+ * vit_linear_fwd_f32_mfma (host-only, no GPU call): 1 when an f32 forward of these M, N, K with X (row pitch ldx)
+ * and W at these addresses takes the f32 MFMA path in either mode -- at least 64 output tiles of 128 x 128,
+ * K % 32 == 0, N % 4 == 0, ldx % 4 == 0, X and W 16-byte aligned -- else 0.  Only the addresses' alignment is
+ * looked at.  Ask before asking a producer for an image.
+ * vit_gemm_f32_presplit_act_count: launches that read an activation image since the last reset (they count in
+ * the three counters above as well). */
+enum { VIT_DTYPE_F32_SPLIT = 2 };
+int vit_linear_fwd_f32_mfma(int M, int N, int K, const void* X, int64_t ldx, const void* W);
+int vit_gemm_f32_presplit_act_count(int reset);
+int vit_layer_norm_fwd_image_ok(int add, int D, int64_t strides_or, uint64_t ptrs_or);
+
 /* Host-only query (no GPU call): rows per launch the bf16 MFMA path uses for a row-contiguous
  * operand of M rows x ld elements (its staging offsets are 32-bit: larger operands are split
  * into row chunks, a multiple of 256 rows each); M when one launch fits, 0 if none does. */

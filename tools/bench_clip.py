@@ -91,13 +91,16 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds, which="cls",
         switch = lambda on: vit_amd.set_float32_matmul_precision("high" if on else "highest")
     elif which == "f32pre":  # "high" throughout; pre-split weight images off and on
         switch = lambda on: vit_amd.set_float32_matmul_precision("high", presplit_weights=on)
+    elif which == "f32act":  # "high" with weight images throughout; activation images off and on
+        switch = lambda on: vit_amd.set_float32_matmul_precision("high", presplit_weights=True, presplit_activations=on)
     elif which == "f32attn":  # the fp32 attention mode off and on, the GEMM mode as --f32-matmul says
         switch = lambda on: vit_amd.set_float32_attention_precision("high" if on else "highest")
     else:
         switch = m.clip_model.set_cls_tail if which == "cls" else m.clip_model.set_eot_tail
-    if which in ("eot", "f32", "f32attn", "f32pre"):
+    if which in ("eot", "f32", "f32attn", "f32pre", "f32act"):
         m.clip_model.set_cls_tail(cls_fixed)
-    key = {"f32": "f32_high", "f32attn": "f32_attention_high", "f32pre": "f32_presplit"}.get(which, which + "_tail")
+    key = {"f32": "f32_high", "f32attn": "f32_attention_high", "f32pre": "f32_presplit",
+           "f32act": "f32_presplit_act"}.get(which, which + "_tail")
 
     def window(n):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -136,7 +139,7 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds, which="cls",
     return {"ms_per_step": {key + "_off": off, key + "_on": on}, key + "_speedup": round(off["median"] / on["median"], 4),
             "images_per_sec": {key + "_off": round(batch / off["median"] * 1e3, 2),
                                key + "_on": round(batch / on["median"] * 1e3, 2)},
-            "cls_tail_throughout": bool(which in ("eot", "f32", "f32attn", "f32pre") and cls_fixed),
+            "cls_tail_throughout": bool(which in ("eot", "f32", "f32attn", "f32pre", "f32act") and cls_fixed),
             "weight_image_bytes": held,
             "predictions_bit_equal": bool(torch.equal(preds[True], preds[False])),
             "prediction_rel_diff_on_vs_off": float((preds[True] - preds[False]).abs().max() / preds[False].abs().max()),
@@ -170,6 +173,12 @@ def main():
     ap.add_argument("--f32-presplit-ab", action="store_true",
                     help="alternate in-loop 'high' and pre-split 'high' in one process (with --cls-tail: that tail on "
                          "throughout)")
+    ap.add_argument("--f32-presplit-act", action="store_true",
+                    help="with --f32-matmul high --f32-presplit: forward-only blocks hand pre-split activation images "
+                         "from producer to GEMM (presplit_activations=True)")
+    ap.add_argument("--f32-presplit-act-ab", action="store_true",
+                    help="alternate pre-split weights and pre-split weights + activations in one process (with "
+                         "--cls-tail: that tail on throughout)")
     ap.add_argument("--f32-attention", choices=["highest", "high"], default=None,
                     help="fp32 attention arithmetic of the whole run (vit_amd.set_float32_attention_precision; high = "
                          "bf16x3 in the resident f32 kernels)")
@@ -180,17 +189,20 @@ def main():
     import torch
     if a.f32_matmul:
         import vit_amd
-        vit_amd.set_float32_matmul_precision(a.f32_matmul, presplit_weights=a.f32_presplit)
-    elif a.f32_presplit:
-        ap.error("--f32-presplit needs --f32-matmul high")
+        if a.f32_presplit_act and not a.f32_presplit:
+            ap.error("--f32-presplit-act needs --f32-presplit")
+        vit_amd.set_float32_matmul_precision(a.f32_matmul, presplit_weights=a.f32_presplit,
+                                             presplit_activations=a.f32_presplit_act)
+    elif a.f32_presplit or a.f32_presplit_act:
+        ap.error("--f32-presplit / --f32-presplit-act need --f32-matmul high")
     if a.f32_attention:
         import vit_amd
         vit_amd.set_float32_attention_precision(a.f32_attention)
-    if a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab:
+    if a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab:
         if a.rounds < 3:
             ap.error("--rounds must be at least 3: the spread is part of the record")
         r = cls_tail_leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup, a.adapter, a.rounds,
-                         "f32pre" if a.f32_presplit_ab else "f32attn" if a.f32_attention_ab else "f32" if a.f32_ab else "eot" if a.eot_tail else "cls",
+                         "f32act" if a.f32_presplit_act_ab else "f32pre" if a.f32_presplit_ab else "f32attn" if a.f32_attention_ab else "f32" if a.f32_ab else "eot" if a.eot_tail else "cls",
                          a.cls_tail)
     else:
         leg = bench.c3_leg if a.adapter == "dora" else lora_leg
@@ -199,7 +211,10 @@ def main():
     r["adapter"] = a.adapter
     if a.f32_matmul:
         r["f32_matmul"] = a.f32_matmul
-        r["f32_presplit"] = bool(a.f32_presplit)
+        # what ran: a flag given for the whole run, or "ab" for the switch that alternated (weight images are on
+        # throughout when the activation images alternate)
+        r["f32_presplit"] = "ab" if a.f32_presplit_ab else bool(a.f32_presplit or a.f32_presplit_act_ab)
+        r["f32_presplit_act"] = "ab" if a.f32_presplit_act_ab else bool(a.f32_presplit_act)
     if a.f32_attention:
         r["f32_attention"] = a.f32_attention
     print(json.dumps(r))

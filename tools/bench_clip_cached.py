@@ -44,6 +44,11 @@ on throughout): ``f32_high_speedup``, records ``bench_clip_cached_f32high[_clsta
 in-loop ``high`` (the plain series) and pre-split ``high`` (the ``*_tail`` series) on the same prefix caches, which
 both read as hits: ``f32_presplit_speedup``, ``weight_image_bytes``, records
 ``bench_clip_cached_f32high_presplit[_clstail]_{dtype}.json``.
+``--f32-presplit-act`` (with ``--f32-matmul high --f32-presplit``) adds pre-split activation images in the forward-only
+blocks; ``--f32-presplit-act-ab`` (with ``--f32-matmul high``) alternates pre-split weights and
+pre-split weights + activations, one set of caches again, and times the prefix-cache build itself in either mode,
+alternating: ``f32_presplit_act_speedup``, ``cache_build_seconds_ab``, records
+``bench_clip_cached_f32high_presplitact[_clstail]_{dtype}.json``.
 
 ``--adapter lora`` puts the reference's LoRA pair (NEWP:339-404) where DoRA stands; its records are named
 ``bench_clip_cached_lora_{dtype}.json``.
@@ -117,7 +122,7 @@ def model_leg(a, dtype_name):
         pred_diff = float((pc - pu).abs().max() / pu.abs().max())
 
     fixed = caches["train"].take(torch.arange(a.batch))
-    ab = a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab  # an fp32 mode alternates
+    ab = a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab  # an fp32 mode alternates
     tails = (False, True) if (a.cls_tail or a.eot_tail or ab) else (False,)
     # the switch that alternates: the EOT tail if asked for (the class-token tail then stays as --cls-tail says)
     set_tail = m.clip_model.set_eot_tail if a.eot_tail else m.clip_model.set_cls_tail
@@ -127,14 +132,19 @@ def model_leg(a, dtype_name):
     if ab:  # the fp32 GEMM (or attention) mode alternates; each mode reads the prefix caches built in it
         set_mode = (vit_amd.set_float32_attention_precision if a.f32_attention_ab
                     else vit_amd.set_float32_matmul_precision)
-        if a.f32_presplit_ab:  # in-loop "high" against pre-split "high": the same bits, so the same caches
+        if a.f32_presplit_act_ab:  # weight images throughout, activation images off and on: the same bits again
+            set_mode = lambda mode: vit_amd.set_float32_matmul_precision("high", presplit_weights=True,
+                                                                         presplit_activations=mode == "high")
+            by_mode = {False: caches, True: caches}
+        elif a.f32_presplit_ab:  # in-loop "high" against pre-split "high": the same bits, so the same caches
             set_mode = lambda mode: vit_amd.set_float32_matmul_precision("high", presplit_weights=mode == "high")
             by_mode = {False: caches, True: caches}
         else:
             set_mode("high")
             by_mode = {False: caches, True: S.prefix_caches_for(m, data, None, a.batch)}
         set_mode("highest")
-        tail_key = "f32_presplit" if a.f32_presplit_ab else "f32_attention_high" if a.f32_attention_ab else "f32_high"
+        tail_key = ("f32_presplit_act" if a.f32_presplit_act_ab else "f32_presplit" if a.f32_presplit_ab
+                    else "f32_attention_high" if a.f32_attention_ab else "f32_high")
 
         def set_tail(on):
             nonlocal caches
@@ -241,20 +251,31 @@ def model_leg(a, dtype_name):
         rho = {}
         for t in tails:
             set_tail(t)
-            rho[("presplit" if t else "high") if a.f32_presplit_ab else ("high" if t else "highest")] = float(S.behavioral_rsa(m, data["inference"], data["reference_rdm"])[0])
+            rho[("act" if t else "presplit") if a.f32_presplit_act_ab else ("presplit" if t else "high") if a.f32_presplit_ab else ("high" if t else "highest")] = float(S.behavioral_rsa(m, data["inference"], data["reference_rdm"])[0])
         set_tail(False)
         rec[tail_key + "_rsa_rho"] = rho
     if len(tails) > 1:
         rec[tail_key + "_prediction_rel_diff"] = tail_diff
         rec[tail_key + "_prediction_bound"] = 1e-3 if dtype_name == "f32" else 3e-2
         rec["cls_tail_throughout"] = bool((a.eot_tail or ab) and a.cls_tail)
-    if a.f32_presplit_ab:
+    if a.f32_presplit_act_ab:  # the prefix-cache build itself, weights-only against weights + activations
+        builds = {"presplit": [], "act": []}
+        for _ in range(a.rounds):
+            for t in tails:
+                set_tail(t)
+                dt, fresh = _timed(lambda: S.prefix_caches_for(m, data, None, a.batch), sync)
+                builds["act" if t else "presplit"].append(dt)
+        set_tail(False)
+        rec["cache_build_seconds_ab"] = {k: _summary(v) for k, v in builds.items()}
+        rec["cache_build_rows_bit_equal"] = bool(torch.equal(fresh["train"].take(idx), caches["train"].take(idx)))
+    if a.f32_presplit_ab or a.f32_presplit_act_ab:
         set_tail(True)
         with torch.no_grad():
             m(visual_prefix=caches["train"].take(idx))
         rec["weight_image_bytes"] = vit_amd.weight_image_bytes(m)
         set_tail(False)
     rec["f32_presplit"] = "ab" if a.f32_presplit_ab else vit_amd.get_float32_matmul_presplit()
+    rec["f32_presplit_act"] = "ab" if a.f32_presplit_act_ab else vit_amd.get_float32_matmul_presplit_activations()
     rec["f32_matmul"], rec["f32_attention"] = (vit_amd.get_float32_matmul_precision(),
                                                "ab" if a.f32_attention_ab else vit_amd.get_float32_attention_precision())
     rec["train_step_images_per_sec"]["cached_without_gather"] = _summary(no_gather)
@@ -331,12 +352,16 @@ def driver(a):
             cmd.append("--f32-presplit")
         if a.f32_presplit_ab:
             cmd.append("--f32-presplit-ab")
+        if a.f32_presplit_act:
+            cmd.append("--f32-presplit-act")
+        if a.f32_presplit_act_ab:
+            cmd.append("--f32-presplit-act-ab")
         if a.f32_attention_ab:
             cmd.append("--f32-attention-ab")
         if a.f32_attention:
             cmd += ["--f32-attention", a.f32_attention]
         print("leg", leg, flush=True)
-        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if (a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab) else 1)).returncode  # TimeoutExpired ends the run
+        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if (a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab) else 1)).returncode  # TimeoutExpired ends the run
         if rc != 0:
             print(f"leg {leg} failed with exit code {rc}: stopping", flush=True)
             return rc
@@ -372,6 +397,10 @@ def main():
                     help="alternate the fp32 GEMM modes highest and high (with --cls-tail: that tail on throughout)")
     ap.add_argument("--f32-presplit", action="store_true",
                     help="with --f32-matmul high: pre-split images of the frozen fp32 weights for the whole run")
+    ap.add_argument("--f32-presplit-act", action="store_true",
+                    help="with --f32-matmul high --f32-presplit: pre-split activation images in forward-only blocks")
+    ap.add_argument("--f32-presplit-act-ab", action="store_true",
+                    help="with --f32-matmul high: alternate pre-split weights and pre-split weights + activations")
     ap.add_argument("--f32-presplit-ab", action="store_true",
                     help="with --f32-matmul high: alternate in-loop high and pre-split high (with --cls-tail: that tail "
                          "on throughout)")
@@ -391,11 +420,17 @@ def main():
         ap.error("--f32-presplit / --f32-presplit-ab need --f32-matmul high")
     if a.f32_presplit_ab and (a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit):
         ap.error("--f32-presplit-ab alternates pre-splitting alone")
+    if (a.f32_presplit_act and not a.f32_presplit) or (a.f32_presplit_act_ab and a.f32_matmul != "high"):
+        ap.error("--f32-presplit-act needs --f32-matmul high --f32-presplit; --f32-presplit-act-ab --f32-matmul high")
+    if a.f32_presplit_act_ab and (a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit
+                                  or a.f32_presplit_act):
+        ap.error("--f32-presplit-act-ab alternates the activation images alone")
     if a.leg is None:
         sys.exit(driver(a))
     if a.f32_matmul:
         import vit_amd
-        vit_amd.set_float32_matmul_precision(a.f32_matmul, presplit_weights=a.f32_presplit)
+        vit_amd.set_float32_matmul_precision(a.f32_matmul, presplit_weights=a.f32_presplit or a.f32_presplit_act_ab,
+                                             presplit_activations=a.f32_presplit_act)
     if a.f32_attention:
         import vit_amd
         vit_amd.set_float32_attention_precision(a.f32_attention)
@@ -403,7 +438,8 @@ def main():
     os.makedirs(a.out, exist_ok=True)
     tag = (("" if a.adapter == "dora" else f"_{a.adapter}") + ("_eottail" if a.eot_tail else "")
            + ("_f32high" if (a.f32_ab or a.f32_matmul == "high") else "")
-           + ("_presplit" if (a.f32_presplit or a.f32_presplit_ab) else "")
+           + ("_presplitact" if (a.f32_presplit_act or a.f32_presplit_act_ab) else
+              "_presplit" if (a.f32_presplit or a.f32_presplit_ab) else "")
            + ("_f32attnhigh" if (a.f32_attention_ab or a.f32_attention == "high") else "") + ("_clstail" if a.cls_tail else ""))
     name = "gather_blocks.json" if a.leg == "gather" else f"bench_clip_cached{tag}_{a.leg}.json"
     with open(os.path.join(a.out, name), "w") as fh:

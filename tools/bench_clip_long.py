@@ -5,6 +5,7 @@ tokens on the streamed f32 kernels against the generic ones (vit_sdpa_long_confi
 
     python tools/bench_clip_long.py [--batch 16] [--steps 5] [--warmup 2] [--rounds 3] [--steps-generic 2]
                                     [--f32-matmul highest|high] [--f32-ab] [--f32-presplit] [--f32-presplit-ab]
+                                    [--f32-presplit-act] [--f32-presplit-act-ab]
                                     [--f32-attention highest|high] [--f32-attention-ab] [--f32-attention-long]
 
 ``--f32-matmul`` sets the fp32 GEMM arithmetic of the run (``high`` = bf16x3); ``--f32-ab``
@@ -48,22 +49,29 @@ def main():
     ap.add_argument("--f32-ab", action="store_true")
     ap.add_argument("--f32-presplit", action="store_true", help="with --f32-matmul high: pre-split weight images")
     ap.add_argument("--f32-presplit-ab", action="store_true", help="alternate in-loop high and pre-split high")
+    ap.add_argument("--f32-presplit-act", action="store_true",
+                    help="with --f32-matmul high --f32-presplit: pre-split activation images (DESIGN 4.26)")
+    ap.add_argument("--f32-presplit-act-ab", action="store_true",
+                    help="alternate pre-split weights and pre-split weights + activations")
     ap.add_argument("--f32-attention", choices=["highest", "high"], default=None)
     ap.add_argument("--f32-attention-ab", action="store_true")
     ap.add_argument("--f32-attention-long", action="store_true",
                     help="with --f32-attention high or --f32-attention-ab: high also covers streamed attention")
     a = ap.parse_args()
-    if a.f32_ab + a.f32_attention_ab + a.f32_presplit_ab > 1:
+    if a.f32_ab + a.f32_attention_ab + a.f32_presplit_ab + a.f32_presplit_act_ab > 1:
         ap.error("one switch alternates at a time")
     if a.f32_presplit and a.f32_matmul != "high":
         ap.error("--f32-presplit needs --f32-matmul high")
+    if a.f32_presplit_act and not a.f32_presplit:
+        ap.error("--f32-presplit-act needs --f32-matmul high --f32-presplit")
     if a.f32_attention_long and not (a.f32_attention == "high" or a.f32_attention_ab):
         ap.error("--f32-attention-long needs --f32-attention high or --f32-attention-ab")
 
     def set_attention(mode):
         vit_amd.set_float32_attention_precision(mode, long_sequences=a.f32_attention_long and mode == "high")
     if a.f32_matmul:
-        vit_amd.set_float32_matmul_precision(a.f32_matmul, presplit_weights=a.f32_presplit)
+        vit_amd.set_float32_matmul_precision(a.f32_matmul, presplit_weights=a.f32_presplit,
+                                             presplit_activations=a.f32_presplit_act)
     if a.f32_attention:
         set_attention(a.f32_attention)
     set_mode = set_attention if a.f32_attention_ab else vit_amd.set_float32_matmul_precision
@@ -72,6 +80,11 @@ def main():
         sides = ("high", "presplit")
         set_mode = lambda name: vit_amd.set_float32_matmul_precision("highest" if name == "highest" else "high",
                                                                      presplit_weights=name == "presplit")
+    if a.f32_presplit_act_ab:
+        sides = ("presplit", "act")
+        set_mode = lambda name: vit_amd.set_float32_matmul_precision(
+            "highest" if name == "highest" else "high", presplit_weights=name != "highest",
+            presplit_activations=name == "act")
     dev = torch.device("cuda", 0)
     lib = L.lib()
     torch.manual_seed(0)
@@ -105,24 +118,25 @@ def main():
         assert torch.isfinite(loss)
         return a.batch * steps / dt, lib.vit_sdpa_long_f32_count(0) - c0
 
-    if a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab:
+    if a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab:
         ips = {k: [] for k in sides}
         extra = {}
         try:
-            if a.f32_presplit_ab:
+            if a.f32_presplit_ab or a.f32_presplit_act_ab:
+                count = lib.vit_gemm_f32_presplit_act_count if a.f32_presplit_act_ab else lib.vit_gemm_f32_presplit_count
                 lib.vit_sdpa_long_config(1)
                 with torch.no_grad():  # (a process's first forward registers the stream-K workspace after its patch
                     m(x)               # embedding has run: its bits are not a later forward's in either form)
                 preds = {}
                 for name in ips:
                     set_mode(name)
-                    c0 = lib.vit_gemm_f32_presplit_count(0)
+                    c0 = count(0)
                     with torch.no_grad():
                         preds[name] = m(x)
-                    assert (lib.vit_gemm_f32_presplit_count(0) > c0) == (name == "presplit"), name
+                    assert (count(0) > c0) == (name == sides[1]), name
                     if name == "presplit":
                         extra["weight_image_bytes"] = vit_amd.weight_image_bytes(m)
-                extra["predictions_bit_equal"] = bool(torch.equal(preds["high"], preds["presplit"]))
+                extra["predictions_bit_equal"] = bool(torch.equal(preds[sides[0]], preds[sides[1]]))
             if a.f32_attention_ab and a.f32_attention_long:
                 lib.vit_sdpa_long_config(1)
                 preds = {}
@@ -145,9 +159,10 @@ def main():
         med = {k: statistics.median(v) for k, v in ips.items()}
         print(json.dumps({"metric": "images/sec CLIP-HBA ViT-L/14@336px + DoRA fp32 train step", "batch": a.batch,
                           "steps": a.steps, "rounds": a.rounds, "images_per_sec": ips, "median": med,
-                          "alternated": ("f32_presplit" if a.f32_presplit_ab else
+                          "alternated": ("f32_presplit_act" if a.f32_presplit_act_ab else
+                                         "f32_presplit" if a.f32_presplit_ab else
                                          "f32_attention" if a.f32_attention_ab else "f32_matmul"),
-                          "f32_matmul": "ab" if a.f32_ab else "high" if a.f32_presplit_ab else (a.f32_matmul or "highest"),
+                          "f32_matmul": "ab" if a.f32_ab else "high" if (a.f32_presplit_ab or a.f32_presplit_act_ab) else (a.f32_matmul or "highest"),
                           "spread": {k: round((max(v) - min(v)) / med[k], 4) for k, v in ips.items()},
                           f"{sides[1]}_over_{sides[0]}": round(med[sides[1]] / med[sides[0]], 3), **extra}), flush=True)
         return

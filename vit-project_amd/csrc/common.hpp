@@ -13,7 +13,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
-enum { VIT_F32 = 0, VIT_BF16 = 1 };
+enum { VIT_F32 = 0, VIT_BF16 = 1,
+       VIT_F32_SPLIT = 2 };  // an f32-sized buffer holding the pre-split image of the f32 matrix
 
 static constexpr int WAVE = 64;
 

@@ -1333,22 +1333,27 @@ static int f32_precision_env() {
   return s && strcmp(s, "high") == 0 ? 1 : 0;
 }
 static int g_f32_split = f32_precision_env();
-static int g_f32_count = 0, g_f32_split_count = 0, g_f32_presplit_count = 0;
+static int g_f32_count = 0, g_f32_split_count = 0, g_f32_presplit_count = 0, g_f32_presplit_act_count = 0;
 
-// SPLIT = 2: Q is the pre-split image of a weight (f32w, RC x RC only)
+// SPLIT = 2: Q is the pre-split image of a weight (f32w, RC x RC only).  SPLIT = 3: P is the image of
+// the activation as well, and / or TO = f32a::img_t: C is written as an image (f32a)
+template <int SPLIT, typename TO> constexpr bool f32a_kernel() { return SPLIT == 3 || std::is_same<TO, f32a::img_t>::value; }
 template <int PL, int QL, int EPI, typename TO, int SPLIT> static auto f32_plain_kernel() {
-  if constexpr (SPLIT == 2) return &f32w::gemm_kernel<PL, QL, EPI, TO, float, 2>;
+  if constexpr (f32a_kernel<SPLIT, TO>()) return &f32a::gemm_kernel<PL, QL, EPI, TO, float, SPLIT>;
+  else if constexpr (SPLIT == 2) return &f32w::gemm_kernel<PL, QL, EPI, TO, float, 2>;
   else return &f32m::gemm_kernel<PL, QL, EPI, TO, float, SPLIT>;
 }
 template <int PL, int QL, int EPI, typename TO, int SPLIT> static auto f32_sk_kernel() {
-  if constexpr (SPLIT == 2) return &f32w::gemm_sk_kernel<PL, QL, EPI, TO, float, 2>;
+  if constexpr (f32a_kernel<SPLIT, TO>()) return &f32a::gemm_sk_kernel<PL, QL, EPI, TO, float, SPLIT>;
+  else if constexpr (SPLIT == 2) return &f32w::gemm_sk_kernel<PL, QL, EPI, TO, float, 2>;
   else return &f32m::gemm_sk_kernel<PL, QL, EPI, TO, float, SPLIT>;
 }
 
 template <int PL, int QL, int EPI, typename TO, int SPLIT>
 static int launch_f32_mode(const void* P, int64_t ldp, const void* Q, int64_t ldq, int M, int N, int R, int split,
                            const Epi& e, hipStream_t s) {
-  static_assert(SPLIT != 2 || (PL == LAY_RC && QL == LAY_RC), "a weight image is read row-contiguous");
+  static_assert(SPLIT < 2 || (PL == LAY_RC && QL == LAY_RC), "an operand image is read row-contiguous");
+  static_assert(!std::is_same<TO, f32a::img_t>::value || SPLIT >= 2, "an image output: the pre-split kernels");
   const auto plain = f32_plain_kernel<PL, QL, EPI, TO, SPLIT>();
   const auto sk = f32_sk_kernel<PL, QL, EPI, TO, SPLIT>();
   static bool attr = false;
@@ -1359,7 +1364,8 @@ static int launch_f32_mode(const void* P, int64_t ldp, const void* Q, int64_t ld
   }
   ++g_f32_count;
   g_f32_split_count += SPLIT != 0;
-  g_f32_presplit_count += SPLIT == 2;
+  g_f32_presplit_count += SPLIT >= 2;
+  g_f32_presplit_act_count += SPLIT == 3;
   const int64_t tiles = (int64_t)((M + f32m::BM - 1) / f32m::BM) * ((N + f32m::BN - 1) / f32m::BN);
   const int G = 2 * num_cus();  // two workgroups per CU
   if (split <= 1 && R % f32m::BK == 0 && tiles >= G && ragged_waste(tiles, G) > 0.03) {
@@ -1528,6 +1534,40 @@ static int gemm_any(int epi, int dtype, int out_dtype, int pl, int ql, int M, in
 
 static Epi make_epi() { Epi e; memset(&e, 0, sizeof(e)); e.dbg = g_dbg; return e; }
 
+// would an f32 forward of this geometry take the f32 MFMA path (gemm_dispatch's rule for P and Q)
+static bool f32_fwd_mfma_ok(int M, int N, int K, const void* X, int64_t ldx, const void* W) {
+  return M > 0 && N > 0 && fast_f32_ok(VIT_F32, LAY_RC, LAY_RC, M, N, K, X, W, ldx, K) && f32_grid_ok(M, N, 1);
+}
+// the forward with an activation image as X and / or as Y (vit_linear_fwd_wimg)
+template <int EPI>
+static int linear_fwd_image(bool ximg, bool oimg, int M, int N, int K, const void* X, int64_t ldx, const void* Wimg,
+                            const Epi& e, hipStream_t s) {
+  if constexpr (EPI != EPI_RESID) {
+    if (oimg) {
+      if (ximg) return launch_f32_mode<LAY_RC, LAY_RC, EPI, f32a::img_t, 3>(X, ldx, Wimg, K, M, N, K, 1, e, s);
+      return launch_f32_mode<LAY_RC, LAY_RC, EPI, f32a::img_t, 2>(X, ldx, Wimg, K, M, N, K, 1, e, s);
+    }
+  }
+  return launch_f32_mode<LAY_RC, LAY_RC, EPI, float, 3>(X, ldx, Wimg, K, M, N, K, 1, e, s);
+}
+static int linear_fwd_image_any(int dtype, int out_dtype, int epi, int M, int N, int K, const void* X, int64_t ldx,
+                                const void* W, const void* Wimg, const Epi& e, hipStream_t s) {
+  const bool ximg = dtype == VIT_F32_SPLIT, oimg = out_dtype == VIT_F32_SPLIT;
+  if ((!ximg && dtype != VIT_F32) || (!oimg && out_dtype != VIT_F32)) return (int)hipErrorInvalidValue;
+  if (epi != EPI_STORE && epi != EPI_BIAS_GELU_FWD && epi != EPI_BIAS_QGELU_FWD && !(epi == EPI_RESID && !oimg))
+    return (int)hipErrorInvalidValue;
+  if (oimg && N % 32) return (int)hipErrorInvalidValue;
+  if (Wimg == nullptr || !aligned16(Wimg) || !g_f32_split) return (int)hipErrorInvalidValue;
+  if (!f32_fwd_mfma_ok(M, N, K, X, ldx, W) || !epi_fast_ok(epi, VIT_F32, VIT_F32, e))
+    return (int)hipErrorInvalidValue;
+  switch (epi) {
+    case EPI_STORE: return linear_fwd_image<EPI_STORE>(ximg, oimg, M, N, K, X, ldx, Wimg, e, s);
+    case EPI_RESID: return linear_fwd_image<EPI_RESID>(ximg, oimg, M, N, K, X, ldx, Wimg, e, s);
+    case EPI_BIAS_GELU_FWD: return linear_fwd_image<EPI_BIAS_GELU_FWD>(ximg, oimg, M, N, K, X, ldx, Wimg, e, s);
+    default: return linear_fwd_image<EPI_BIAS_QGELU_FWD>(ximg, oimg, M, N, K, X, ldx, Wimg, e, s);
+  }
+}
+
 extern "C" {
 
 // Host-side plan of the bf16 MFMA path's 32-bit staging offsets (no GPU needed; tests):
@@ -1649,9 +1689,28 @@ int vit_gemm_splitk(int p_layout, int q_layout, int M, int N, int R, const float
 // vit_linear_fwd_wimg: the same with Wimg = vit_gemm_f32_weight_image(N, K, W, K, 0) of the current W.  When the
 // call takes the f32 MFMA path in "high" (vit_gemm_f32_precision(1)) and Wimg is not NULL, the image alone is read
 // (W is never dereferenced) and the result is vit_linear_fwd's bit for bit; in every other case it is vit_linear_fwd.
+//
+// Activation images: dtype == VIT_F32_SPLIT reads X as the pre-split image of the f32 X (f32a, SPLIT =
+// 3), out_dtype == VIT_F32_SPLIT writes Y as the image of the f32 Y (f32a::epilogue_image; STORE and the act-only
+// codes, N % 32 == 0).  Such a call has no other kernel to run on: without a weight image, outside mode 1 or off
+// the f32 MFMA path it is hipErrorInvalidValue with nothing launched.
+int vit_linear_fwd_f32_mfma(int M, int N, int K, const void* X, int64_t ldx, const void* W) {
+  return f32_fwd_mfma_ok(M, N, K, X, ldx, W) ? 1 : 0;
+}
+int vit_gemm_f32_presplit_act_count(int reset) {
+  const int c = g_f32_presplit_act_count;
+  if (reset) g_f32_presplit_act_count = 0;
+  return c;
+}
 int vit_linear_fwd_wimg(int dtype, int out_dtype, int epi, int M, int N, int K, const void* X, int64_t ldx,
                         const void* W, const float* bias, void* Y, int64_t ldy, const void* resid,
                         void* act_out, const void* Wimg, void* stream) {
+  if (dtype == VIT_F32_SPLIT || out_dtype == VIT_F32_SPLIT) {
+    if (act_out != nullptr) return (int)hipErrorInvalidValue;  // none of the accepted epilogues writes one
+    Epi e = make_epi();
+    e.C = Y; e.ldc = ldy; e.bias = bias; e.aux = resid; e.ld_aux = ldy;
+    return linear_fwd_image_any(dtype, out_dtype, epi, M, N, K, X, ldx, W, Wimg, e, (hipStream_t)stream);
+  }
   Epi e = make_epi();
   e.C = Y; e.ldc = ldy; e.bias = bias; e.aux = resid; e.ld_aux = ldy; e.aux_out = act_out;
   return gemm_any(epi, dtype, out_dtype, LAY_RC, LAY_RC, M, N, K, X, ldx, W, K, 1, e, (hipStream_t)stream, true,

@@ -44,6 +44,11 @@
 // the reads frag<LAY_RC>(.., h = 0) / (.., h = 1) (chunks g and 4 + g) ARE Q's hi / lo packs: no VALU work
 // for Q, P split as in SPLIT = 1, the same three MFMAs on the same operand bits in the same order, so the
 // result is SPLIT = 1's bit for bit.
+//
+// SPLIT = 3 (namespace f32a below, DESIGN 4.26): SPLIT = 2 with P read from the same kind of image, written by the
+// kernel that produced the activation (a LayerNorm forward, or the image epilogue below of the GEMM in front).  The
+// image rule is Q's: P is row-contiguous too, staged by the same stage<LAY_RC> and read by the same frag<LAY_RC>.
+// No split8 is left in the k-step: 16 ds_read_b128 and 48 MFMAs on the operand bits of SPLIT = 1, in its order.
 namespace f32m {
 
 constexpr int BM = 128, BN = 128, BK = 32, THREADS = 256, WAVES = 4, S = 2;
@@ -127,9 +132,10 @@ __device__ __forceinline__ void mainloop(const float* __restrict__ P, int64_t ld
     big::lds_barrier();
     const bool more = kt + 1 < ke;
     const uint32_t cur = big::lds_addr(smem + (kt % S) * STAGE);
-    if constexpr (SPLIT == 2) {
-      static_assert(QL == LAY_RC, "the pre-split image is row-contiguous");
+    if constexpr (SPLIT == 2 || SPLIT == 3) {
+      static_assert(QL == LAY_RC && (SPLIT == 2 || PL == LAY_RC), "the pre-split image is row-contiguous");
       // Q is a pre-split image: its h = 0 / h = 1 reads are the hi / lo packs.  Issue and read order as below.
+      // SPLIT = 3: P is one too (an activation image), so the k-step has no split8 at all.
       f32x4 pf[2][AI], qf[2][AJ];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -143,7 +149,12 @@ __device__ __forceinline__ void mainloop(const float* __restrict__ P, int64_t ld
 #pragma unroll
       for (int a = 0; a < AI; ++a) {
         bf16x8 ph, pl;
-        split8(pf[0][a], pf[1][a], ph, pl);
+        if constexpr (SPLIT == 3) {
+          ph = __builtin_bit_cast(bf16x8, pf[0][a]);
+          pl = __builtin_bit_cast(bf16x8, pf[1][a]);
+        } else {
+          split8(pf[0][a], pf[1][a], ph, pl);
+        }
 #pragma unroll
         for (int b = 0; b < AJ; ++b) {
           const bf16x8 qh = __builtin_bit_cast(bf16x8, qf[0][b]), ql = __builtin_bit_cast(bf16x8, qf[1][b]);
@@ -274,3 +285,64 @@ __global__ __launch_bounds__(256) void weight_image_t_kernel(const float* __rest
 }
 
 }  // namespace f32w
+
+// The kernels that read or write an activation image (DESIGN 4.26), a namespace of their own again: SPLIT = 3 reads
+// P and Q as images; TO = img_t writes C as the image of the f32 matrix the plain epilogue would have stored, for
+// the GEMM behind it to read as its P (SPLIT = 2 or 3 in front of it).
+namespace f32a {
+
+using namespace f32m;
+
+struct img_t { float cell; };  // output type tag: 4-byte cells at the f32 matrix's row pitch
+
+// The image-writing epilogue (EPI_STORE and the two act-only codes; N % 32 == 0).  A lane holds both inputs of the
+// split8 of lane group g = lane >> 4 in the 32-column k-block m of its wave: acc[a][2m] is columns 32m + 4g .. + 3
+// (the h = 0 half), acc[a][2m + 1] columns 32m + 16 + 4g .. + 3 (h = 1).  Bias, activation and rounding are
+// epi_vec's for an f32 output; then hi chunk g and lo chunk g of that row's k-block, 16 bytes each.
+template <int EPI>
+__device__ __forceinline__ void epilogue_image(const Epi& e, const f32x4 (&acc)[AI][AJ], int M, int N, int i0, int j0,
+                                               int wave, int lane) {
+  static_assert(EPI == EPI_STORE || epi_act_only(EPI), "image outputs: the plain store and the act-only forms");
+  static_assert(AJ % 2 == 0, "fragment pairs");
+  const int wi = wave >> 1, wj = wave & 1, g = lane >> 4;
+#pragma unroll
+  for (int a = 0; a < AI; ++a) {
+    const int i = i0 + wi * 64 + a * 16 + (lane & 15);
+#pragma unroll
+    for (int m = 0; m < AJ / 2; ++m) {
+      const int jb = j0 + wj * 64 + 32 * m;  // first column of the k-block
+      if (i < M && jb < N) {
+        f32x4 x[2] = {acc[a][2 * m], acc[a][2 * m + 1]};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (e.bias) x[h] += *reinterpret_cast<const f32x4*>(e.bias + jb + 16 * h + 4 * g);
+          if constexpr (epi_act_only(EPI)) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              float ga, gd;
+              epi_act_pair<EPI>(x[h][t], ga, gd);
+              x[h][t] = ga;
+            }
+          }
+        }
+        bf16x8 hi, lo;
+        split8(x[0], x[1], hi, lo);
+        char* dst = (char*)e.C + ((int64_t)i * e.ldc + jb) * 4 + 16 * g;
+        *reinterpret_cast<bf16x8*>(dst) = hi;
+        *reinterpret_cast<bf16x8*>(dst + 64) = lo;
+      }
+    }
+  }
+}
+
+// what the kernels below call: the image epilogue for TO = img_t, f32m's own for every other output
+template <int EPI, typename TO, typename TA>
+__device__ __forceinline__ void epilogue(const Epi& e, const f32x4 (&acc)[AI][AJ], int M, int N, int i0, int j0,
+                                         int z, int wave, int lane) {
+  if constexpr (std::is_same<TO, img_t>::value) epilogue_image<EPI>(e, acc, M, N, i0, j0, wave, lane);
+  else f32m::epilogue<EPI, TO, TA>(e, acc, M, N, i0, j0, z, wave, lane);
+}
+
+#include "gemm_f32_kernels.inc"
+
+}  // namespace f32a

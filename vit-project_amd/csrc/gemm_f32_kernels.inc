@@ -1,6 +1,7 @@
-// Included by gemm_f32.inc, once inside namespace f32m (SPLIT = 0 / 1: f32 operands) and once inside namespace
-// f32w (SPLIT = 2: Q is a pre-split weight image): the tile kernel and the stream-K kernel of the fp32 MFMA GEMM,
-// one text for both.  mainloop, epilogue and the constants are f32m's.
+// Included by gemm_f32.inc, once inside namespace f32m (SPLIT = 0 / 1: f32 operands), once inside namespace
+// f32w (SPLIT = 2: Q is a pre-split weight image) and once inside namespace f32a (SPLIT = 3: P is an activation
+// image too; TO = img_t: C is written as one): the tile kernel and the stream-K kernel of the fp32 MFMA GEMM,
+// one text for all.  mainloop and the constants are f32m's; epilogue is f32m's, wrapped in f32a.
 
 template <int PL, int QL, int EPI, typename TO, typename TA, int SPLIT>
 __global__ __launch_bounds__(THREADS, 2) void gemm_kernel(const float* __restrict__ P, int64_t ldp,

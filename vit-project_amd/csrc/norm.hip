@@ -9,6 +9,7 @@
 // scalar kernel (NV = 0) covers any other D (test configs).
 #include "common.hpp"
 #include "reduce.hpp"
+#include "bf16_split.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -40,6 +41,27 @@ template <> __device__ __forceinline__ void st4<bf16>(bf16* p, f32x4 v) {
 // first column of float4 group k of this lane
 __device__ __forceinline__ int col4(int lane, int k) { return (k * 64 + lane) * 4; }
 
+// TY of the vector forwards that write y as the pre-split image of the f32 y (VIT_F32_SPLIT; gemm_f32.inc SPLIT = 3,
+// DESIGN 4.26): 4-byte cells at the f32 row pitch.  A lane's four columns col4(lane, k) .. + 3 are one half of a
+// split8: q = lane % 8 < 4 holds the h = 0 half of lane group g = q of its 32-column k-block, q >= 4 the h = 1 half
+// of g = q - 4, so the partner is four lanes away.  After the exchange both lanes hold both halves; the low one
+// stores hi chunk g (byte 16 g of the block), the high one lo chunk g (byte 64 + 16 g): each lane the 16 bytes at
+// which it would have stored its f32 values.  Every lane of the wave must call it.
+struct f32img { float cell; };
+__device__ __forceinline__ void st4_image(f32img* p, f32x4 v, int lane) {
+  f32x4 o;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) o[t] = __shfl_xor(v[t], 4, 64);
+  const bool upper = lane & 4;
+  bf16x8 hi, lo;
+  split8(upper ? o : v, upper ? v : o, hi, lo);
+  *reinterpret_cast<bf16x8*>(p) = upper ? lo : hi;
+}
+template <typename TY> __device__ __forceinline__ void st4_y(TY* p, f32x4 v, int lane) {
+  if constexpr (std::is_same<TY, f32img>::value) st4_image(p, v, lane);
+  else st4<TY>(p, v);
+}
+
 template <int NV, typename TX, typename TY>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, int64_t ldx, TY* __restrict__ y,
                                                      int64_t ldy, const float* __restrict__ w,
@@ -68,7 +90,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, i
       f32x4 g = *reinterpret_cast<const f32x4*>(w + c), bb = *reinterpret_cast<const f32x4*>(b + c), o;
 #pragma unroll
       for (int t = 0; t < 4; ++t) o[t] = (v[k][t] - mu) * rs * g[t] + bb[t];
-      st4<TY>(yr + c, o);
+      st4_y<TY>(yr + c, o, lane);
     }
     if (lane == 0) { if (mean) mean[row] = mu; if (rstd) rstd[row] = rs; }
   } else {
@@ -78,6 +100,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, i
     float q = 0.f;
     for (int c = lane; c < D; c += 64) { float d = (float)xr[c] - mu; q += d * d; }
     const float rs = rsqrtf(wave_sum(q) / D + eps);
+    static_assert(!std::is_same<TY, f32img>::value, "the element-wise kernel has no image form");
     for (int c = lane; c < D; c += 64) yr[c] = (TY)(((float)xr[c] - mu) * rs * w[c] + b[c]);
     if (lane == 0) { if (mean) mean[row] = mu; if (rstd) rstd[row] = rs; }
   }
@@ -127,7 +150,7 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const float* __restrict
     f32x4 g = *reinterpret_cast<const f32x4*>(w + c), bb = *reinterpret_cast<const f32x4*>(b + c), o;
 #pragma unroll
     for (int t = 0; t < 4; ++t) o[t] = (v[k][t] - mu) * rs * g[t] + bb[t];
-    st4<TY>(yr + c, o);
+    st4_y<TY>(yr + c, o, lane);
   }
   if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
 }
@@ -415,6 +438,31 @@ static void launch_fwd(int nv, dim3 grid, hipStream_t s, const void* x, int64_t 
 // The vector kernels read and write 4 elements at a time: 16 bytes of f32, 8 of bf16 (null: not accessed).
 static bool ln_aligned(const void* p, int dtype) { return ((uintptr_t)p & (dtype == VIT_BF16 ? 7 : 15)) == 0; }
 
+// y as a pre-split image (VIT_F32_SPLIT): the vector kernels alone, at the widths the f32 form runs them (so mean,
+// rstd and y's values are the f32 call's bits).  The rule both entry points and the host query share: `add` = 1 for
+// vit_add_layer_norm_fwd (NV 1 .. 8), 0 for vit_layer_norm_fwd (NV 1, 2, 3, 4, 6, 8: D = 1280 and 1792 run the
+// element-wise kernel there); strides_or / ptrs_or: the OR of every row stride / address of the call.
+static bool ln_image_ok(int add, int D, int64_t strides_or, uint64_t ptrs_or) {
+  if (D <= 0 || D % 256 || D > 2048 || strides_or % 4 || (ptrs_or & 15)) return false;
+  return add || (D != 5 * 256 && D != 7 * 256);
+}
+// the image form of launch_fwd: no element-wise instantiation exists
+static bool launch_fwd_image(int nv, dim3 grid, hipStream_t s, const void* x, int64_t ldx, void* y, int64_t ldy,
+                             const float* w, const float* b, float* mean, float* rstd, int rows, int D, float eps) {
+#define F(NV) hipLaunchKernelGGL((ln_fwd_kernel<NV, float, f32img>), grid, dim3(64 * LN_WAVES), 0, s, (const float*)x, ldx, (f32img*)y, ldy, w, b, mean, rstd, rows, D, eps)
+  switch (nv) {
+    case 1: F(1); break;
+    case 2: F(2); break;
+    case 3: F(3); break;
+    case 4: F(4); break;
+    case 6: F(6); break;
+    case 8: F(8); break;
+    default: return false;
+  }
+#undef F
+  return true;
+}
+
 static int g_ln_pipe = -1;  // VIT_LN_BWD_PIPE / vit_layer_norm_bwd_variant: 1 pipelined (default), 0 plain loop
 
 template <typename TX, typename TD, typename TC>
@@ -436,6 +484,12 @@ static void launch_bwd(int nv, int nblk, hipStream_t s, const void* x, int64_t l
 
 extern "C" {
 
+// Host-only query (no GPU call): can vit_layer_norm_fwd (add == 0, f32 x) / vit_add_layer_norm_fwd (add != 0, f32 r)
+// write y as a pre-split image for this width, given the OR of every row stride and of every address of the call?
+int vit_layer_norm_fwd_image_ok(int add, int D, int64_t strides_or, uint64_t ptrs_or) {
+  return ln_image_ok(add, D, strides_or, ptrs_or) ? 1 : 0;
+}
+
 // F.layer_norm forward over rows of x (row stride ldx; f32 or bf16 in) -> y (dtype_y).
 int vit_layer_norm_fwd(int dtype_x, int dtype_y, int rows, int D, const void* x, int64_t ldx, void* y,
                        int64_t ldy, const float* w, const float* b, float* mean, float* rstd, float eps,
@@ -448,6 +502,14 @@ int vit_layer_norm_fwd(int dtype_x, int dtype_y, int rows, int D, const void* x,
   bool vec = (D % 256 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && ln_aligned(x, dtype_x) && ln_aligned(y, dtype_y) &&
              ln_aligned(w, VIT_F32) && ln_aligned(b, VIT_F32);
   int nv = vec ? D / 256 : 0;
+  if (dtype_y == VIT_F32_SPLIT) {  // y as a pre-split image: f32 x, vector kernels only (nothing else can write one)
+    if (dtype_x != VIT_F32 || !vec ||
+        !ln_image_ok(0, D, ldx | ldy, (uintptr_t)x | (uintptr_t)y | (uintptr_t)w | (uintptr_t)b) ||
+        !launch_fwd_image(nv, grid, s, x, ldx, y, ldy, w, b, mean, rstd, rows, D, eps))
+      return (int)hipErrorInvalidValue;
+    VIT_CHECK_LAUNCH();
+    return 0;
+  }
   if (dtype_x == VIT_F32 && dtype_y == VIT_F32) launch_fwd<float, float>(nv, grid, s, x, ldx, y, ldy, w, b, mean, rstd, rows, D, eps);
   else if (dtype_x == VIT_F32) launch_fwd<float, bf16>(nv, grid, s, x, ldx, y, ldy, w, b, mean, rstd, rows, D, eps);
   else if (dtype_y == VIT_BF16) launch_fwd<bf16, bf16>(nv, grid, s, x, ldx, y, ldy, w, b, mean, rstd, rows, D, eps);
@@ -472,13 +534,16 @@ int vit_add_layer_norm_fwd(int dtype_r, int dtype_y, int rows, int D, const floa
       !ln_aligned(w, VIT_F32) || !ln_aligned(b, VIT_F32))
     return (int)hipErrorInvalidValue;
   dim3 grid((rows + LN_WAVES - 1) / LN_WAVES);
-  if ((dtype_r != VIT_BF16 && dtype_r != VIT_F32) || (dtype_y != VIT_BF16 && dtype_y != VIT_F32))
+  if ((dtype_r != VIT_BF16 && dtype_r != VIT_F32) ||
+      (dtype_y != VIT_BF16 && dtype_y != VIT_F32 && dtype_y != VIT_F32_SPLIT))
     return (int)hipErrorInvalidValue;
+  if (dtype_y == VIT_F32_SPLIT && (dtype_r != VIT_F32 || y == nullptr)) return (int)hipErrorInvalidValue;
 #define A(NV, TR, TY)                                                                                          \
   hipLaunchKernelGGL((add_ln_fwd_kernel<NV, TR, TY>), grid, dim3(64 * LN_WAVES), 0, s, x, ldx, (const TR*)r, ldr, xs, \
                      ldxs, (TY*)y, ldy, w, b, mean, rstd, rows, D, eps)
 #define AD(NV)                                                         \
-  if (dtype_r == VIT_BF16 && dtype_y == VIT_BF16) A(NV, bf16, bf16);   \
+  if (dtype_y == VIT_F32_SPLIT) A(NV, float, f32img);                  \
+  else if (dtype_r == VIT_BF16 && dtype_y == VIT_BF16) A(NV, bf16, bf16);   \
   else if (dtype_r == VIT_BF16) A(NV, bf16, float);                    \
   else if (dtype_y == VIT_BF16) A(NV, float, bf16);                    \
   else A(NV, float, float);

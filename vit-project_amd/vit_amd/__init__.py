@@ -11,7 +11,7 @@ from .optim import FusedSGD, FusedAdamW, CosineAnnealingLRWithWarmup
 from .dora import DoRALayer, dora_weight
 from .lora import LoRALayer, lora_weight
 from .ops import set_float32_matmul_precision, get_float32_matmul_precision
-from .ops import get_float32_matmul_presplit, weight_image_bytes
+from .ops import get_float32_matmul_presplit, get_float32_matmul_presplit_activations, weight_image_bytes
 from .ops import set_float32_attention_precision, get_float32_attention_precision, get_float32_attention_long
 from . import rsa
 from . import clip
@@ -31,7 +31,7 @@ __all__ = ["VisionTransformer", "create_model", "cross_entropy", "set_wgrad_over
            "prefix_cache", "VisualPrefixCache", "LoRALayer", "lora_weight", "apply_lora_to_ViT", "unfreeze_lora_layers",
            "set_float32_matmul_precision", "get_float32_matmul_precision", "set_float32_attention_precision",
            "get_float32_attention_precision", "get_float32_attention_long", "get_float32_matmul_presplit",
-           "weight_image_bytes"]
+           "get_float32_matmul_presplit_activations", "weight_image_bytes"]
 
 
 def load_library(path=None):

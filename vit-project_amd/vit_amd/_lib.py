@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIT_HIP_LIB", os.path.join(_HERE, "lib", "libvit_hip.so"))
 
 F32, BF16 = 0, 1
+F32_SPLIT = 2  # VIT_DTYPE_F32_SPLIT: an f32-sized buffer holding the pre-split image of the f32 matrix
 LAY_RC, LAY_CR = 0, 1
 EPI_STORE, EPI_BIAS_GELU, EPI_RESID, EPI_GELU_BWD, EPI_PATCH, EPI_BIAS_QGELU, EPI_QGELU_BWD = range(7)
 # act-only forms of the fc1 pair for passes no backward follows (7 is the library's internal accumulate code)
@@ -37,6 +38,9 @@ SIGNATURES = {
     "vit_gemm_f32_count": [i32],
     "vit_gemm_f32_split_count": [i32],
     "vit_gemm_f32_presplit_count": [i32],
+    "vit_gemm_f32_presplit_act_count": [i32],
+    "vit_linear_fwd_f32_mfma": [i32, i32, i32, vp, i64, vp],
+    "vit_layer_norm_fwd_image_ok": [i32, i32, i64, C.c_uint64],
     "vit_gemm_f32_weight_image": [i32, i32, vp, i64, i32, vp, vp],
     "vit_linear_fwd_wimg": [i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp],
     "vit_linear_dgrad_wimg": [i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, vp, vp],

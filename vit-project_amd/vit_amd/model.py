@@ -355,30 +355,52 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
         if rs is None:  # the EPI_RESID epilogue reads its residual at the output's row stride: compact copy
             xc = torch.empty(B, D, dtype=f32, device=dev)
 
-    def fc1(sl):
+    def images(sl):
+        """Which of (h1, h2, act) over rows ``sl`` travel as pre-split activation images: forward-only
+        f32 blocks on the dense chain, where each is read by one GEMM and nothing else.  Both ends must be able to:
+        the consumer GEMM has a weight image and takes the MFMA path, and the producer -- the LayerNorm entry this
+        chain runs, or fc1 on the pre-split MFMA path itself -- can write an image.  Anything else keeps the f32
+        tensor and today's calls.  proj keeps its f32 operand (attention writes it)."""
+        if not fwd_only or ct or T != f32 or not ops.get_float32_matmul_presplit_activations():
+            return False, False, False
+        if pend is not None:  # ln1 is the fused add + LayerNorm
+            ln1_ok = ops.layer_norm_writes_image(h1[sl], pend[0][sl], pend[1][sl], x2[sl], n1w, n1b, add=True)
+        else:
+            ln1_ok = ops.layer_norm_writes_image(h1[sl], x2[sl], n1w, n1b)
+        if rs is not None:
+            ln2_ok = ops.layer_norm_writes_image(h2[sl], x2[sl], pb[sl], xm[sl], n2w, n2b, add=True)
+        else:
+            ln2_ok = ops.layer_norm_writes_image(h2[sl], xm[sl], n2w, n2b)
+        fc1_ok = ops.linear_fwd_takes_image(h2[sl], W1, I1)  # fc1 reads I1 on the MFMA path, whatever h2 holds
+        return (ln1_ok and ops.linear_fwd_takes_image(h1[sl], Wqkv, Iqkv), ln2_ok and fc1_ok,
+                fc1_ok and F % 32 == 0 and ops.linear_fwd_takes_image(act[sl], W2, I2))
+
+    def fc1(sl, x_image=False, out_image=False):
         if fwd_only:
-            return lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=act[sl], wimg=I1)
+            return lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=act[sl], wimg=I1,
+                                          x_image=x_image, out_image=out_image)
         return lambda: ops.linear_fwd(h2[sl], W1, fc1b.detach(), epi=act_epi, out=dact[sl], act_out=act[sl], wimg=I1)
 
-    def ln1(sl):
+    def ln1(sl, out_image=False):
         if pend is not None:
             return lambda: ops.add_layer_norm_fwd(pend[0][sl], pend[1][sl], x2[sl], n1w.detach(), n1b.detach(), eps,
-                                                  out=h1[sl], mean=m1[sl], rstd=r1[sl])
+                                                  out=h1[sl], mean=m1[sl], rstd=r1[sl], out_image=out_image)
         return lambda: ops.layer_norm_fwd(x2[sl], n1w.detach(), n1b.detach(), eps, T, out=h1[sl], mean=m1[sl],
-                                          rstd=r1[sl])
+                                          rstd=r1[sl], out_image=out_image)
 
     def chain_fused(b0, b1):
         sl = slice(b0 * N, b1 * N)
+        i1, i2, ia = images(sl)
         steps = [
-            ln1(sl),
-            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv),
+            ln1(sl, i1),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv, x_image=i1),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
                                  fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre),
             lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), out=pb[sl], wimg=Iproj),
             lambda: ops.add_layer_norm_fwd(x2[sl], pb[sl], xm[sl], n2w.detach(), n2b.detach(), eps, out=h2[sl],
-                                           mean=m2[sl], rstd=r2[sl]),
-            fc1(sl),
-            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), out=yb[sl], wimg=I2),
+                                           mean=m2[sl], rstd=r2[sl], out_image=i2),
+            fc1(sl, i2, ia),
+            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), out=yb[sl], wimg=I2, x_image=ia),
         ]
         if cfg.get("resid_last"):
             steps.append(lambda: ops.add_layer_norm_fwd(xm[sl], yb[sl], xo[sl]))
@@ -432,17 +454,19 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
             return chain_fused(b0, b1)
         r0, r1_ = b0 * N, b1 * N
         sl = slice(r0, r1_)
+        i1, i2, ia = images(sl)
         return [
             lambda: ops.layer_norm_fwd(x2[sl], n1w.detach(), n1b.detach(), eps, T, out=h1[sl], mean=m1[sl],
-                                       rstd=r1[sl]),
-            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv),
+                                       rstd=r1[sl], out_image=i1),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv, x_image=i1),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
                                  fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre),
             lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), epi=L.EPI_RESID, resid=x2[sl], out=xm[sl], wimg=Iproj),
             lambda: ops.layer_norm_fwd(xm[sl], n2w.detach(), n2b.detach(), eps, T, out=h2[sl], mean=m2[sl],
-                                       rstd=r2[sl]),
-            fc1(sl),
-            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), epi=L.EPI_RESID, resid=xm[sl], out=xo[sl], wimg=I2),
+                                       rstd=r2[sl], out_image=i2),
+            fc1(sl, i2, ia),
+            lambda: ops.linear_fwd(act[sl], W2, fc2b.detach(), epi=L.EPI_RESID, resid=xm[sl], out=xo[sl], wimg=I2,
+                                   x_image=ia),
         ]
 
     def run(steps):

@@ -78,12 +78,16 @@ def register_capture_stream(stream, device=None):
     _streamk(stream.device if device is None else device, stream)
 
 
-def linear_fwd(x2d, w, bias=None, epi=L.EPI_STORE, out=None, out_dtype=None, resid=None, act_out=None, wimg=None):
+def linear_fwd(x2d, w, bias=None, epi=L.EPI_STORE, out=None, out_dtype=None, resid=None, act_out=None, wimg=None,
+               x_image=False, out_image=False):
     """y = epi(x @ w^T + bias).  x2d [M,K] (row stride x2d.stride(0)), w [N,K] contiguous.
     EPI_BIAS_GELU / EPI_BIAS_QGELU return (act'(pre), act(pre)) with pre = x @ w^T + bias;
     EPI_BIAS_GELU_FWD / EPI_BIAS_QGELU_FWD (no backward follows) return act(pre) alone, the same bits.
     ``wimg``: the pre-split image of ``w`` (:func:`weight_image`), read in its place by the fp32 "high" MFMA
-    kernels -- the same bits."""
+    kernels -- the same bits.
+    ``x_image`` / ``out_image`` (fp32 "high" with ``wimg`` only): ``x2d`` holds / ``out`` receives the
+    pre-split image of the f32 matrix instead of its values (:func:`linear_fwd_takes_image`); a call the pre-split
+    MFMA kernels cannot run raises."""
     L.require_gpu(x2d)
     M, K = x2d.shape
     N = w.shape[0]
@@ -103,8 +107,10 @@ def linear_fwd(x2d, w, bias=None, epi=L.EPI_STORE, out=None, out_dtype=None, res
         assert resid.stride(0) == out.stride(0)
     if x2d.dtype == torch.float32:
         _streamk(x2d.device)
-    args = (L.dt(x2d), L.dt(out), epi, M, N, K, ptr(x2d), x2d.stride(0), ptr(w), ptr(bias), ptr(out), out.stride(0),
-            ptr(resid), ptr(act_out))
+    if x_image or out_image:
+        assert wimg is not None and x2d.dtype == torch.float32 and out.dtype == torch.float32
+    args = (L.F32_SPLIT if x_image else L.dt(x2d), L.F32_SPLIT if out_image else L.dt(out), epi, M, N, K, ptr(x2d),
+            x2d.stride(0), ptr(w), ptr(bias), ptr(out), out.stride(0), ptr(resid), ptr(act_out))
     if wimg is not None:
         assert wimg.numel() == N * K and wimg.dtype == torch.float32 and wimg.device == w.device
         call("vit_linear_fwd_wimg", *args, ptr(wimg), _s(x2d))
@@ -396,7 +402,9 @@ def colsum(x2d, out=None, accumulate=False):
 # LayerNorm
 # ----------------------------------------------------------------------------
 
-def layer_norm_fwd(x2d, w, b, eps, out_dtype, rows=None, ldx=None, out=None, need_stats=True, mean=None, rstd=None):
+def layer_norm_fwd(x2d, w, b, eps, out_dtype, rows=None, ldx=None, out=None, need_stats=True, mean=None, rstd=None,
+                   out_image=False):
+    """``out_image``: ``out`` (f32) receives the pre-split image of the f32 result (D % 256 == 0)."""
     rows = x2d.shape[0] if rows is None else rows
     D = w.numel()
     ldx = x2d.stride(0) if ldx is None else ldx
@@ -405,7 +413,8 @@ def layer_norm_fwd(x2d, w, b, eps, out_dtype, rows=None, ldx=None, out=None, nee
     if need_stats and mean is None:
         mean = torch.empty(rows, dtype=torch.float32, device=x2d.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x2d.device)
-    call("vit_layer_norm_fwd", L.dt(x2d), L.dt(out), rows, D, ptr(x2d), ldx, ptr(out), out.stride(0), ptr(w),
+    assert not out_image or out.dtype == torch.float32
+    call("vit_layer_norm_fwd", L.dt(x2d), L.F32_SPLIT if out_image else L.dt(out), rows, D, ptr(x2d), ldx, ptr(out), out.stride(0), ptr(w),
          ptr(b), ptr(mean), ptr(rstd), float(eps), _s(x2d))
     return out, mean, rstd
 
@@ -416,15 +425,19 @@ def add_layer_norm_supported(D: int) -> bool:
     return D % 256 == 0 and 256 <= D <= 2048
 
 
-def add_layer_norm_fwd(x2d, r2d, xs, w=None, b=None, eps=1e-6, out=None, mean=None, rstd=None):
+def add_layer_norm_fwd(x2d, r2d, xs, w=None, b=None, eps=1e-6, out=None, mean=None, rstd=None, out_image=False):
     """xs = x2d + r2d (f32 + bf16 / f32 -> f32; xs may be x2d) and, with ``out`` given, out =
     LayerNorm(xs) (bf16 / f32) with its row mean / rstd: a Linear's residual add fused into the
-    LayerNorm after it."""
+    LayerNorm after it.  ``out_image``: ``out`` (f32) receives the pre-split image of the f32 LayerNorm result."""
     assert x2d.dtype == torch.float32 and xs.dtype == torch.float32
     rows, D = xs.shape
     if out is not None:
         assert mean is not None and rstd is not None
-    call("vit_add_layer_norm_fwd", L.dt(r2d), L.dt(out) if out is not None else L.dt(r2d), rows, D, ptr(x2d),
+    ydt = L.dt(r2d) if out is None else L.dt(out)
+    if out_image:
+        assert out is not None and out.dtype == torch.float32
+        ydt = L.F32_SPLIT
+    call("vit_add_layer_norm_fwd", L.dt(r2d), ydt, rows, D, ptr(x2d),
          x2d.stride(0), ptr(r2d), r2d.stride(0), ptr(xs), xs.stride(0),
          ptr(out), out.stride(0) if out is not None else 0, ptr(w), ptr(b), ptr(mean), ptr(rstd), float(eps), _s(xs))
     return xs
@@ -866,7 +879,7 @@ def mse_bwd(pred, target, grad_loss=None):
 _F32_MATMUL = ("highest", "high")  # vit_gemm_f32_precision 0 / 1
 
 
-def set_float32_matmul_precision(precision, presplit_weights=False):
+def set_float32_matmul_precision(precision, presplit_weights=False, presplit_activations=False):
     """The arithmetic of the fp32 MFMA GEMMs (``compute_dtype=torch.float32``), after
     ``torch.set_float32_matmul_precision``:
 
@@ -894,7 +907,16 @@ def set_float32_matmul_precision(precision, presplit_weights=False):
     Computed weights (DoRA / LoRA ``out_proj.weight``), weight gradients and the patch embedding keep the
     in-loop split.  Both switches are set on every call, so a call without the keyword switches pre-splitting
     off (the images are freed at the model's next forward); :func:`get_float32_matmul_presplit` reads it and
-    ``VIT_F32_MATMUL_PRESPLIT=1`` beside ``VIT_F32_MATMUL=high`` sets the initial value."""
+    ``VIT_F32_MATMUL_PRESPLIT=1`` beside ``VIT_F32_MATMUL=high`` sets the initial value.
+
+    ``presplit_activations=True`` (with ``"high"`` and ``presplit_weights=True`` only; anything else raises
+    ``ValueError`` and changes nothing): in forward-only fp32 blocks on the dense chain, the
+    LayerNorms write ``h1`` / ``h2`` and fc1's epilogue writes ``act`` as pre-split images, byte for byte in place of
+    the f32 tensors, and the qkv / fc1 / fc2 GEMMs read both operands as images: no split is left in their k-steps.
+    The same MFMAs on the same bits again, so results and cache keys stay those of ``"high"``.  Training blocks,
+    the class-token / EOT tails, proj, computed weights and GEMMs off the MFMA path run as without the switch.
+    All three switches are set on every call; :func:`get_float32_matmul_presplit_activations` reads this one and
+    ``VIT_F32_MATMUL_PRESPLIT_ACT=1`` beside the other two variables sets its initial value."""
     if precision == "medium":
         raise ValueError('float32 matmul precision "medium" (operands rounded to one bfloat16) is not a mode of '
                          'the fp32 path: build the model with compute_dtype=torch.bfloat16')
@@ -903,8 +925,12 @@ def set_float32_matmul_precision(precision, presplit_weights=False):
     if presplit_weights and precision != "high":
         raise ValueError('presplit_weights=True keeps hi / lo images of the weights for the three bf16 products: it '
                          'needs precision "high"')
+    if presplit_activations and not presplit_weights:
+        raise ValueError('presplit_activations=True runs the GEMMs whose two operands are both pre-split images: it '
+                         'needs precision "high" and presplit_weights=True')
     L.lib().vit_gemm_f32_precision(_F32_MATMUL.index(precision))
     _F32_PRESPLIT[0] = bool(presplit_weights)
+    _F32_PRESPLIT_ACT[0] = bool(presplit_activations)
 
 
 def get_float32_matmul_precision() -> str:
@@ -920,6 +946,45 @@ def get_float32_matmul_presplit() -> bool:
     :func:`set_float32_matmul_precision` are on.  (``VIT_F32_MATMUL_PRESPLIT=1`` without ``VIT_F32_MATMUL=high``
     leaves this ``False``.)"""
     return bool(_F32_PRESPLIT[0] and L.lib().vit_gemm_f32_precision(-1) == 1)
+
+
+_F32_PRESPLIT_ACT = [os.environ.get("VIT_F32_MATMUL_PRESPLIT_ACT", "") == "1"]
+
+
+def get_float32_matmul_presplit_activations() -> bool:
+    """Whether forward-only fp32 blocks hand pre-split activation images from producer to GEMM: all three switches
+    of :func:`set_float32_matmul_precision` are on.  (``VIT_F32_MATMUL_PRESPLIT_ACT=1`` without the other two
+    variables leaves this ``False``.)"""
+    return bool(_F32_PRESPLIT_ACT[0] and get_float32_matmul_presplit())
+
+
+def linear_fwd_takes_image(x2d, w, wimg) -> bool:
+    """Whether ``linear_fwd(x2d, w, .., wimg=wimg)`` may be given ``x2d`` as a pre-split activation image: the switch
+    is on, the weight has an image and the library says an f32 forward of this geometry takes the MFMA path
+    (vit_linear_fwd_f32_mfma, host-only).  Ask before asking a producer for an image: the library refuses an image
+    it has no kernel for."""
+    if wimg is None or x2d.dtype != torch.float32 or not get_float32_matmul_presplit_activations():
+        return False
+    M, K = x2d.shape
+    return bool(L.lib().vit_linear_fwd_f32_mfma(M, w.shape[0], K, ptr(x2d), x2d.stride(0), ptr(w)))
+
+
+def layer_norm_writes_image(out, *others, add=False) -> bool:
+    """Whether ``layer_norm_fwd`` (``add=False``) / ``add_layer_norm_fwd`` (``add=True``) can write ``out`` as a
+    pre-split image, given every other 2-D tensor and vector of the call (vit_layer_norm_fwd_image_ok, host-only): f32
+    throughout, D a multiple of 256 up to 2048 that the entry runs on its vector kernels, strides and addresses
+    aligned.  Ask before asking the producer: the library refuses what it cannot write."""
+    ts = [t for t in (out, *others) if t is not None]
+    if not get_float32_matmul_presplit_activations() or any(t.dtype != torch.float32 for t in ts):
+        return False
+    strides = ptrs = 0
+    for t in ts:
+        ptrs |= t.data_ptr()
+        if t.dim() == 2:
+            if t.stride(1) != 1:
+                return False
+            strides |= t.stride(0)
+    return bool(L.lib().vit_layer_norm_fwd_image_ok(int(add), out.shape[1], strides, ptrs))
 
 
 def weight_image_raw(w, transposed=False, out=None):

@@ -466,9 +466,10 @@ def _sweep_worker(rank, world, make_model_and_optimizer, criterion, data, condit
         torch.set_num_threads(threads)
     mode = kw.pop("float32_matmul", None)
     presplit = kw.pop("float32_matmul_presplit", False)
+    presplit_act = kw.pop("float32_matmul_presplit_act", False)
     if mode is not None:
         from . import ops
-        ops.set_float32_matmul_precision(mode, presplit_weights=presplit)
+        ops.set_float32_matmul_precision(mode, presplit_weights=presplit, presplit_activations=presplit_act)
     mode = kw.pop("float32_attention", None)
     long_sequences = kw.pop("float32_attention_long", False)
     if mode is not None:
@@ -491,8 +492,8 @@ def launch_sweep(nprocs, make_model_and_optimizer, criterion, data, conditions, 
     must be picklable (module-level).  Returns {rank: [((start, length), csv, source)]}.
     ``cache_visual_prefix``: each worker builds and owns its visual prefix caches (``run_sweep``).
     The workers run in the caller's fp32 GEMM mode (``set_float32_matmul_precision``, its ``presplit_weights``
-    switch included; ``VIT_F32_MATMUL`` and ``VIT_F32_MATMUL_PRESPLIT`` are inherited through the environment as
-    well) and fp32 attention mode (``set_float32_attention_precision``,
+    and ``presplit_activations`` switches included; ``VIT_F32_MATMUL``, ``VIT_F32_MATMUL_PRESPLIT`` and
+    ``VIT_F32_MATMUL_PRESPLIT_ACT`` are inherited through the environment as well) and fp32 attention mode (``set_float32_attention_precision``,
     its ``long_sequences`` switch included; ``VIT_F32_ATTENTION``, ``VIT_F32_ATTENTION_LONG``)."""
     import torch.multiprocessing as mp
     from . import _lib, ops
@@ -501,6 +502,7 @@ def launch_sweep(nprocs, make_model_and_optimizer, criterion, data, conditions, 
     if _lib._lib is not None:  # (a process that never loaded the library cannot have switched the mode)
         kw = dict(kw, float32_matmul=ops.get_float32_matmul_precision(),
                   float32_matmul_presplit=ops.get_float32_matmul_presplit(),
+                  float32_matmul_presplit_act=ops.get_float32_matmul_presplit_activations(),
                   float32_attention=ops.get_float32_attention_precision(),
                   float32_attention_long=ops.get_float32_attention_long())
     ctx = mp.get_context("spawn")

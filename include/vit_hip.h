@@ -456,6 +456,26 @@ int vit_sdpa_f32_long_precision(int mode);
 /* Host-side count of vit_sdpa_fwd / vit_sdpa_bwd calls that took the streamed bf16x3 kernels (one per call; they
  * count in vit_sdpa_long_f32_count as well and never in vit_sdpa_f32_split_count; reset != 0 zeroes it). */
 int vit_sdpa_long_f32_split_count(int reset);
+/* Pre-split images through f32 "high" attention (additive to ABI 10), forward only.  qkv_img holds the
+ * pre-split activation image (the rule of vit_gemm_f32_weight_image, row by row at the f32 row pitch ld_qkv: what
+ * vit_linear_fwd_wimg writes with out_dtype VIT_DTYPE_F32_SPLIT) of the f32 qkv of vit_sdpa_fwd, and o_img receives the
+ * image of the f32 o that vit_sdpa_fwd would write (row pitch ld_o; what vit_linear_fwd_wimg reads with dtype
+ * VIT_DTYPE_F32_SPLIT); lse is vit_sdpa_fwd's.  The image forms of the bf16x3 kernels run: the same MFMAs on the same
+ * bits, so o_img is the image of vit_sdpa_fwd's o and lse its lse, bit for bit.  Both ends are images or neither.
+ * It launches only where vit_sdpa_fwd with f32 tensors would take the bf16x3 kernels: vit_sdpa_f32_precision is 1,
+ * head_dim 64, ld_qkv and ld_o multiples of 4, qkv_img and o_img 16-byte aligned (checked here; vit_sdpa_fwd takes
+ * that on trust), and either N <= 288 (causal or
+ * not) or N > 288 with causal == 0, the streamed kernels on (vit_sdpa_long_config) and vit_sdpa_f32_long_precision 1.
+ * Anything else returns hipErrorInvalidValue with nothing launched and nothing written: an image is never read as floats.
+ * vit_sdpa_fwd_takes_image (host-only, no GPU call): 1 exactly when that entry would launch; strides_or = ld_qkv | ld_o,
+ * ptrs_or = the OR of the addresses of qkv_img and o_img (lse is stored a float at a time: any address).  Ask before asking the qkv GEMM for an image.
+ * vit_sdpa_f32_image_count: calls of vit_sdpa_fwd_image that launched since the last reset (reset != 0 zeroes it); they
+ * count in vit_sdpa_f32_split_count (N <= 288) or vit_sdpa_long_f32_count and vit_sdpa_long_f32_split_count (past 288)
+ * as the f32 forms do. */
+int vit_sdpa_fwd_image(int B, int H, int N, int head_dim, const void* qkv_img, int64_t ld_qkv, void* o_img,
+                       int64_t ld_o, float* lse, float scale, int causal, void* stream);
+int vit_sdpa_fwd_takes_image(int B, int H, int N, int head_dim, int causal, int64_t strides_or, uint64_t ptrs_or);
+int vit_sdpa_f32_image_count(int reset);
 /* Tuning hook: the bf16 backward form for N <= 224 (-1 = from VIT_ATTN_BWD_SPLIT, 1 = whole-head fused
  * (the default), 2 = two kernels; 0, round 4's banded form, was removed in ABI 8: hipErrorInvalidValue).
  * The two forms agree to bf16 rounding (some f32 sums are ordered differently). */

@@ -5,6 +5,11 @@ H = 16, N = 257) and the text tower's (B = 66, H = 12, N = 77, causal).  Per sha
 ratio of the medians and whether it counts (past twice the larger spread).  Prints one JSON line per shape.
 
     python tools/bench_attn_f32.py [--pairs 3] [--reps 20] [--shape B,H,N,causal ...]
+
+``--image``: the "high" forward on f32 qkv / o against the image forward (qkv and o as pre-split images,
+``vit_sdpa_fwd_image``), alternated the same way; past 288 tokens both sides run the streamed kernels
+(``long_sequences=True``).  The o image must equal the image of the f32 o and lse must be equal, bit for bit, before
+anything is timed.
 """
 import argparse
 import json
@@ -78,17 +83,55 @@ def shape_leg(B, H, N, causal, pairs, reps):
     return rec
 
 
+def image_leg(B, H, N, causal, pairs, reps):
+    """f32 "high" forward against the image forward of the same values."""
+    D = H * 64
+    g = torch.Generator().manual_seed(0)
+    qkv = (torch.randn(B * N, 3 * D, generator=g) * 1.5).cuda()
+    lib = L.lib()
+    sides = ("f32", "image")
+    us = {m: [] for m in sides}
+    try:
+        ops.set_float32_attention_precision("high", long_sequences=N > 288, presplit=True)
+        qimg = ops.weight_image_raw(qkv)   # an activation image is the row-by-row image of the matrix
+        o, lse = ops.sdpa_fwd(qkv, B, H, N, causal=causal)
+        oi, lsei = torch.empty_like(o), torch.empty_like(lse)
+        assert ops.sdpa_fwd_takes_image(qimg, B, H, N, oi, lsei, causal=causal)
+        calls = {"f32": lambda: ops.sdpa_fwd(qkv, B, H, N, o=o, lse=lse, causal=causal),
+                 "image": lambda: ops.sdpa_fwd(qimg, B, H, N, o=oi, lse=lsei, causal=causal, image=True)}
+        c0 = lib.vit_sdpa_f32_image_count(0)
+        for fn in calls.values():
+            window(fn, 3)
+        assert lib.vit_sdpa_f32_image_count(0) - c0 == 3
+        assert torch.equal(oi.view(torch.int32), ops.weight_image_raw(o).view(torch.int32)), "o image != image of o"
+        assert torch.equal(lsei.view(torch.int32), lse.view(torch.int32)), "lse differs"
+        for _ in range(pairs):
+            for m in sides:
+                us[m].append(window(calls[m], reps))
+    finally:
+        ops.set_float32_attention_precision("highest")
+    rec = {"B": B, "H": H, "N": N, "causal": bool(causal), "pairs": pairs, "reps": reps, "bits_equal": True}
+    s = {m: summary(us[m]) for m in sides}
+    ratio = s["f32"]["median_us"] / s["image"]["median_us"]
+    fl = 4.0 * B * H * N * N * 64 * (0.5 if causal else 1.0)
+    rec["fwd"] = dict(s, image_speedup=round(ratio, 3),
+                      counts=bool(abs(ratio - 1) > 2 * max(s[m]["spread"] for m in sides)),
+                      image_tflops_of_the_f32_product=round(fl / s["image"]["median_us"] / 1e6, 1))
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=3, help="alternating (highest, high) pairs, at least 3")
     ap.add_argument("--reps", type=int, default=20, help="calls per timed window")
     ap.add_argument("--shape", action="append", default=None, help="B,H,N,causal (0 / 1); may be given more than once")
+    ap.add_argument("--image", action="store_true", help='the "high" forward on f32 tensors against the image forward')
     a = ap.parse_args()
     if a.pairs < 3:
         ap.error("--pairs must be at least 3: the spread is part of the record")
     shapes = [tuple(int(x) for x in s.split(",")) for s in a.shape] if a.shape else [(64, 16, 257, 0), (66, 12, 77, 1)]
     for B, H, N, causal in shapes:
-        print(json.dumps(shape_leg(B, H, N, causal, a.pairs, a.reps)), flush=True)
+        print(json.dumps((image_leg if a.image else shape_leg)(B, H, N, causal, a.pairs, a.reps)), flush=True)
 
 
 if __name__ == "__main__":

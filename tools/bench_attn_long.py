@@ -18,6 +18,10 @@ alternated over P pairs in this one process, as tools/bench_attn_f32.py alternat
 and mode the median of P windows of --reps back-to-back calls, the spread (max - min) / median, the ratio of the
 medians and whether it counts (past twice the larger spread).  One JSON line.
 
+--image (with --dtype f32 --pairs P): the streamed "high" forward on f32 qkv / o against the image
+forward (``vit_sdpa_fwd_image``) at --n, alternated the same way (tools/bench_attn_f32.py's image leg: bit equality of
+the two sides is asserted before anything is timed).  One JSON line.
+
 Prints one JSON line per (variant, round) and a final summary line.  --no-generic / --no-streamed skip a
 variant (a tree without the streamed kernels can still time its resident kernels with --n 0).
 """
@@ -176,10 +180,18 @@ def main():
     ap.add_argument("--no-streamed", action="store_true")
     ap.add_argument("--pairs", type=int, default=0, help="--dtype f32: alternate the streamed kernels' highest and "
                     "high + long arithmetic over this many pairs (at least 3) instead of the variants above")
+    ap.add_argument("--image", action="store_true", help="with --dtype f32 --pairs: the streamed high forward on f32 "
+                    "tensors against the image forward")
     a = ap.parse_args()
+    if a.image and not a.pairs:
+        ap.error("--image needs --pairs")
     if a.pairs:
         if a.pairs < 3 or a.dtype != "f32" or a.fp8 or a.n <= 288:
             ap.error("--pairs needs at least 3 pairs, --dtype f32, --n past 288 and no --fp8")
+        if a.image:
+            from tools.bench_attn_f32 import image_leg
+            print(json.dumps(image_leg(a.batch, a.heads, a.n, 0, a.pairs, a.reps)), flush=True)
+            return None
         return main_pairs(a)
     lib = L.lib()
     dtype = torch.float32 if a.dtype == "f32" else torch.bfloat16

@@ -93,14 +93,16 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds, which="cls",
         switch = lambda on: vit_amd.set_float32_matmul_precision("high", presplit_weights=on)
     elif which == "f32act":  # "high" with weight images throughout; activation images off and on
         switch = lambda on: vit_amd.set_float32_matmul_precision("high", presplit_weights=True, presplit_activations=on)
+    elif which == "f32attnimg":  # attention "high" throughout; images through attention off and on
+        switch = lambda on: vit_amd.set_float32_attention_precision("high", presplit=on)
     elif which == "f32attn":  # the fp32 attention mode off and on, the GEMM mode as --f32-matmul says
         switch = lambda on: vit_amd.set_float32_attention_precision("high" if on else "highest")
     else:
         switch = m.clip_model.set_cls_tail if which == "cls" else m.clip_model.set_eot_tail
-    if which in ("eot", "f32", "f32attn", "f32pre", "f32act"):
+    if which in ("eot", "f32", "f32attn", "f32attnimg", "f32pre", "f32act"):
         m.clip_model.set_cls_tail(cls_fixed)
     key = {"f32": "f32_high", "f32attn": "f32_attention_high", "f32pre": "f32_presplit",
-           "f32act": "f32_presplit_act"}.get(which, which + "_tail")
+           "f32act": "f32_presplit_act", "f32attnimg": "f32_attention_presplit"}.get(which, which + "_tail")
 
     def window(n):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -139,7 +141,7 @@ def cls_tail_leg(dev, dtype, batch, steps, warmup, adapter, rounds, which="cls",
     return {"ms_per_step": {key + "_off": off, key + "_on": on}, key + "_speedup": round(off["median"] / on["median"], 4),
             "images_per_sec": {key + "_off": round(batch / off["median"] * 1e3, 2),
                                key + "_on": round(batch / on["median"] * 1e3, 2)},
-            "cls_tail_throughout": bool(which in ("eot", "f32", "f32attn", "f32pre", "f32act") and cls_fixed),
+            "cls_tail_throughout": bool(which in ("eot", "f32", "f32attn", "f32attnimg", "f32pre", "f32act") and cls_fixed),
             "weight_image_bytes": held,
             "predictions_bit_equal": bool(torch.equal(preds[True], preds[False])),
             "prediction_rel_diff_on_vs_off": float((preds[True] - preds[False]).abs().max() / preds[False].abs().max()),
@@ -185,8 +187,17 @@ def main():
     ap.add_argument("--f32-attention-ab", action="store_true",
                     help="alternate --f32-attention highest and high in one process, the GEMMs as --f32-matmul says "
                          "(with --cls-tail: that tail on throughout)")
+    ap.add_argument("--f32-attention-presplit", action="store_true",
+                    help="with --f32-attention high: forward-only blocks carry pre-split images through attention "
+                         "(set_float32_attention_precision('high', presplit=True); needs the --f32-presplit-act chain)")
+    ap.add_argument("--f32-attention-presplit-ab", action="store_true",
+                    help="alternate attention high without and with images through attention in one process, the GEMMs "
+                         "as the --f32-matmul flags say (the baseline: --f32-matmul high --f32-presplit "
+                         "--f32-presplit-act)")
     a = ap.parse_args()
     import torch
+    if a.f32_attention_presplit and a.f32_attention != "high":
+        ap.error("--f32-attention-presplit needs --f32-attention high")
     if a.f32_matmul:
         import vit_amd
         if a.f32_presplit_act and not a.f32_presplit:
@@ -197,12 +208,13 @@ def main():
         ap.error("--f32-presplit / --f32-presplit-act need --f32-matmul high")
     if a.f32_attention:
         import vit_amd
-        vit_amd.set_float32_attention_precision(a.f32_attention)
-    if a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab:
+        vit_amd.set_float32_attention_precision(a.f32_attention, presplit=a.f32_attention_presplit)
+    if (a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab
+            or a.f32_attention_presplit_ab):
         if a.rounds < 3:
             ap.error("--rounds must be at least 3: the spread is part of the record")
         r = cls_tail_leg(torch.device("cuda", 0), a.dtype, a.batch, a.steps, a.warmup, a.adapter, a.rounds,
-                         "f32act" if a.f32_presplit_act_ab else "f32pre" if a.f32_presplit_ab else "f32attn" if a.f32_attention_ab else "f32" if a.f32_ab else "eot" if a.eot_tail else "cls",
+                         "f32attnimg" if a.f32_attention_presplit_ab else "f32act" if a.f32_presplit_act_ab else "f32pre" if a.f32_presplit_ab else "f32attn" if a.f32_attention_ab else "f32" if a.f32_ab else "eot" if a.eot_tail else "cls",
                          a.cls_tail)
     else:
         leg = bench.c3_leg if a.adapter == "dora" else lora_leg
@@ -217,6 +229,8 @@ def main():
         r["f32_presplit_act"] = "ab" if a.f32_presplit_act_ab else bool(a.f32_presplit_act)
     if a.f32_attention:
         r["f32_attention"] = a.f32_attention
+    if a.f32_attention_presplit or a.f32_attention_presplit_ab:
+        r["f32_attention_presplit"] = "ab" if a.f32_attention_presplit_ab else True
     print(json.dumps(r))
 
 

@@ -44,6 +44,10 @@ on throughout): ``f32_high_speedup``, records ``bench_clip_cached_f32high[_clsta
 in-loop ``high`` (the plain series) and pre-split ``high`` (the ``*_tail`` series) on the same prefix caches, which
 both read as hits: ``f32_presplit_speedup``, ``weight_image_bytes``, records
 ``bench_clip_cached_f32high_presplit[_clstail]_{dtype}.json``.
+``--f32-attention-presplit`` (with ``--f32-attention high``) carries pre-split images through attention in the
+forward-only blocks; ``--f32-attention-presplit-ab`` alternates attention ``high`` without and with them,
+the GEMMs as the ``--f32-matmul`` flags say (the baseline: ``--f32-matmul high --f32-presplit --f32-presplit-act``), on
+one set of caches: ``f32_attention_presplit_speedup``, ``cache_build_seconds_ab``.
 ``--f32-presplit-act`` (with ``--f32-matmul high --f32-presplit``) adds pre-split activation images in the forward-only
 blocks; ``--f32-presplit-act-ab`` (with ``--f32-matmul high``) alternates pre-split weights and
 pre-split weights + activations, one set of caches again, and times the prefix-cache build itself in either mode,
@@ -122,7 +126,8 @@ def model_leg(a, dtype_name):
         pred_diff = float((pc - pu).abs().max() / pu.abs().max())
 
     fixed = caches["train"].take(torch.arange(a.batch))
-    ab = a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab  # an fp32 mode alternates
+    ab = (a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab
+          or a.f32_attention_presplit_ab)  # an fp32 mode alternates
     tails = (False, True) if (a.cls_tail or a.eot_tail or ab) else (False,)
     # the switch that alternates: the EOT tail if asked for (the class-token tail then stays as --cls-tail says)
     set_tail = m.clip_model.set_eot_tail if a.eot_tail else m.clip_model.set_cls_tail
@@ -132,7 +137,10 @@ def model_leg(a, dtype_name):
     if ab:  # the fp32 GEMM (or attention) mode alternates; each mode reads the prefix caches built in it
         set_mode = (vit_amd.set_float32_attention_precision if a.f32_attention_ab
                     else vit_amd.set_float32_matmul_precision)
-        if a.f32_presplit_act_ab:  # weight images throughout, activation images off and on: the same bits again
+        if a.f32_attention_presplit_ab:  # attention "high" throughout, images through it off and on: the same bits
+            set_mode = lambda mode: vit_amd.set_float32_attention_precision("high", presplit=mode == "high")
+            by_mode = {False: caches, True: caches}
+        elif a.f32_presplit_act_ab:  # weight images throughout, activation images off and on: the same bits again
             set_mode = lambda mode: vit_amd.set_float32_matmul_precision("high", presplit_weights=True,
                                                                          presplit_activations=mode == "high")
             by_mode = {False: caches, True: caches}
@@ -143,7 +151,8 @@ def model_leg(a, dtype_name):
             set_mode("high")
             by_mode = {False: caches, True: S.prefix_caches_for(m, data, None, a.batch)}
         set_mode("highest")
-        tail_key = ("f32_presplit_act" if a.f32_presplit_act_ab else "f32_presplit" if a.f32_presplit_ab
+        tail_key = ("f32_attention_presplit" if a.f32_attention_presplit_ab else
+                    "f32_presplit_act" if a.f32_presplit_act_ab else "f32_presplit" if a.f32_presplit_ab
                     else "f32_attention_high" if a.f32_attention_ab else "f32_high")
 
         def set_tail(on):
@@ -251,20 +260,21 @@ def model_leg(a, dtype_name):
         rho = {}
         for t in tails:
             set_tail(t)
-            rho[("act" if t else "presplit") if a.f32_presplit_act_ab else ("presplit" if t else "high") if a.f32_presplit_ab else ("high" if t else "highest")] = float(S.behavioral_rsa(m, data["inference"], data["reference_rdm"])[0])
+            rho[("attnimg" if t else "attn") if a.f32_attention_presplit_ab else ("act" if t else "presplit") if a.f32_presplit_act_ab else ("presplit" if t else "high") if a.f32_presplit_ab else ("high" if t else "highest")] = float(S.behavioral_rsa(m, data["inference"], data["reference_rdm"])[0])
         set_tail(False)
         rec[tail_key + "_rsa_rho"] = rho
     if len(tails) > 1:
         rec[tail_key + "_prediction_rel_diff"] = tail_diff
         rec[tail_key + "_prediction_bound"] = 1e-3 if dtype_name == "f32" else 3e-2
         rec["cls_tail_throughout"] = bool((a.eot_tail or ab) and a.cls_tail)
-    if a.f32_presplit_act_ab:  # the prefix-cache build itself, weights-only against weights + activations
-        builds = {"presplit": [], "act": []}
+    if a.f32_presplit_act_ab or a.f32_attention_presplit_ab:  # the prefix-cache build itself, off against on
+        bk = ("attn", "attnimg") if a.f32_attention_presplit_ab else ("presplit", "act")
+        builds = {k: [] for k in bk}
         for _ in range(a.rounds):
             for t in tails:
                 set_tail(t)
                 dt, fresh = _timed(lambda: S.prefix_caches_for(m, data, None, a.batch), sync)
-                builds["act" if t else "presplit"].append(dt)
+                builds[bk[t]].append(dt)
         set_tail(False)
         rec["cache_build_seconds_ab"] = {k: _summary(v) for k, v in builds.items()}
         rec["cache_build_rows_bit_equal"] = bool(torch.equal(fresh["train"].take(idx), caches["train"].take(idx)))
@@ -278,6 +288,7 @@ def model_leg(a, dtype_name):
     rec["f32_presplit_act"] = "ab" if a.f32_presplit_act_ab else vit_amd.get_float32_matmul_presplit_activations()
     rec["f32_matmul"], rec["f32_attention"] = (vit_amd.get_float32_matmul_precision(),
                                                "ab" if a.f32_attention_ab else vit_amd.get_float32_attention_precision())
+    rec["f32_attention_presplit"] = "ab" if a.f32_attention_presplit_ab else vit_amd.get_float32_attention_presplit()
     rec["train_step_images_per_sec"]["cached_without_gather"] = _summary(no_gather)
     return rec
 
@@ -360,8 +371,12 @@ def driver(a):
             cmd.append("--f32-attention-ab")
         if a.f32_attention:
             cmd += ["--f32-attention", a.f32_attention]
+        if a.f32_attention_presplit:
+            cmd.append("--f32-attention-presplit")
+        if a.f32_attention_presplit_ab:
+            cmd.append("--f32-attention-presplit-ab")
         print("leg", leg, flush=True)
-        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if (a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab) else 1)).returncode  # TimeoutExpired ends the run
+        rc = subprocess.run(cmd, timeout=LEG_TIMEOUT[leg] * a.timeout_scale * (2 if (a.cls_tail or a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab or a.f32_attention_presplit_ab) else 1)).returncode  # TimeoutExpired ends the run
         if rc != 0:
             print(f"leg {leg} failed with exit code {rc}: stopping", flush=True)
             return rc
@@ -409,7 +424,17 @@ def main():
     ap.add_argument("--f32-attention-ab", action="store_true",
                     help="alternate the fp32 attention modes highest and high, the GEMMs as --f32-matmul says (with "
                          "--cls-tail: that tail on throughout)")
+    ap.add_argument("--f32-attention-presplit", action="store_true",
+                    help="with --f32-attention high: pre-split images through attention in forward-only blocks")
+    ap.add_argument("--f32-attention-presplit-ab", action="store_true",
+                    help="alternate attention high without and with images through attention, the GEMMs as the "
+                         "--f32-matmul flags say")
     a = ap.parse_args()
+    if a.f32_attention_presplit and a.f32_attention != "high":
+        ap.error("--f32-attention-presplit needs --f32-attention high")
+    if a.f32_attention_presplit_ab and (a.eot_tail or a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab
+                                        or a.f32_presplit_act_ab or a.f32_attention == "highest"):
+        ap.error("--f32-attention-presplit-ab alternates the images through attention alone, attention at high")
     if a.rounds < 3:
         ap.error("--rounds must be at least 3: the spread is part of the record")
     if a.f32_ab and (a.eot_tail or a.f32_matmul):
@@ -433,14 +458,16 @@ def main():
                                              presplit_activations=a.f32_presplit_act)
     if a.f32_attention:
         import vit_amd
-        vit_amd.set_float32_attention_precision(a.f32_attention)
+        vit_amd.set_float32_attention_precision(a.f32_attention, presplit=a.f32_attention_presplit)
     rec = gather_leg(a) if a.leg == "gather" else model_leg(a, a.leg)
     os.makedirs(a.out, exist_ok=True)
     tag = (("" if a.adapter == "dora" else f"_{a.adapter}") + ("_eottail" if a.eot_tail else "")
            + ("_f32high" if (a.f32_ab or a.f32_matmul == "high") else "")
            + ("_presplitact" if (a.f32_presplit_act or a.f32_presplit_act_ab) else
               "_presplit" if (a.f32_presplit or a.f32_presplit_ab) else "")
-           + ("_f32attnhigh" if (a.f32_attention_ab or a.f32_attention == "high") else "") + ("_clstail" if a.cls_tail else ""))
+           + ("_f32attnhigh" if (a.f32_attention_ab or a.f32_attention == "high") else "")
+           + ("_attnpresplit" if (a.f32_attention_presplit or a.f32_attention_presplit_ab) else "")
+           + ("_clstail" if a.cls_tail else ""))
     name = "gather_blocks.json" if a.leg == "gather" else f"bench_clip_cached{tag}_{a.leg}.json"
     with open(os.path.join(a.out, name), "w") as fh:
         json.dump(rec, fh, indent=1)

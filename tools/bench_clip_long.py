@@ -7,6 +7,7 @@ tokens on the streamed f32 kernels against the generic ones (vit_sdpa_long_confi
                                     [--f32-matmul highest|high] [--f32-ab] [--f32-presplit] [--f32-presplit-ab]
                                     [--f32-presplit-act] [--f32-presplit-act-ab]
                                     [--f32-attention highest|high] [--f32-attention-ab] [--f32-attention-long]
+                                    [--f32-attention-presplit] [--f32-attention-presplit-ab]
 
 ``--f32-matmul`` sets the fp32 GEMM arithmetic of the run (``high`` = bf16x3); ``--f32-ab``
 alternates ``highest`` and ``high`` instead, both on the streamed attention kernels.  ``--f32-attention`` and
@@ -19,6 +20,11 @@ difference between the two modes' predictions on the batch over the largest pred
 ``--f32-presplit`` (with ``--f32-matmul high``) keeps pre-split images of the frozen fp32 weights (DESIGN §4.25);
 ``--f32-presplit-ab`` alternates in-loop ``high`` and pre-split ``high`` (sides ``high`` / ``presplit``), the
 attention as ``--f32-attention`` says, and records whether the two sides' predictions are the same bits.
+``--f32-attention-presplit`` (with ``--f32-attention high``) carries pre-split images through attention
+in the forward-only blocks; ``--f32-attention-presplit-ab`` alternates attention ``high`` without and with them (sides
+``attn`` / ``attnimg``), ``long_sequences`` as ``--f32-attention-long`` says on both sides and the GEMMs as the
+``--f32-matmul`` flags say (the baseline: ``--f32-matmul high --f32-presplit --f32-presplit-act --f32-attention-long``),
+and records whether the two sides' predictions are the same bits.
 """
 import argparse
 import json
@@ -57,18 +63,29 @@ def main():
     ap.add_argument("--f32-attention-ab", action="store_true")
     ap.add_argument("--f32-attention-long", action="store_true",
                     help="with --f32-attention high or --f32-attention-ab: high also covers streamed attention")
+    ap.add_argument("--f32-attention-presplit", action="store_true",
+                    help="with --f32-attention high: pre-split images through attention (DESIGN 4.27)")
+    ap.add_argument("--f32-attention-presplit-ab", action="store_true",
+                    help="alternate attention high without and with images through attention")
     a = ap.parse_args()
-    if a.f32_ab + a.f32_attention_ab + a.f32_presplit_ab + a.f32_presplit_act_ab > 1:
+    if a.f32_ab + a.f32_attention_ab + a.f32_presplit_ab + a.f32_presplit_act_ab + a.f32_attention_presplit_ab > 1:
         ap.error("one switch alternates at a time")
+    if a.f32_attention_presplit and a.f32_attention != "high":
+        ap.error("--f32-attention-presplit needs --f32-attention high")
+    if a.f32_attention_presplit_ab and a.f32_attention not in (None, "high"):
+        ap.error("--f32-attention-presplit-ab runs attention high on both sides")
     if a.f32_presplit and a.f32_matmul != "high":
         ap.error("--f32-presplit needs --f32-matmul high")
     if a.f32_presplit_act and not a.f32_presplit:
         ap.error("--f32-presplit-act needs --f32-matmul high --f32-presplit")
-    if a.f32_attention_long and not (a.f32_attention == "high" or a.f32_attention_ab):
-        ap.error("--f32-attention-long needs --f32-attention high or --f32-attention-ab")
+    if a.f32_attention_long and not (a.f32_attention == "high" or a.f32_attention_ab or a.f32_attention_presplit_ab):
+        ap.error("--f32-attention-long needs --f32-attention high, --f32-attention-ab or --f32-attention-presplit-ab")
 
-    def set_attention(mode):
-        vit_amd.set_float32_attention_precision(mode, long_sequences=a.f32_attention_long and mode == "high")
+    def set_attention(mode, presplit=None):
+        high = mode == "high"
+        vit_amd.set_float32_attention_precision(
+            mode, long_sequences=a.f32_attention_long and high,
+            presplit=high and (a.f32_attention_presplit if presplit is None else presplit))
     if a.f32_matmul:
         vit_amd.set_float32_matmul_precision(a.f32_matmul, presplit_weights=a.f32_presplit,
                                              presplit_activations=a.f32_presplit_act)
@@ -85,6 +102,9 @@ def main():
         set_mode = lambda name: vit_amd.set_float32_matmul_precision(
             "highest" if name == "highest" else "high", presplit_weights=name != "highest",
             presplit_activations=name == "act")
+    if a.f32_attention_presplit_ab:  # attention high (+ long as asked) on both sides, the images off and on
+        sides = ("attn", "attnimg")
+        set_mode = lambda name: set_attention("highest" if name == "highest" else "high", presplit=name == "attnimg")
     dev = torch.device("cuda", 0)
     lib = L.lib()
     torch.manual_seed(0)
@@ -118,7 +138,7 @@ def main():
         assert torch.isfinite(loss)
         return a.batch * steps / dt, lib.vit_sdpa_long_f32_count(0) - c0
 
-    if a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab:
+    if a.f32_ab or a.f32_attention_ab or a.f32_presplit_ab or a.f32_presplit_act_ab or a.f32_attention_presplit_ab:
         ips = {k: [] for k in sides}
         extra = {}
         try:
@@ -137,6 +157,20 @@ def main():
                     if name == "presplit":
                         extra["weight_image_bytes"] = vit_amd.weight_image_bytes(m)
                 extra["predictions_bit_equal"] = bool(torch.equal(preds[sides[0]], preds[sides[1]]))
+            if a.f32_attention_presplit_ab:
+                lib.vit_sdpa_long_config(1)
+                with torch.no_grad():  # (the first forward of a process: see above)
+                    m(x)
+                preds = {}
+                for name in ips:
+                    set_mode(name)
+                    c0 = lib.vit_sdpa_f32_image_count(0)
+                    with torch.no_grad():
+                        preds[name] = m(x)
+                    extra["image_launches_" + name] = lib.vit_sdpa_f32_image_count(0) - c0
+                assert extra["image_launches_attn"] == 0, extra
+                extra["predictions_bit_equal"] = bool(torch.equal(preds["attn"], preds["attnimg"]))
+                extra["f32_attention_long"] = bool(a.f32_attention_long)
             if a.f32_attention_ab and a.f32_attention_long:
                 lib.vit_sdpa_long_config(1)
                 preds = {}
@@ -159,7 +193,8 @@ def main():
         med = {k: statistics.median(v) for k, v in ips.items()}
         print(json.dumps({"metric": "images/sec CLIP-HBA ViT-L/14@336px + DoRA fp32 train step", "batch": a.batch,
                           "steps": a.steps, "rounds": a.rounds, "images_per_sec": ips, "median": med,
-                          "alternated": ("f32_presplit_act" if a.f32_presplit_act_ab else
+                          "alternated": ("f32_attention_presplit" if a.f32_attention_presplit_ab else
+                                         "f32_presplit_act" if a.f32_presplit_act_ab else
                                          "f32_presplit" if a.f32_presplit_ab else
                                          "f32_attention" if a.f32_attention_ab else "f32_matmul"),
                           "f32_matmul": "ab" if a.f32_ab else "high" if (a.f32_presplit_ab or a.f32_presplit_act_ab) else (a.f32_matmul or "highest"),

@@ -63,6 +63,14 @@ def presplit_act_pairs(a, dev, M, D, x, h, w, b, wi):
         "fwd qkv (bias), image X": (
             lambda: fwd(x, w["qkv"], b["qkv"], out=y3, wimg=wi["qkv"]),
             lambda: fwd(ximg, w["qkv"], b["qkv"], out=y3, wimg=wi["qkv"], x_image=True), 2 * M * 3 * D * D, None, False),
+        "fwd proj (bias + residual), image X": (   # its X is the attention kernels' o image
+            lambda: fwd(x, w["proj"], b["proj"], epi=L.EPI_RESID, resid=r, out=y, wimg=wi["proj"]),
+            lambda: fwd(ximg, w["proj"], b["proj"], epi=L.EPI_RESID, resid=r, out=y, wimg=wi["proj"], x_image=True),
+            2 * M * D * D, None, False),
+        "producer: qkv epilogue, image X, image Y": (   # ... and the qkv GEMM writes attention's operand image
+            lambda: fwd(ximg, w["qkv"], b["qkv"], out=y3, wimg=wi["qkv"], x_image=True),
+            lambda: fwd(ximg, w["qkv"], b["qkv"], out=y3, wimg=wi["qkv"], x_image=True, out_image=True),
+            2 * M * 3 * D * D, None, True),
         "fwd fc1 (bias + QuickGELU act-only), image X, image Y": (
             lambda: fwd(x, w["fc1"], b["fc1"], epi=QG, out=y4, wimg=wi["fc1"]),
             lambda: fwd(ximg, w["fc1"], b["fc1"], epi=QG, out=y4, wimg=wi["fc1"], x_image=True, out_image=True),
@@ -93,7 +101,7 @@ def presplit_act_pairs(a, dev, M, D, x, h, w, b, wi):
                 c0 = lib.vit_gemm_f32_presplit_act_count(0)
                 t[side].append(timeit(fns[side], a.reps))
                 reads = lib.vit_gemm_f32_presplit_act_count(0) > c0
-                assert reads == (side == "act" and "image X" in name), (name, side)
+                assert reads == ("image X" in name and (side == "act" or name.startswith("producer: qkv"))), (name, side)
                 outs[side] = fns[side]().clone()
         want = ops.weight_image_raw(outs["presplit"]) if image_out else outs["presplit"]
         med = {m: sorted(v)[len(v) // 2] for m, v in t.items()}

@@ -1682,12 +1682,47 @@ struct F32X3 {
   static_assert(LDS_DKV <= CU_LDS, "one workgroup per CU");
 };
 
+// Image forms (IMAGE = true): the head slices are read from, and o is written as, the pre-split
+// activation image of DESIGN 4.26 in place of the f32 values -- the same addresses and row pitch.  A row's head slice
+// is two 128-byte k-blocks m; hi chunk g of a block is at byte 128m + 16g, lo chunk g at 128m + 64 + 16g, and element j
+// of a chunk is column 16 (j >> 2) + 4g + (j & 3) of the block: the bytes split8 gives for those columns.  The LDS
+// images, the fragments and every MFMA are the f32 forms'; only the operand bits' origin and the o store differ.
+typedef uint32_t u32x2_ __attribute__((ext_vector_type(2)));
+// hi / lo chunk g = c & 3 of k-block m = c >> 2 of an image row -> row r of a hi and a lo LDS image.  A chunk's low
+// 8 bytes are head dims 32m + 4g .. + 3 and its high 8 bytes 32m + 16 + 4g .. + 3: half g & 1 of the granules
+// 4m + (g >> 1) and 4m + 2 + (g >> 1).
+__device__ __forceinline__ void x3_put_chunk(char* hi, char* lo, int r, int c, const u32x4_& h, const u32x4_& l) {
+  const int c0 = (c & 4) + ((c & 3) >> 1), half = (c & 1) * 8;
+  const int o0 = at_off(r, c0) + half, o1 = at_off(r, c0 + 2) + half;
+  *reinterpret_cast<u32x2_*>(hi + o0) = u32x2_{h[0], h[1]};
+  *reinterpret_cast<u32x2_*>(hi + o1) = u32x2_{h[2], h[3]};
+  *reinterpret_cast<u32x2_*>(lo + o0) = u32x2_{l[0], l[1]};
+  *reinterpret_cast<u32x2_*>(lo + o1) = u32x2_{l[2], l[3]};
+}
+// the hi (u = 0) / lo (u = 1) chunk c of the image row whose head slice starts at p
+__device__ __forceinline__ u32x4_ x3_chunk(const float* p, int c, int u) {
+  return *reinterpret_cast<const u32x4_*>(reinterpret_cast<const char*>(p) + (c >> 2) * 128 + u * 64 + (c & 3) * 16);
+}
+
 // Rows [0, N) of two f32 head slices -> a hi and a lo bf16 image each (at_off layout, rows >= N zero).
-template <int ROWS>
+// IMAGE: the slices are image rows, copied chunk by chunk.
+template <int ROWS, bool IMAGE = false>
 __device__ __forceinline__ void x3_load2(char* ahi, char* alo, const float* sa, int64_t lda, char* bhi, char* blo,
                                          const float* sb, int64_t ldb, int N) {
   for (int i = threadIdx.x; i < ROWS * 8; i += AT_THREADS) {
     const int r = i >> 3, c = i & 7;
+    if constexpr (IMAGE) {
+      u32x4_ ah = {0u, 0u, 0u, 0u}, al = ah, bh = ah, bl = ah;
+      if (r < N) {
+        ah = x3_chunk(sa + (int64_t)r * lda, c, 0);
+        al = x3_chunk(sa + (int64_t)r * lda, c, 1);
+        bh = x3_chunk(sb + (int64_t)r * ldb, c, 0);
+        bl = x3_chunk(sb + (int64_t)r * ldb, c, 1);
+      }
+      x3_put_chunk(ahi, alo, r, c, ah, al);
+      x3_put_chunk(bhi, blo, r, c, bh, bl);
+      continue;
+    }
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, b0 = a0, b1 = a0;
     if (r < N) {
       a0 = *reinterpret_cast<const f32x4*>(sa + (int64_t)r * lda + c * 8);
@@ -1720,83 +1755,47 @@ __device__ __forceinline__ void x3_store_row(float* p, const f32x4 (&x)[4], floa
     *reinterpret_cast<f32x4*>(p + dt * 16 + 4 * g) = f32x4{x[dt][0] * mul, x[dt][1] * mul, x[dt][2] * mul, x[dt][3] * mul};
 }
 
-template <int NT, bool CAUSAL>
-__global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_fwd_f32x3(const float* __restrict__ qkv,
-                                                                             int64_t ld_qkv, int D, int H, int N,
-                                                                             float scale, float* __restrict__ o,
-                                                                             int64_t ld_o, float* __restrict__ lse) {
-  using X = AtBf16x3;
-  constexpr int NT2 = F32X3<NT>::NT2, ROWS = F32X3<NT>::ROWS, IMG = F32X3<NT>::IMG;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char *Khi = smem, *Klo = smem + IMG, *Vhi = smem + 2 * IMG, *Vlo = smem + 3 * IMG;
-  const X::Img Kimg = {Khi, Klo}, Vimg = {Vhi, Vlo};
-  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
-  const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
-  x3_load2<ROWS>(Khi, Klo, base + D, ld_qkv, Vhi, Vlo, base + 2 * D, ld_qkv, N);
-  const AtOffsets off(lane);
-  __syncthreads();
-  const float c2 = scale * LOG2E;
-  for (int qt = wave; qt < NT; qt += AT_WAVES) {
-    const int q = qt * 16 + (lane & 15);
-    X::Frag qf[2];
-    {
-      f32x4 x[4];
-      x3_row(base + (int64_t)min(q, N - 1) * ld_qkv, g, qf, x);
-    }
-    f32x4 s[NT];
+// x3_row from an image row: the lane's fragment kk is granule c = 4 kk + g of the head slice -- k0 = 8g, half
+// hh = g >> 1 of the chunks ga = 2 (g & 1) and ga + 1 of k-block kk, 8 bytes each, hi then (+ 64) lo.
+__device__ __forceinline__ void x3_row_image(const float* p, int g, AtBf16x3::Frag (&f)[2]) {
+  const char* b = reinterpret_cast<const char*>(p) + (g & 1) * 32 + (g >> 1) * 8;
 #pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-      s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kk = 0; kk < 2; ++kk) {
+    u32x2_ w[4];
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) s[kt] = X::mma(X::row(Kimg, kt * 16, off.row[kk]), qf[kk], s[kt]);
-      if (kt % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // bound K-fragment hoisting (VGPRs)
-    }
-    // keys >= N exist only in the last tile
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if ((NT - 1) * 16 + 4 * g + r >= N) s[NT - 1][r] = -INFINITY;
-    if constexpr (CAUSAL) {
-#pragma unroll
-      for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (kt * 16 + 4 * g + r > q) s[kt][r] = -INFINITY;
-    }
-    float mr[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mr[r] = fmaxf(mr[r], s[kt][r]);
-    float m = fmaxf(fmaxf(mr[0], mr[1]), fmaxf(mr[2], mr[3]));
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    const float mc = m * c2;
-    float lr[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { const float p = fexp2(fmaf(s[kt][r], c2, -mc)); s[kt][r] = p; lr[r] += p; }
-    float l = (lr[0] + lr[1]) + (lr[2] + lr[3]);
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    f32x4 oacc[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < NT2; ++ks) {
-      const f32x4 hi = (2 * ks + 1 < NT) ? s[2 * ks + 1 < NT ? 2 * ks + 1 : 0] : f32x4{0.f, 0.f, 0.f, 0.f};
-      const X::Frag pf = X::pack(s[2 * ks], hi);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) oacc[dt] = X::mma(X::tr(Vimg, ks * 32, off.tr[dt]), pf, oacc[dt]);
-      if (ks % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // bound V-fragment hoisting (VGPRs)
-    }
-    if (q < N) {
-      x3_store_row(o + ((int64_t)b * N + q) * ld_o + h * 64, oacc, 1.0f / l, g);
-      if (g == 0) lse[(int64_t)bh * N + q] = (mc + __log2f(l)) * LN2;
-    }
+    for (int u = 0; u < 4; ++u) w[u] = *reinterpret_cast<const u32x2_*>(b + kk * 128 + (u >> 1) * 64 + (u & 1) * 16);
+    f[kk].hi = __builtin_bit_cast(bf16x8, u32x4_{w[0][0], w[0][1], w[1][0], w[1][1]});
+    f[kk].lo = __builtin_bit_cast(bf16x8, u32x4_{w[2][0], w[2][1], w[3][0], w[3][1]});
   }
 }
+// x3_store_row as an image row: x[2m], x[2m + 1] are the two halves of chunk g of k-block m.  The products are
+// x3_store_row's; split8<1> because mul ends a reciprocal and the asm's operands are not modelled.
+__device__ __forceinline__ void x3_store_row_image(float* p, const f32x4 (&x)[4], float mul, int g) {
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const f32x4 a = {x[2 * m][0] * mul, x[2 * m][1] * mul, x[2 * m][2] * mul, x[2 * m][3] * mul};
+    const f32x4 b = {x[2 * m + 1][0] * mul, x[2 * m + 1][1] * mul, x[2 * m + 1][2] * mul, x[2 * m + 1][3] * mul};
+    bf16x8 h, l;
+    split8<1>(a, b, h, l);
+    char* d = reinterpret_cast<char*>(p) + m * 128 + g * 16;
+    *reinterpret_cast<bf16x8*>(d) = h;
+    *reinterpret_cast<bf16x8*>(d + 64) = l;
+  }
+}
+
+// The resident "high" forward, stated once in attn_x3_fwd.inc: attn_fwd_f32x3 (f32 qkv and o) and
+// attn_fwd_image_x3 (qkv and o hold pre-split images; o and lse are attn_fwd_f32x3's bit for bit, o as
+// its image).
+#define X3_FWD_KERNEL attn_fwd_f32x3
+#define X3_IMAGE 0
+#include "attn_x3_fwd.inc"
+#undef X3_FWD_KERNEL
+#undef X3_IMAGE
+#define X3_FWD_KERNEL attn_fwd_image_x3
+#define X3_IMAGE 1
+#include "attn_x3_fwd.inc"
+#undef X3_FWD_KERNEL
+#undef X3_IMAGE
 
 template <int NT>
 __global__ __launch_bounds__(AT_THREADS, F32X3<NT>::WPS) void attn_bwd_dq_f32x3(
@@ -2546,6 +2545,28 @@ __device__ __forceinline__ SxPiece sx_fetch(const float* sa, int64_t lda, const 
   }
   return p;
 }
+// The same from image rows: this thread's hi (a[0] / b[0]) and lo (a[1] / b[1]) chunk c
+struct SxChunk { u32x4_ a[2], b[2]; };
+__device__ __forceinline__ SxChunk sx_fetch_image(const float* sa, int64_t lda, const float* sb, int64_t ldb, int j0,
+                                                  int N) {
+  const int row = min(j0 + (int)(threadIdx.x >> 3), N - 1), c = threadIdx.x & 7;
+  SxChunk p;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    p.a[u] = x3_chunk(sa + (int64_t)row * lda, c, u);
+    p.b[u] = x3_chunk(sb + (int64_t)row * ldb, c, u);
+  }
+  return p;
+}
+__device__ __forceinline__ void sx_commit(char* buf, SxChunk p, int j0, int N) {
+  const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
+  if (j0 + r >= N) {
+    p.a[0] = u32x4_{0u, 0u, 0u, 0u};
+    p.a[1] = p.a[0]; p.b[0] = p.a[0]; p.b[1] = p.a[0];
+  }
+  x3_put_chunk(buf, buf + ST_IMG, r, c, p.a[0], p.a[1]);
+  x3_put_chunk(buf + 2 * ST_IMG, buf + 3 * ST_IMG, r, c, p.b[0], p.b[1]);
+}
 __device__ __forceinline__ void sx_commit(char* buf, SxPiece p, int j0, int N) {
   const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
   if (j0 + r >= N) {
@@ -2569,9 +2590,17 @@ __device__ __forceinline__ AtBf16x3::Img sx_img(const char* buf, int mtx) {
   return {buf + 2 * mtx * ST_IMG, buf + (2 * mtx + 1) * ST_IMG};
 }
 
-__global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_stream_x3(const float* __restrict__ qkv, int64_t ld_qkv, int D,
-                                                                   int H, int N, float scale, float* __restrict__ o,
-                                                                   int64_t ld_o, float* __restrict__ lse) {
+// The streamed "high" forward, for attn_fwd_stream_x3 (f32 qkv and o) and attn_fwd_image_stream (both as images).
+template <bool IMAGE>
+__device__ __forceinline__ auto sx_fetch_kv(const float* base, int64_t ld_qkv, int D, int j0, int N) {
+  if constexpr (IMAGE)
+    return sx_fetch_image(base + D, ld_qkv, base + 2 * D, ld_qkv, j0, N);
+  else
+    return sx_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0, N);
+}
+template <bool IMAGE>
+__device__ __forceinline__ void sx_fwd(const float* qkv, int64_t ld_qkv, int D, int H, int N, float scale, float* o,
+                                       int64_t ld_o, float* lse) {
   using X = AtBf16x3;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
@@ -2579,13 +2608,15 @@ __global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_stream_x3(const float*
   const float* base = qkv + (int64_t)b * N * ld_qkv + h * 64;
   const int q = blockIdx.y * ST_QB + wave * 16 + (lane & 15);
   X::Frag qf[2];
-  {
+  if constexpr (IMAGE) {
+    x3_row_image(base + (int64_t)min(q, N - 1) * ld_qkv, g, qf);
+  } else {
     f32x4 x[4];
     x3_row(base + (int64_t)min(q, N - 1) * ld_qkv, g, qf, x);
   }
   const AtOffsets off(lane);
   const int nc = (N + ST_CH - 1) / ST_CH;
-  SxPiece pc = sx_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, 0, N);
+  auto pc = sx_fetch_kv<IMAGE>(base, ld_qkv, D, 0, N);
   sx_commit(smem, pc, 0, N);
   __syncthreads();
   const float c2 = scale * LOG2E;
@@ -2599,7 +2630,7 @@ __global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_stream_x3(const float*
     const X::Img Kimg = sx_img(buf, 0), Vimg = sx_img(buf, 1);
     const int j0 = c * ST_CH;
     const bool more = c + 1 < nc;
-    if (more) pc = sx_fetch(base + D, ld_qkv, base + 2 * D, ld_qkv, j0 + ST_CH, N);
+    if (more) pc = sx_fetch_kv<IMAGE>(base, ld_qkv, D, j0 + ST_CH, N);
     f32x4 s[4];
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
@@ -2621,9 +2652,24 @@ __global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_stream_x3(const float*
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
   if (q < N) {
-    x3_store_row(o + ((int64_t)b * N + q) * ld_o + h * 64, oacc, 1.0f / l, g);
+    if constexpr (IMAGE)
+      x3_store_row_image(o + ((int64_t)b * N + q) * ld_o + h * 64, oacc, 1.0f / l, g);
+    else
+      x3_store_row(o + ((int64_t)b * N + q) * ld_o + h * 64, oacc, 1.0f / l, g);
     if (g == 0) lse[(int64_t)bh * N + q] = (m * c2 + __log2f(l)) * LN2;
   }
+}
+__global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_stream_x3(const float* __restrict__ qkv, int64_t ld_qkv, int D,
+                                                                   int H, int N, float scale, float* __restrict__ o,
+                                                                   int64_t ld_o, float* __restrict__ lse) {
+  sx_fwd<false>(qkv, ld_qkv, D, H, N, scale, o, ld_o, lse);
+}
+// qkv and o hold pre-split images; o and lse are attn_fwd_stream_x3's bit for bit (o as its image)
+__global__ __launch_bounds__(AT_THREADS, 4) void attn_fwd_image_stream(const float* __restrict__ qkv, int64_t ld_qkv,
+                                                                         int D, int H, int N, float scale,
+                                                                         float* __restrict__ o, int64_t ld_o,
+                                                                         float* __restrict__ lse) {
+  sx_fwd<true>(qkv, ld_qkv, D, H, N, scale, o, ld_o, lse);
 }
 
 // query-parallel half of the streamed "high" backward: delta = rowsum(dO * O) on the unsplit f32 values (as in
@@ -2835,6 +2881,7 @@ struct F32X3Res : F32X3<NT> {  // bf16x3: F32X3's layout constants and the kerne
   static constexpr int THREADS = AT_THREADS;
   // the mask is a template argument, as in fwd_mfma
   static auto fwd(int causal) { return causal ? attn_fwd_f32x3<NT, true> : attn_fwd_f32x3<NT, false>; }
+  static auto fwd_image(int causal) { return causal ? attn_fwd_image_x3<NT, true> : attn_fwd_image_x3<NT, false>; }
   static auto dq() { return attn_bwd_dq_f32x3<NT>; }
   static auto dkv() { return attn_bwd_dkv_f32x3<NT>; }
 };
@@ -2914,6 +2961,27 @@ static int bwd_f32(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, 
                      (const float*)dout, ld_do, lse, (const float*)delta, (float*)dqkv, ld_dqkv, causal);
   VIT_CHECK_LAUNCH();
   g_f32_split_count += F::SPLIT;
+  return 0;
+}
+// The image form of the resident "high" forward: fwd_f32<F32X3Res<NT>> with qkv and o as pre-split
+// images.  g_f32_image_count: vit_sdpa_fwd_image calls that launched (they count in g_f32_split_count or
+// g_long_f32_split_count too, as the f32 forms do).
+static int g_f32_image_count = 0;
+template <int NT>
+static int fwd_f32_image(const void* qkv, int64_t ld_qkv, int D, int B, int H, int N, float scale, int causal, void* o,
+                         int64_t ld_o, float* lse, hipStream_t s) {
+  using F = F32X3Res<NT>;
+  static bool attr = false;
+  if (!attr) {
+    raise_lds(F::fwd_image(0), F::LDS);
+    raise_lds(F::fwd_image(1), F::LDS);
+    attr = true;
+  }
+  hipLaunchKernelGGL(F::fwd_image(causal), dim3(B * H), dim3(F::THREADS), F::LDS, s, (const float*)qkv, ld_qkv, D, H, N,
+                     scale, (float*)o, ld_o, lse);
+  VIT_CHECK_LAUNCH();
+  ++g_f32_split_count;
+  ++g_f32_image_count;
   return 0;
 }
 // The generic backward: any token count and alignment, causal or not.
@@ -3316,6 +3384,56 @@ int vit_sdpa_fwd(int dtype, int B, int H, int N, int head_dim, const void* qkv, 
     return 0;
   });
 }
+
+// Whether vit_sdpa_fwd_image launches: where vit_sdpa_fwd with f32 tensors of this geometry takes the bf16x3
+// kernels -- mode "high", head_dim 64, every row pitch a multiple of 4 floats, up to 288 tokens (causal or not) or,
+// past them, not causal with the streamed kernels on and the long switch set -- and, one thing more than vit_sdpa_fwd
+// looks at (it takes 16-byte aligned rows on trust), qkv_img and o_img 16-byte aligned.  lse is stored a float at a
+// time and may sit anywhere.
+static bool sdpa_image_ok(int B, int H, int N, int head_dim, int causal, int64_t strides_or, uint64_t ptrs_or) {
+  if (head_dim != 64 || N <= 0 || B <= 0 || H <= 0 || !g_f32_split) return false;
+  const bool aligned = strides_or % 4 == 0 && ptrs_or % 16 == 0;
+  switch (attn_path(VIT_F32, N, causal, aligned)) {
+    case AP_RESIDENT_F32: return true;
+    case AP_STREAM_F32: return stream_f32_split();
+    default: return false;
+  }
+}
+// Host-only query (no GPU call): 1 when vit_sdpa_fwd_image would launch for this geometry, strides_or = ld_qkv | ld_o,
+// ptrs_or = the OR of the addresses of qkv_img and o_img; else 0.
+int vit_sdpa_fwd_takes_image(int B, int H, int N, int head_dim, int causal, int64_t strides_or, uint64_t ptrs_or) {
+  return sdpa_image_ok(B, H, N, head_dim, causal, strides_or, ptrs_or) ? 1 : 0;
+}
+// vit_sdpa_fwd for f32 "high" with qkv and o as pre-split activation images (the f32 row
+// pitches): the bf16x3 kernels' image forms, o the image of vit_sdpa_fwd's o and lse its lse, bit for bit.  Anything
+// else is hipErrorInvalidValue with nothing launched and nothing written: an image is never read as floats.
+int vit_sdpa_fwd_image(int B, int H, int N, int head_dim, const void* qkv_img, int64_t ld_qkv, void* o_img,
+                       int64_t ld_o, float* lse, float scale, int causal, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!qkv_img || !o_img || !lse) return (int)hipErrorInvalidValue;
+  if (!sdpa_image_ok(B, H, N, head_dim, causal, ld_qkv | ld_o, (uint64_t)qkv_img | (uint64_t)o_img))
+    return (int)hipErrorInvalidValue;
+  const int D = H * 64;
+  if (N > AT_RESIDENT_MAX) {
+    static bool attr = false;
+    if (!attr) {
+      raise_lds(attn_fwd_image_stream, SX_LDS);
+      attr = true;
+    }
+    hipLaunchKernelGGL(attn_fwd_image_stream, dim3(B * H, (N + ST_QB - 1) / ST_QB), dim3(AT_THREADS), SX_LDS, s,
+                       (const float*)qkv_img, ld_qkv, D, H, N, scale, (float*)o_img, ld_o, lse);
+    VIT_CHECK_LAUNCH();
+    ++g_long_f32_count;
+    ++g_long_f32_split_count;
+    ++g_f32_image_count;
+    return 0;
+  }
+  return by_tiles(N, [&](auto nt) {
+    return fwd_f32_image<nt()>(qkv_img, ld_qkv, D, B, H, N, scale, causal, o_img, ld_o, lse, s);
+  });
+}
+// Host-side count of vit_sdpa_fwd_image calls that launched; reset != 0 zeroes it.
+int vit_sdpa_f32_image_count(int reset) { return take_count(g_f32_image_count, reset); }
 
 // Query-limited forward: only query 0 of every (b, h) will be read.  bf16, N <= 288, aligned rows: the
 // resident kernel on query tile 0 (rows 0..15 of each image bit for bit vit_sdpa_fwd's; every other row

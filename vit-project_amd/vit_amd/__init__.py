@@ -13,6 +13,7 @@ from .lora import LoRALayer, lora_weight
 from .ops import set_float32_matmul_precision, get_float32_matmul_precision
 from .ops import get_float32_matmul_presplit, get_float32_matmul_presplit_activations, weight_image_bytes
 from .ops import set_float32_attention_precision, get_float32_attention_precision, get_float32_attention_long
+from .ops import get_float32_attention_presplit
 from . import rsa
 from . import clip
 from . import prefix_cache
@@ -31,7 +32,7 @@ __all__ = ["VisionTransformer", "create_model", "cross_entropy", "set_wgrad_over
            "prefix_cache", "VisualPrefixCache", "LoRALayer", "lora_weight", "apply_lora_to_ViT", "unfreeze_lora_layers",
            "set_float32_matmul_precision", "get_float32_matmul_precision", "set_float32_attention_precision",
            "get_float32_attention_precision", "get_float32_attention_long", "get_float32_matmul_presplit",
-           "get_float32_matmul_presplit_activations", "weight_image_bytes"]
+           "get_float32_matmul_presplit_activations", "weight_image_bytes", "get_float32_attention_presplit"]
 
 
 def load_library(path=None):

@@ -93,6 +93,9 @@ SIGNATURES = {
     "vit_sdpa_f32_split_count": [i32],
     "vit_sdpa_f32_long_precision": [i32],
     "vit_sdpa_long_f32_split_count": [i32],
+    "vit_sdpa_fwd_image": [i32, i32, i32, i32, vp, i64, vp, i64, vp, f32, i32, vp],
+    "vit_sdpa_fwd_takes_image": [i32, i32, i32, i32, i32, i64, C.c_uint64],
+    "vit_sdpa_f32_image_count": [i32],
     "vit_sdpa_bwd": [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, f32, i32, vp, vp, i64, vp],
     "vit_sdpa_bwd_partial_floats": [i32, i32, i32],
     "vit_patch_unfold": [i32, i32, i32, i32, i32, i32, vp, vp, vp],

@@ -360,9 +360,14 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
         f32 blocks on the dense chain, where each is read by one GEMM and nothing else.  Both ends must be able to:
         the consumer GEMM has a weight image and takes the MFMA path, and the producer -- the LayerNorm entry this
         chain runs, or fc1 on the pre-split MFMA path itself -- can write an image.  Anything else keeps the f32
-        tensor and today's calls.  proj keeps its f32 operand (attention writes it)."""
+        tensor and today's calls.
+
+        The fourth flag (``set_float32_attention_precision("high", presplit=True)``): ``qkv`` and ``o``
+        travel as images through attention -- both or neither.  The qkv GEMM writes an image (the pre-split MFMA path
+        with its weight image, whatever ``h1`` holds; 3D a multiple of 32), the attention image kernels cover the
+        call, and proj can read one.  Never with fp8 attention."""
         if not fwd_only or ct or T != f32 or not ops.get_float32_matmul_presplit_activations():
-            return False, False, False
+            return False, False, False, False
         if pend is not None:  # ln1 is the fused add + LayerNorm
             ln1_ok = ops.layer_norm_writes_image(h1[sl], pend[0][sl], pend[1][sl], x2[sl], n1w, n1b, add=True)
         else:
@@ -372,8 +377,14 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
         else:
             ln2_ok = ops.layer_norm_writes_image(h2[sl], xm[sl], n2w, n2b)
         fc1_ok = ops.linear_fwd_takes_image(h2[sl], W1, I1)  # fc1 reads I1 on the MFMA path, whatever h2 holds
-        return (ln1_ok and ops.linear_fwd_takes_image(h1[sl], Wqkv, Iqkv), ln2_ok and fc1_ok,
-                fc1_ok and F % 32 == 0 and ops.linear_fwd_takes_image(act[sl], W2, I2))
+        qkv_ok = ops.linear_fwd_takes_image(h1[sl], Wqkv, Iqkv)  # as fc1: qkv reads Iqkv on the MFMA path
+        b0, b1 = sl.start // N, sl.stop // N
+        attn_ok = (qkv_ok and not attn_fp8 and ops.get_float32_attention_presplit() and (3 * D) % 32 == 0
+                   and ops.sdpa_fwd_takes_image(qkv[sl], b1 - b0, H, N, o[sl], lse[b0 * H * N:b1 * H * N],
+                                                causal=causal)
+                   and ops.linear_fwd_takes_image(o[sl], Wproj, Iproj))
+        return (ln1_ok and qkv_ok, ln2_ok and fc1_ok,
+                fc1_ok and F % 32 == 0 and ops.linear_fwd_takes_image(act[sl], W2, I2), attn_ok)
 
     def fc1(sl, x_image=False, out_image=False):
         if fwd_only:
@@ -390,13 +401,13 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
 
     def chain_fused(b0, b1):
         sl = slice(b0 * N, b1 * N)
-        i1, i2, ia = images(sl)
+        i1, i2, ia, io = images(sl)
         steps = [
             ln1(sl, i1),
-            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv, x_image=i1),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv, x_image=i1, out_image=io),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
-                                 fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre),
-            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), out=pb[sl], wimg=Iproj),
+                                 fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre, image=io),
+            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), out=pb[sl], wimg=Iproj, x_image=io),
             lambda: ops.add_layer_norm_fwd(x2[sl], pb[sl], xm[sl], n2w.detach(), n2b.detach(), eps, out=h2[sl],
                                            mean=m2[sl], rstd=r2[sl], out_image=i2),
             fc1(sl, i2, ia),
@@ -454,14 +465,15 @@ def _block_chain(x, params, cfg, fwd_only, attn1=False, row_tail=None):
             return chain_fused(b0, b1)
         r0, r1_ = b0 * N, b1 * N
         sl = slice(r0, r1_)
-        i1, i2, ia = images(sl)
+        i1, i2, ia, io = images(sl)
         return [
             lambda: ops.layer_norm_fwd(x2[sl], n1w.detach(), n1b.detach(), eps, T, out=h1[sl], mean=m1[sl],
                                        rstd=r1[sl], out_image=i1),
-            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv, x_image=i1),
+            lambda: ops.linear_fwd(h1[sl], Wqkv, qkvb.detach(), out=qkv[sl], wimg=Iqkv, x_image=i1, out_image=io),
             lambda: ops.sdpa_fwd(qkv[sl], b1 - b0, H, N, o=o[sl], lse=lse[b0 * H * N:b1 * H * N], causal=causal,
-                                 fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre),
-            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), epi=L.EPI_RESID, resid=x2[sl], out=xm[sl], wimg=Iproj),
+                                 fp8=attn_fp8, fp8_long=attn_fp8_long, fp8_pre=attn_fp8_pre, image=io),
+            lambda: ops.linear_fwd(o[sl], Wproj, projb.detach(), epi=L.EPI_RESID, resid=x2[sl], out=xm[sl], wimg=Iproj,
+                                   x_image=io),
             lambda: ops.layer_norm_fwd(xm[sl], n2w.detach(), n2b.detach(), eps, T, out=h2[sl], mean=m2[sl],
                                        rstd=r2[sl], out_image=i2),
             fc1(sl, i2, ia),

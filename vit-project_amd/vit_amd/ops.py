@@ -522,13 +522,16 @@ def fp8_switches(enable, long_sequences=False, prequantize=False):
     return on, on and bool(long_sequences), on and bool(long_sequences) and bool(prequantize)
 
 
-def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=False, fp8_long=False, fp8_pre=False):
+def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=False, fp8_long=False, fp8_pre=False,
+             image=False):
     """softmax(q k^T * scale) v per (b, h) from the fused qkv [B*N, 3D], any N (past 288 tokens the
     streamed bf16 or f32 kernels, or the generic ones for causal / misaligned rows); fp8: the block-scaled e4m3
     MFMA kernels (forward only: their lse is not the bf16 backward's) -- the resident one up to 320 tokens,
     past that the streamed one if ``fp8_long``, else ValueError.  ``fp8_pre`` (with ``fp8`` and ``fp8_long``,
     past 320 tokens only): K and V are quantised once into a workspace that lives for this call and the
-    pre-quantised kernel streams it -- the streamed kernel's bits."""
+    pre-quantised kernel streams it -- the streamed kernel's bits.  ``image`` (fp32 ``"high"`` only):
+    ``qkv2d`` holds and ``o`` receives the pre-split image of the f32 tensor (vit_sdpa_fwd_image;
+    :func:`sdpa_fwd_takes_image`); a call the image kernels cannot run raises."""
     if fp8:
         check_fp8_tokens(N, long=fp8_long)
     D = H * 64
@@ -537,6 +540,13 @@ def sdpa_fwd(qkv2d, B, H, N, o=None, scale=None, lse=None, causal=False, fp8=Fal
     if lse is None:
         lse = torch.empty(B * H * N, dtype=torch.float32, device=qkv2d.device)
     scale = 64 ** -0.5 if scale is None else scale
+    if image:
+        L.require_gpu(qkv2d)
+        assert not fp8 and qkv2d.dtype == torch.float32 and o.dtype == torch.float32
+        assert qkv2d.stride(1) == 1 and o.stride(1) == 1
+        call("vit_sdpa_fwd_image", B, H, N, 64, ptr(qkv2d), qkv2d.stride(0), ptr(o), o.stride(0), ptr(lse),
+             float(scale), int(causal), _s(qkv2d))
+        return o, lse
     if fp8 and fp8_long and fp8_pre and N > FP8_ATTN_MAX_TOKENS:
         ws = sdpa_fp8_quant_kv(qkv2d, B, H, N)  # from the caching allocator, on this stream; not kept
         return sdpa_fwd_fp8_pre(qkv2d, ws, B, H, N, o=o, scale=scale, lse=lse, causal=causal)
@@ -1052,7 +1062,7 @@ def weight_image_bytes(module_or_params) -> int:
 _F32_ATTENTION = ("highest", "high")  # vit_sdpa_f32_precision 0 / 1
 
 
-def set_float32_attention_precision(precision, long_sequences=False):
+def set_float32_attention_precision(precision, long_sequences=False, presplit=False):
     """The arithmetic of the fp32 attention kernels (f32 operands, head_dim 64, aligned rows): the resident ones
     (up to 288 tokens, causal or not) and, with ``long_sequences=True``, the streamed ones past 288
     tokens (not causal):
@@ -1067,8 +1077,20 @@ def set_float32_attention_precision(precision, long_sequences=False):
 
     ``long_sequences=True`` (with ``"high"`` only; with ``"highest"`` it raises ``ValueError`` and changes
     nothing) also runs streamed f32 attention -- 577 tokens for CLIP ViT-L/14@336px -- as three bf16 products, after
-    ``set_attention_fp8(True, long_sequences=True)``.  Both switches are set on every call, so a call without the
-    keyword switches the long form off; :func:`get_float32_attention_long` reads it.
+    ``set_attention_fp8(True, long_sequences=True)``.  All three switches are set on every call, so a call without a
+    keyword switches that form off; :func:`get_float32_attention_long` reads this one.
+
+    ``presplit=True`` (with ``"high"`` only; with ``"highest"`` it raises ``ValueError`` and changes nothing; DESIGN
+    §4.27) carries pre-split images through attention in forward-only fp32 blocks on the dense chain, where the
+    pre-split activation chain of :func:`set_float32_matmul_precision` runs: the qkv GEMM writes ``qkv`` as an image,
+    the ``"high"`` forward kernels read K, V and Q from it and write ``o`` as one, and proj reads that -- no operand
+    split is left in attention but P's, and none in proj.  The same MFMAs on the same bits, so results and cache keys
+    stay those of ``"high"``.  Both ends or neither: a block whose qkv GEMM cannot write an image, whose attention
+    geometry the image kernels do not cover (:func:`sdpa_fwd_takes_image`) or whose proj cannot read one runs the
+    f32 calls.  Without ``set_float32_matmul_precision("high", presplit_weights=True, presplit_activations=True)``
+    this switch has no effect: the image GEMM forms at both ends exist only on that path.
+    :func:`get_float32_attention_presplit` reads it and ``VIT_F32_ATTENTION_PRESPLIT=1`` beside
+    ``VIT_F32_ATTENTION=high`` sets its initial value.
 
     Independent of the GEMM switch: ``set_float32_matmul_precision("high")`` leaves attention exact, and this
     leaves the GEMMs exact.  Process-wide and read when a kernel is launched; cached frozen-prefix tensors carry the
@@ -1080,8 +1102,12 @@ def set_float32_attention_precision(precision, long_sequences=False):
     if long_sequences and precision != "high":
         raise ValueError('long_sequences=True runs streamed fp32 attention as three bf16 products: it needs '
                          'precision "high"')
+    if presplit and precision != "high":
+        raise ValueError('presplit=True carries hi / lo images through the three-bf16-product attention kernels: it '
+                         'needs precision "high"')
     L.lib().vit_sdpa_f32_precision(_F32_ATTENTION.index(precision))
     L.lib().vit_sdpa_f32_long_precision(1 if long_sequences else 0)
+    _F32_ATTENTION_PRESPLIT[0] = bool(presplit)
 
 
 def get_float32_attention_precision() -> str:
@@ -1095,6 +1121,28 @@ def get_float32_attention_long() -> bool:
     leaves the C switch set and this ``False``: the kernels stay exact.)"""
     lib = L.lib()
     return bool(lib.vit_sdpa_f32_precision(-1) == 1 and lib.vit_sdpa_f32_long_precision(-1) == 1)
+
+
+_F32_ATTENTION_PRESPLIT = [os.environ.get("VIT_F32_ATTENTION_PRESPLIT", "") == "1"]
+
+
+def get_float32_attention_presplit() -> bool:
+    """Whether forward-only fp32 blocks carry pre-split images through attention: ``presplit=True`` of
+    :func:`set_float32_attention_precision` while the mode is ``"high"``.  (``VIT_F32_ATTENTION_PRESPLIT=1`` without
+    ``VIT_F32_ATTENTION=high`` leaves this ``False``.)"""
+    return bool(_F32_ATTENTION_PRESPLIT[0] and L.lib().vit_sdpa_f32_precision(-1) == 1)
+
+
+def sdpa_fwd_takes_image(qkv2d, B, H, N, o, lse=None, causal=False) -> bool:
+    """Whether ``sdpa_fwd(qkv2d, B, H, N, o=o, lse=lse, causal=causal, image=True)`` has a kernel
+    (vit_sdpa_fwd_takes_image, host-only): f32 tensors whose call would take the fp32 ``"high"`` kernels -- the mode,
+    head_dim 64, row pitches that are multiples of 4 floats, 16-byte aligned ``qkv2d`` and ``o`` (``lse`` may sit
+    anywhere), up to 288 tokens or, not causal, past them with ``long_sequences=True``.  Ask before asking the qkv GEMM for an image: the library refuses
+    an image it has no kernel for."""
+    if qkv2d.dtype != torch.float32 or o.dtype != torch.float32 or qkv2d.stride(1) != 1 or o.stride(1) != 1:
+        return False
+    ptrs = qkv2d.data_ptr() | o.data_ptr()
+    return bool(L.lib().vit_sdpa_fwd_takes_image(B, H, N, 64, int(causal), qkv2d.stride(0) | o.stride(0), ptrs))
 
 
 def gemm(P, p_layout, Q, q_layout, M, N, R, out=None, out_dtype=torch.float32, bias=None):

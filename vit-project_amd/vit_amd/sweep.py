@@ -472,9 +472,10 @@ def _sweep_worker(rank, world, make_model_and_optimizer, criterion, data, condit
         ops.set_float32_matmul_precision(mode, presplit_weights=presplit, presplit_activations=presplit_act)
     mode = kw.pop("float32_attention", None)
     long_sequences = kw.pop("float32_attention_long", False)
+    attn_presplit = kw.pop("float32_attention_presplit", False)
     if mode is not None:
         from . import ops
-        ops.set_float32_attention_precision(mode, long_sequences=long_sequences)
+        ops.set_float32_attention_precision(mode, long_sequences=long_sequences, presplit=attn_presplit)
     if devices:
         dev = torch.device("cuda", devices[rank % len(devices)])
         torch.cuda.set_device(dev)
@@ -494,7 +495,8 @@ def launch_sweep(nprocs, make_model_and_optimizer, criterion, data, conditions, 
     The workers run in the caller's fp32 GEMM mode (``set_float32_matmul_precision``, its ``presplit_weights``
     and ``presplit_activations`` switches included; ``VIT_F32_MATMUL``, ``VIT_F32_MATMUL_PRESPLIT`` and
     ``VIT_F32_MATMUL_PRESPLIT_ACT`` are inherited through the environment as well) and fp32 attention mode (``set_float32_attention_precision``,
-    its ``long_sequences`` switch included; ``VIT_F32_ATTENTION``, ``VIT_F32_ATTENTION_LONG``)."""
+    its ``long_sequences`` and ``presplit`` switches included; ``VIT_F32_ATTENTION``, ``VIT_F32_ATTENTION_LONG``,
+    ``VIT_F32_ATTENTION_PRESPLIT``)."""
     import torch.multiprocessing as mp
     from . import _lib, ops
     if cache_visual_prefix:
@@ -504,7 +506,8 @@ def launch_sweep(nprocs, make_model_and_optimizer, criterion, data, conditions, 
                   float32_matmul_presplit=ops.get_float32_matmul_presplit(),
                   float32_matmul_presplit_act=ops.get_float32_matmul_presplit_activations(),
                   float32_attention=ops.get_float32_attention_precision(),
-                  float32_attention_long=ops.get_float32_attention_long())
+                  float32_attention_long=ops.get_float32_attention_long(),
+                  float32_attention_presplit=ops.get_float32_attention_presplit())
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     devices = list(gpus) if gpus else []

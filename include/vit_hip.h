@@ -206,7 +206,10 @@ int vit_linear_dgrad_partial_floats(int M, int K);
 /* F.linear weight gradient dW (f32) = dY^T X, split-K over rows with fp32 slabs
  * in `workspace` (>= split*N*K*4 bytes, else hipErrorInvalidValue with nothing launched) -- autograd of
  * VIT:142.  The slab sum moves 16 bytes at a time: with N*K % 4 != 0, or a workspace or dW that is not 16-byte
- * aligned, the call runs unsplit (the same sum in one pass); a misaligned dW also keeps the generic kernel. */
+ * aligned, the call runs unsplit (the same sum in one pass); a misaligned dW also keeps the generic kernel.
+ * A split call adds the ragged M % 32 rows into the last slab before it sums the slabs (slab 0, then += slab z),
+ * as vit_linear_wgrad_partials does: with at most 8 slabs dW is bit for bit what vit_colreduce_batch makes of
+ * that call's slabs. */
 int vit_linear_wgrad(int dtype, int M, int N, int K, const void* dY, int64_t lddy, const void* X,
                      int64_t ldx, float* dW, int split, void* workspace, int64_t ws_bytes, void* stream);
 /* The same weight gradient as split-K partials only: slabs[z][N*K] f32 for
@@ -243,7 +246,9 @@ int vit_colreduce_multi(const float* part, int nq, int S, int N, float* out0, fl
  * out[N] (+)= sum of the S rows of part [S][N].  Sums run in a fixed order (bitwise reproducible);
  * jobs with more than 64 partial rows combine 64-row chunk partials in-launch (agent-scope
  * release/acquire + a ticket counter per 256-column strip).  scratch / counters sized by
- * vit_colreduce_batch_sizes; counters zero-filled before first use (the kernel leaves them zero). */
+ * vit_colreduce_batch_sizes; counters zero-filled before first use (the kernel leaves them zero).
+ * scratch must be 16-byte aligned; each job that takes scratch gets a slice of it whose size is rounded up to a
+ * multiple of 4 floats (in both functions), so every slice starts on 16 bytes whatever jobs stand in front of it. */
 int vit_colreduce_batch_sizes(const int64_t* jobs, int njobs, int64_t* scratch_floats, int* counters);
 int vit_colreduce_batch(const int64_t* jobs, int njobs, float* scratch, int64_t scratch_floats, int* counters,
                         int ncounters, void* stream);

@@ -165,8 +165,10 @@ def test_linear_wgrad(M, N, K, split):
 def test_linear_wgrad_partials_sum_to_dw(M, N, K, split, dtype):
     """Split-K slabs only (vit_linear_wgrad_partials, reduced later by the block's batch launch):
     their sum is dW, including a ragged M % 32 tail folded into the last slab; through ColBatch
-    the result agrees with the immediate path's reduction to rounding (the batch sums the slabs
-    in a different fixed order)."""
+    the result is the immediate path's reduction bit for bit while there are at most 8 slabs (the
+    batch's short path adds the slabs in splitk_reduce_kernel's order: slab 0, then += slab z;
+    tests/test_gpu_reductions.py pins both orders), and agrees with it to rounding past 8 (the
+    tall path sums 64-row chunks wave by wave)."""
     dy = _rnd(M, N, seed=13, dtype=dtype)
     x = _rnd(M, K, seed=14, dtype=dtype)
     ref = dy.float().T @ x.float()
@@ -181,6 +183,8 @@ def test_linear_wgrad_partials_sum_to_dw(M, N, K, split, dtype):
     _close(out, ref, 2e-5, "wgrad via batch")
     imm = ops.linear_wgrad(dyd, xd, split=split)
     _close(out, imm, 1e-6, "batch vs immediate reduction")
+    if L.lib().vit_linear_wgrad_nslabs(L.dt(dyd), M, N, K, split) <= 8:
+        assert torch.equal(out, imm), "batch vs immediate reduction: not bitwise equal with at most 8 slabs"
 
 
 @pytest.mark.parametrize("M,tail", [(197 * 32, False), (197 * 32, True), (197 * 3, False)])

@@ -138,12 +138,18 @@ __global__ __launch_bounds__(256) void colreduce_batch_kernel(CbJobs jobs, float
 }
 
 bool job_vec_ok(const float* part, int N) { return N % 4 == 0 && ((uintptr_t)part & 15) == 0; }
+// A job's slice of the shared scratch starts on 16 bytes: the running offset is rounded up to 4 floats after
+// every job that takes scratch (a fallback job's ceil(S/64) * N floats need be no multiple of 4, and the
+// ticketed job behind it stores and loads its chunk partials as f32x4).
+int64_t scr_round(int64_t floats) { return (floats + 3) & ~(int64_t)3; }
 }  // namespace
 
 extern "C" {
 
 // jobs: njobs x {part, out, S, N, accumulate} as int64 (host memory).  Scratch floats and
-// counters the batch needs (jobs whose partials take the vector path and span > 64 rows).
+// counters the batch needs (jobs whose partials take the vector path and span > 64 rows, and the
+// second stage of fallback jobs of more than 64 rows).  Every job's slice is rounded up to a multiple
+// of 4 floats, exactly as vit_colreduce_batch hands the slices out, so each starts on 16 bytes.
 int vit_colreduce_batch_sizes(const int64_t* jobs, int njobs, int64_t* scratch_floats, int* counters) {
   int64_t sf = 0;
   int nc = 0;
@@ -154,11 +160,11 @@ int vit_colreduce_batch_sizes(const int64_t* jobs, int njobs, int64_t* scratch_f
     if (job_vec_ok((const float*)q[0], N)) {
       const int chunks = S <= CB_SHORT ? 1 : (S + CB_ROWS - 1) / CB_ROWS;
       if (chunks > 1) {
-        sf += (int64_t)chunks * N;
+        sf = scr_round(sf + (int64_t)chunks * N);
         nc += (N + CB_COLS - 1) / CB_COLS;
       }
     } else {
-      sf += colreduce_scratch_floats(S, N);
+      sf = scr_round(sf + colreduce_scratch_floats(S, N));
     }
   }
   *scratch_floats = sf;
@@ -169,7 +175,9 @@ int vit_colreduce_batch_sizes(const int64_t* jobs, int njobs, int64_t* scratch_f
 // out_i[N_i] (+)= sum over the S_i rows of part_i, for every job, in one launch (16 jobs per
 // launch; jobs whose partials are not 16-B vectors take the two-stage colreduce).  scratch /
 // counters as vit_colreduce_batch_sizes says; counters zero-filled before the first call (the
-// kernel leaves them zero).
+// kernel leaves them zero).  The running scratch offset is rounded up to 4 floats after every job
+// that takes scratch (as in vit_colreduce_batch_sizes): with `scratch` itself on 16 bytes, so is
+// every job's slice, whatever job mix stands in front of it.
 int vit_colreduce_batch(const int64_t* jobs, int njobs, float* scratch, int64_t scratch_floats, int* counters,
                         int ncounters, void* stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -196,7 +204,7 @@ int vit_colreduce_batch(const int64_t* jobs, int njobs, float* scratch, int64_t 
     if (S <= 0 || N <= 0 || !part || !out) continue;
     if (!job_vec_ok(part, N)) {
       launch_colreduce(part, S, N, out, acc, s, scratch + scr);
-      scr += colreduce_scratch_floats(S, N);
+      scr = scr_round(scr + colreduce_scratch_floats(S, N));
       continue;
     }
     CbJob& J = b.j[b.n];
@@ -213,7 +221,7 @@ int vit_colreduce_batch(const int64_t* jobs, int njobs, float* scratch, int64_t 
     wg += J.strips * J.chunks;
     if (J.chunks > 1) {
       cnt0 += J.strips;
-      scr += (int64_t)J.chunks * N;
+      scr = scr_round(scr + (int64_t)J.chunks * N);
     }
     if (++b.n == CB_MAXJ) flush();
   }

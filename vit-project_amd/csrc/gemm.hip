@@ -1822,9 +1822,20 @@ int vit_linear_wgrad(int dtype, int M, int N, int K, const void* dY, int64_t ldd
     rc = gemm_any(EPI_STORE, dtype, VIT_F32, LAY_CR, LAY_CR, N, K, R0, dY, lddy, X, ldx, split, e, s, fast);
     if (rc) return rc;
     const int64_t n = (int64_t)N * K;
+    if (R0 < M) {
+      // the ragged M % 32 rows go into the last slab before the slab sum, as vit_linear_wgrad_partials folds them:
+      // dW is then bit for bit what a vit_colreduce_batch job makes of that call's slabs (at most 8 of them)
+      Epi t = make_epi();
+      t.C = (float*)workspace + (int64_t)(nz - 1) * n; t.ldc = K;
+      const size_t esz = dtype == VIT_BF16 ? 2 : 4;
+      rc = gemm_any(EPI_ACC, dtype, VIT_F32, LAY_CR, LAY_CR, N, K, M - R0, (const char*)dY + (size_t)R0 * lddy * esz,
+                    lddy, (const char*)X + (size_t)R0 * ldx * esz, ldx, 1, t, s, false);
+      if (rc) return rc;
+    }
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, s,
                        (const float*)workspace, nz, n, dW);
     VIT_CHECK_LAUNCH();
+    return 0;
   }
   if (rc || R0 == M) return rc;
   Epi t = make_epi();
